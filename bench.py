@@ -9,9 +9,11 @@ One "step" = one pass of the hot path over one batch of 200 synthetic 3x64x64 im
 i.e. 400 images through forward+backward per step.  Inputs (the whole 8000-image task) are
 resident in HBM before the timed region; batches are gathered on device.
 
-Prints ONE JSON line (rank 0) as the LAST line of stdout, at most LINE_LIMIT bytes (compact_line): the contract's keys,
-`roofline`, `cpu_baseline` and a few scalars.  The full record (everything below) is written to
-gpurun_out/bench_details.json and to stderr as `bench-details: {...}`.  Objects of the full record:
+Prints ONE JSON line (rank 0) as the LAST line of stdout, at most LINE_LIMIT bytes (compact_line).  A plain run
+(`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the contract's keys alone;
+`--dump-outputs DIR` then also writes what the last timed step computed (parameters, momentum, Fisher, gradient, loss,
+running stats) as DIR/<name>.npy.  `--full` adds everything below to the line (`roofline`, `cpu_baseline` and a few
+scalars); its whole record goes to the details file (emit) and to stderr as `bench-details: {...}`.  Objects of the full record:
   roofline      — dominant kernel (by time) vs the fp32-MFMA peak, timed with HIP events on
                   the launch stream inside this process
   cpu_baseline  — the CPU oracle (torch-CPU restatement of the reference path, kind "port")
@@ -109,6 +111,11 @@ def parse():
     ap.add_argument("--sweep-blobs", type=str, default=None, help="tuning: g,amp,noise_lr,q of the sweep's synthetic tasks")
     ap.add_argument("--forced-leg", type=str, default=None, help="internal: run the teacher-forced trainings of this plan file (JSON) on the "
                                                                  "kernel path CLHIP_BS selects")
+    ap.add_argument("--full", action="store_true", help="measure beyond the headline step: per-kernel roofline, the other BASELINE configs, "
+                                                        "the CPU baseline, the sweeps, and the details record (off: set up, warm up, time the "
+                                                        "steps, print the line)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -1447,6 +1454,25 @@ def emit(out):
     print(compact_line(out, path), flush=True)
 
 
+DUMP_LIMIT = 64 << 20    # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: each device tensor as `path`/<name>.npy, float64 kept, every other dtype as float32.  Should the arrays hold
+    more than `limit` bytes together, each is replaced by a fixed sample of its flattened elements (indices drawn from a seeded
+    generator, sorted: the same in every run of the same arguments) so that the files stay within the limit."""
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    if total > limit:
+        rng = np.random.RandomState(0)
+        keep = limit / float(total)
+        host = {k: v.reshape(-1)[np.sort(rng.choice(v.size, int(v.size * keep), replace=False))] for k, v in sorted(host.items())}
+    os.makedirs(path, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def host_cpu():
     model = ""
     try:
@@ -1619,7 +1645,7 @@ def main():
     # then timed INSIDE the timed steps: clhip_net_probe_kind keeps a ring of HIP event pairs around that layer's forward /
     # backward-data / weight-gradient launch on the stream it is issued on, read after the loop
     rows, dom = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         rows = time_kernels(eng, data_x[:N].contiguous(), N, args.kernel_iters)
         # dominant = the kernel INSTANCE with the largest share of a pass (sum over its launches), not the longest single
         # launch; its longest launch is the one probed in situ
@@ -1723,6 +1749,11 @@ def main():
         grid["visible_devices"] = os.environ.get("HIP_VISIBLE_DEVICES", os.environ.get("CUDA_VISIBLE_DEVICES"))
     if not torch.isfinite(A.theta).all():
         raise SystemExit("non-finite parameters after the timed run")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after the last timed one: the updated parameter arena and its momentum, the
+        # accumulated Fisher diagonal, the gradient and loss of the last Fisher batch, the training loss / #correct sums
+        dump_outputs(args.dump_outputs, {"params": A.theta, "momentum": buf, "fisher": fisher, "grad": A.grad,
+                                         "loss": eng.loss, "train_stats": stats})
     probed_us, probed_n = eng.probe_read() if dom is not None else (0.0, 0)
     if dom is not None:
         eng.probe(None)
@@ -1748,14 +1779,16 @@ def main():
     }
     if grid is not None:
         out["grid"] = grid
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         # second number of the line at EVERY N (1 included: the anchor of the curve): the framework itself through
         # `driver --shard` on a bounded task sequence, the same work whatever the world size (every rank takes part)
         try:
             out["sharded_sweep"] = sharded_sweep(local_rank, world)
         except BaseException as e:       # the headline line is printed regardless (stage failures are collective: shard.all_ok)
             out["sharded_sweep"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(compact_line(out), flush=True)        # a plain run: the headline line alone
+    if rank == 0 and args.full:
         agg = {}
         for r in rows:
             a = agg.setdefault(r["kernel"], dict(flops=0.0, sec=0.0, launches=0))

@@ -150,14 +150,16 @@ def test_ebll_autoencoder_grid_host_logic(tmp_path, monkeypatch):
 
 
 def test_task_dataset_cache_passthrough_on_cpu(tmp_path):
-    """load_task_datasets: dict passes through; without a device the file is simply unpickled (no HBM cache)."""
+    """load_task_datasets: dict passes through; without a device the file is simply unpickled (no HBM cache), with one the
+    decoded task lands on it."""
     from clsurvey_amd import data as D
     d = D.synthetic_task(8, 4, 4, 2, hw=8, seed=1)
     assert D.load_task_datasets(d) is d
     p = os.path.join(str(tmp_path), "t.pth.tar")
     torch.save(d, p)
     got = D.load_task_datasets(p)
-    assert sorted(got) == ["test", "train", "val"] and torch.equal(got["train"].x, d["train"].x)
+    assert sorted(got) == ["test", "train", "val"] and torch.equal(got["train"].x.cpu(), d["train"].x)
+    assert got["train"].x.is_cuda == torch.cuda.is_available()
 
 
 # --------------------------------------------------------------------------- G9: the PRODUCT's schedules vs the reference's
@@ -861,3 +863,34 @@ def test_bench_last_line_is_compact_and_parseable():
     assert len(line) <= bench.LINE_LIMIT
     rec = json.loads(line)
     assert rec["value"] == float("%.6g" % full["value"]) and "roofline" in rec and "cpu_baseline" in rec
+
+
+def test_bench_plain_run_flags_and_output_dump(tmp_path, monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` leaves `--full` off; `--dump-outputs DIR` writes DIR/<name>.npy as float32 (float64
+    kept), and an output larger than the limit is cut to the same seeded sample in every run, within the limit."""
+    import importlib.util
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+    out = {"params": torch.arange(10, dtype=torch.float32), "loss": torch.tensor([2.5], dtype=torch.float16),
+           "train_stats": torch.tensor([1.0, 2.0], dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in out}
+    assert got["params"].dtype == np.float32 and got["loss"].dtype == np.float32 and got["train_stats"].dtype == np.float64
+    assert np.array_equal(got["params"], np.arange(10, dtype=np.float32)) and got["train_stats"].tolist() == [1.0, 2.0]
+    big = {"x": torch.randn(5000), "y": torch.randn(3000, dtype=torch.float64)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, limit=16000)
+    b = {n: np.load(str(tmp_path / "b" / (n + ".npy"))) for n in big}
+    c = {n: np.load(str(tmp_path / "c" / (n + ".npy"))) for n in big}
+    assert sum(v.nbytes for v in b.values()) <= 16000 and all(np.array_equal(b[n], c[n]) for n in big)
+    assert set(b["x"].tolist()) <= set(big["x"].numpy().tolist())

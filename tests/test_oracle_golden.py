@@ -668,13 +668,22 @@ def test_model_name_training_step_oracle_matches_reference_g34(golden):
         assert float(np.abs(logits.numpy() - ref_logits).max()) <= 1e-5 * float(np.abs(ref_logits).max()), name
         assert abs(float(loss) - float(g[name + "__loss"][0])) <= 1e-5 * abs(float(g[name + "__loss"][0]))
         gmax = max(float(t.abs().max()) for t in grads)
+        # the bias of a conv that feeds a train-mode BatchNorm has an exactly zero gradient (the batch mean cancels it): both sides
+        # hold fp32 round-off there, whose bits depend on the host's reduction order, so it is held to zero at the gradients' scale
+        feats = list(m.features.named_children())
+        zero_grad = {"features.%s.bias" % a for (a, c), (_, b) in zip(feats, feats[1:])
+                     if isinstance(c, torch.nn.Conv2d) and isinstance(b, torch.nn.BatchNorm2d)}
         for j, ((n, _), t) in enumerate(zip(named, grads)):
             v, sums = g["%s__grad_%s__v" % (name, n)], g["%s__grad_%s__s" % (name, n)]
             got = t.numpy().reshape(-1)
             assert got.size == int(sums[2])
-            e = float(np.abs(got[GC.positions(got.size, 3500 + 50 * k + j)] - v).max()) / max(float(np.abs(v).max()), 1e-4 * gmax)
-            assert e <= 1e-5, (name, n, e)
-            assert abs(float(got.astype(np.float64).sum()) - float(sums[0])) <= 1e-5 * float(sums[1]) + 1e-12, (name, n)
+            if n in zero_grad:
+                assert max(float(np.abs(got).max()), float(np.abs(v).max())) <= 1e-5 * gmax, (name, n)
+                assert max(abs(float(got.astype(np.float64).sum())), abs(float(sums[0]))) <= 1e-5 * gmax * got.size, (name, n)
+            else:
+                e = float(np.abs(got[GC.positions(got.size, 3500 + 50 * k + j)] - v).max()) / max(float(np.abs(v).max()), 1e-4 * gmax)
+                assert e <= 1e-5, (name, n, e)
+                assert abs(float(got.astype(np.float64).sum()) - float(sums[0])) <= 1e-5 * float(sums[1]) + 1e-12, (name, n)
         for n, b in m.named_buffers():
             ref = g["%s__buf_%s" % (name, n)]
             if b.dtype == torch.float32:

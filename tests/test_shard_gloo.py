@@ -72,6 +72,7 @@ def _worker(rank, world, port, tmp):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from clsurvey_amd.framework import driver, shard
+    torch.cuda.is_available = lambda: False     # the gloo ranks of this test run on the host (LOCAL_RANK may exceed a box's GPU count)
     assert shard.init_from_env("gloo") == (rank, world)
     # --- collectives
     got = shard.gather_scalars({rank: 0.1 * (rank + 1), rank + 2: 0.5 + rank})
@@ -260,6 +261,7 @@ def _worker_groups(rank, world, port, tmp):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from clsurvey_amd.framework import driver, shard
+    torch.cuda.is_available = lambda: False     # the gloo ranks of this test run on the host (LOCAL_RANK may exceed a box's GPU count)
     assert shard.init_from_env("gloo") == (rank, world)
     assert shard.split_ranks(2, 8) == [[0, 1, 2, 3], [4, 5, 6, 7]] and shard.split_ranks(3, 8) == [[0, 1, 2], [3, 4, 5], [6, 7]]
     gi, blocks = shard.enter_method_groups(2)

@@ -13,3 +13,4 @@ bash tools/gpu_traffic.sh $TAG/traffic_dgrad dgrad_unpool 200 64 64 32 5 > gpuru
 bash tools/gpu_prof.sh $TAG/bench "--no-cpu-baseline --no-configs --no-sweep" > gpurun_out/$TAG/prof.log 2>&1
 find gpurun_out/$TAG -type d -name "*FETCH_SIZE" -o -type d -name "*WRITE_SIZE" | xargs rm -rf
 ls gpurun_out/$TAG
+ls ${OUT:-out}/$TAG    # the bench line + kernel stats: gpu_prof.sh writes under $OUT
