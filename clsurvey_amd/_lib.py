@@ -148,6 +148,9 @@ SIGNATURES = {
     "clhip_net_forward": (_i, [_p, _p, _p, _i, _p, _p, _p]),
     "clhip_net_backward": (_i, [_p, _p, _p, _p, _i, _p, _p, _p]),
     "clhip_net_loss_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "clhip_rehearsal_assemble": (_i, [_p, _p, _i, _z, _p, _p, _l, _l, _i, _p, _i, _p, _p, _p]),
+    "clhip_softmax_ce_segments": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "clhip_net_loss_step_segments": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -60,6 +60,8 @@ def build_parser():
     p.add_argument("--num_epochs", type=int, default=70)
     p.add_argument("--weight_decay", type=float, default=0)
     p.add_argument("--batch_size", type=int, default=200)
+    # exemplars per task of the rehearsal baselines (the reference defines it in debug runmode only, main.py:276)
+    p.add_argument("--mem_per_task", type=int, default=None)
     p.add_argument("--test", action="store_true")
     p.add_argument("--test_max_task_count", type=int, default=None)
     p.add_argument("--test_starting_task_count", type=int, default=1)

@@ -3,7 +3,8 @@ model load / wrap, postprocess = exemplar collection for the first-task model) a
 rehearsal/train_rehearsal.py:train_model (epoch / phase loop, count-based LR decay and early stop).
 
 Per training batch: GemNet.observe (memory passes + current pass through clhip_net_loss_step_slice, one
-Gram pass, host QP, projection, SGD) or observe_FT in the phase-1 grid; validation through eval_batch.
+Gram pass, host QP, projection, SGD) or observe_FT in the phase-1 grid; the rehearsal baselines' RehearsalNet.observe_FT
+(rehearsal.py: one assembled pass over current batch + exemplars); validation through eval_batch.
 Loss / hit counters stay on the device and are read once per phase.
 """
 import argparse
@@ -12,11 +13,13 @@ import math
 import os
 import time
 
+import numpy as np
 import torch
 from ..data import load_task_datasets
 
 from ..data import DeviceLoader
 from . import gem as G
+from . import rehearsal as R
 from .train_common import set_lr
 
 
@@ -103,8 +106,27 @@ def train_model(model, args, dset_sizes, resume="", save_models_mode=False, savi
     return model, best_acc
 
 
+BASELINES = ("baseline_rehearsal_partial_mem", "baseline_rehearsal_full_mem")
+
+
+def exemplar_split(args, dset_sizes):
+    """main_rehearsal.py:187-202, AFTER the loaders were made with the original batch size (:181): n_append exemplars per
+    step; args.batch_size becomes the exemplar chunk size.  Returns the rows of one step (original batch + n_append).
+    (The args.debug branch, :200, cannot be reached from the framework: overwrite_args never carries debug.)"""
+    if args.method == "baseline_rehearsal_partial_mem":
+        n_mem_samples = args.n_memories * args.task_idx
+    else:
+        n_mem_samples = args.n_memories * args.n_tasks
+    ratio = float(n_mem_samples) / (float(dset_sizes["train"]) + n_mem_samples)
+    args.n_exemplars_to_append_per_batch = int(np.ceil(args.batch_size * ratio))
+    args.total_batch_size = args.batch_size
+    args.batch_size = args.batch_size - args.n_exemplars_to_append_per_batch
+    print("BATCH CONSISTS OF: {} new samples, {} exemplars".format(args.batch_size, args.n_exemplars_to_append_per_batch))
+    return args.total_batch_size + args.n_exemplars_to_append_per_batch
+
+
 def main(overwrite_args, nc_per_task, device="cuda"):
-    """main_rehearsal.py:69-255 for method == 'gem'."""
+    """main_rehearsal.py:69-255 for method 'gem' and the rehearsal baselines ('baseline_rehearsal_{partial,full}_mem')."""
     parser = argparse.ArgumentParser()
     for name, kw in (("--task_name", dict(type=str)), ("--task_count", dict(type=int)),
                      ("--prev_model_path", dict(type=str)), ("--save_path", dict(type=str, default="results/")),
@@ -120,11 +142,16 @@ def main(overwrite_args, nc_per_task, device="cuda"):
     for key_arg, val_arg in overwrite_args.items():
         setattr(args, key_arg, val_arg)
     args.task_idx = args.task_count - 1
-    if args.method != "gem":
-        raise NotImplementedError("rehearsal method %r (iCaRL / rehearsal baselines are out of scope)" % args.method)
+    args.n_exemplars_to_append_per_batch = 0
+    baseline = args.method in BASELINES                              # main_rehearsal.py:152-159
+    if baseline:
+        args.finetune = True
+        args.full_mem_mode = args.method == "baseline_rehearsal_full_mem"
+    elif args.method != "gem":
+        raise NotImplementedError("rehearsal method %r (iCaRL is out of scope)" % args.method)
     assert args.n_outputs == sum(args.nc_per_task)
     assert args.n_tasks == len(nc_per_task)
-    if args.task_count == 1:
+    if args.task_count == 1 and not baseline:
         assert "SI" in args.prev_model_path, "FIRST TASK NOT STARTING FROM SCRATCH, BUT FROM SI: ONLY STORING WRAPPER " \
                                              "WITH EXEMPLARS, path = {}".format(args.prev_model_path)
         assert args.postprocess, "FIRST TASK WE DO ONLY POSTPROCESSING"
@@ -135,8 +162,21 @@ def main(overwrite_args, nc_per_task, device="cuda"):
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}
     in_shape = tuple(args.dset_loaders["train"].x.shape[1:])
+    if baseline:
+        step_rows = exemplar_split(args, dset_sizes)
 
-    if args.is_scratch_model:
+    if baseline:
+        if args.is_scratch_model:
+            assert args.task_idx == 0
+            raw = R.replace_head(torch.load(args.prev_model_path, weights_only=False), args.n_outputs)    # :36-41
+            model = R.RehearsalNet(raw, args.n_outputs, args.n_tasks, args.nc_per_task, args.n_memories, args.lr,
+                                   args.weight_decay, args.full_mem_mode, step_rows, in_shape, device)
+        else:
+            model = torch.load(args.prev_model_path, weights_only=False)
+            if model.batch_size < step_rows:
+                model.batch_size = step_rows
+                model._bind()
+    elif args.is_scratch_model:
         assert args.task_idx == 0
         raw = torch.load(args.prev_model_path, weights_only=False)
         raw = G.extend_head(raw, args.n_outputs)                   # gem.py:96-113

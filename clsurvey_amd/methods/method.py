@@ -366,6 +366,24 @@ def _gem_poststep(self, args, manager):
     manager.best_model_path = target
 
 
+# ------------------------------------------------------------------------------------------------ rehearsal baselines
+def _rehearsal_grid_train(self, args, manager, lr):
+    """FinetuneRehearsalFullMem.grid_train (method.py:1139-1165; the partial-memory class calls the same).  Two of its
+    inputs do not exist in the reference as shipped: `manager.datasets.get_nc_per_task(...)` (:1143; Manager has no
+    `datasets`, the intent is data.dataset.get_nc_per_task(manager.dataset)) and args.mem_per_task, which its CLI sets
+    only in debug runmode (framework/main.py:276); here it is the driver's --mem_per_task."""
+    if getattr(args, "mem_per_task", None) is None:
+        raise ValueError("%s needs the exemplar memory per task: pass --mem_per_task" % self.name)
+    nc = _classes_per_task(manager)
+    kw = dict(weight_decay=args.weight_decay, task_name=args.task_name, task_count=args.task_counter,
+              prev_model_path=manager.previous_task_model_path, save_path=manager.gridsearch_exp_dir, n_outputs=sum(nc),
+              method=self.arg_string, n_memories=args.mem_per_task, n_epochs=args.num_epochs, cuda=True,
+              dataset_path=manager.current_task_dataset_path, n_tasks=manager.dataset.task_count,
+              batch_size=args.batch_size, lr=lr, finetune=True, is_scratch_model=args.task_counter == 1)
+    manager.overwrite_args = kw
+    return _gem.main(kw, nc, device=_dev(args))
+
+
 # ------------------------------------------------------------------------------------------------ IMM / LwF / EBLL extras
 def _imm_init(self, mode="mode"):
     self.set_mode(mode)
@@ -483,6 +501,15 @@ SPECS = [
           flags=("wrap_first_task_model",), phase1=None, output="gem_slice", evaluate="as_is",
           hooks={"grid_train": _gem_grid_train, "train": _gem_train, "poststep": _gem_poststep},
           doc="gradient episodic memory; task 1 only wraps the shared SI model with its exemplars (method.py:281-412)"),
+    _spec("finetuning_rehearsal_partial_mem", Category.BASELINE, flags=("grid_chkpt", "start_scratch", "no_framework"),
+          output="gem_slice", evaluate="as_is", attrs={"arg_string": "baseline_rehearsal_partial_mem"},
+          hooks={"grid_train": _rehearsal_grid_train, "grid_poststep": staticmethod(_adopt_grid_winner)},
+          doc="finetuning + replay of a fixed exemplar memory per task (R-PM, method.py:1090-1118); grid only"),
+    _spec("finetuning_rehearsal_full_mem", Category.BASELINE, flags=("grid_chkpt", "start_scratch", "no_framework"),
+          output="gem_slice", evaluate="as_is", attrs={"arg_string": "baseline_rehearsal_full_mem"},
+          hooks={"grid_train": _rehearsal_grid_train, "grid_poststep": staticmethod(_adopt_grid_winner)},
+          doc="finetuning + replay of one fixed total memory shared out among the tasks seen (R-FM, method.py:1121-1183); "
+              "grid only"),
 ]
 
 
@@ -529,7 +556,8 @@ def _build_class(spec):
     ns.update(spec["hooks"])
     if spec["phase2"] is None and "train" not in spec["hooks"]:
         ns["train"] = None                      # grid-only methods have no phase 2; the drivers never ask for it
-    cls_name = {"finetuning": "Finetune", "packnet": "PackNet"}.get(spec["name"], spec["name"])
+    cls_name = {"finetuning": "Finetune", "packnet": "PackNet", "finetuning_rehearsal_partial_mem": "FinetuneRehearsalPartialMem",
+                "finetuning_rehearsal_full_mem": "FinetuneRehearsalFullMem"}.get(spec["name"], spec["name"])
     return type(cls_name, (Method,), ns)
 
 

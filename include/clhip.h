@@ -468,6 +468,39 @@ int clhip_gem_qp(const double* gram_f64, int m, double margin, double eps, doubl
 int clhip_gem_project_dev(const float* G, size_t ld, const int* row_idx_host, const double* v_dev_f64, const int* info_dev,
                           int m, const float* g, float* out, size_t n, void* stream);
 
+/* ------------------------------------------------------------------ rehearsal baselines
+ * rehearsal/model/baseline_rehearsal_partial_mem.py:125-253 (observe_FT; full_mem.py is the same class): the reference runs
+ * one forward / backward per exemplar chunk of every past task (:205-234) and one for the current batch (:238-247).
+ * Without BatchNorm a sample's forward does not depend on the rest of the batch and the step's dropout mask rows are
+ * shared by every pass (:97-111), so the step is ONE pass over [current batch | exemplar chunks] with per-row slices.
+ *
+ *   rehearsal_assemble  one launch, no allocation, no synchronisation; bitwise copies (16-byte vectors when row_elems % 4
+ *                       == 0 and the tensors are 16-byte aligned):
+ *                         x[0:B)                -> x_mix[0:B)                        (labels -> labels_mix)
+ *                         x[0:ring_rows)        -> store rows [ring_row0, +ring_rows)  the ring-buffer update (:170-186)
+ *                         store[gather_rows[e]] -> x_mix[B + e], e < E                the exemplar chunks (:214-234)
+ *                       gather_rows (device int32[E]) hold store row indices of PAST tasks (never the ring rows).
+ *                       store rows >= store_rows are not read (label -1).  B + ring_rows + E <= 65535.
+ *   softmax_ce_segments segs (device, n_segs <= CLHIP_CE_MAX_SEGS) cover rows of logits[N][ld], N <= 1024:
+ *                         loss = sum_g scale_g * mean_{i in g} CE_i over row i's class slice [col_off, col_off + ncols)
+ *                         dlogits[i] = scale_g / |g| * (softmax - onehot) inside the slice, 0 outside (and 0 for rows of no
+ *                         segment); stats[0] += loss, stats[1] += #hits of segment 0 (arg-max, lowest index on ties).
+ *                       Segment 0 = the current batch with scale 1, chunk c of `count` chunks has scale 1 / count:
+ *                       new_task_loss + sum_c CE_mean(c) / count (:236, :248).  Fixed summation order.  A malformed
+ *                       segment or a label outside its slice makes the loss NaN.
+ *   net_loss_step_segments  per-layer forward (every layer, no fused tail) + softmax_ce_segments + backward in one call:
+ *                       the whole observe_FT step of a plan without BatchNorm.                                          */
+#define CLHIP_CE_MAX_SEGS 256
+typedef struct clhip_ce_segment { int row_begin; int row_end; int col_off; int ncols; float scale; } clhip_ce_segment;
+int clhip_rehearsal_assemble(const float* x, const int64_t* labels_i64, int B, size_t row_elems, float* store_x,
+                             int64_t* store_labels, long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
+                             int E, float* x_mix, int64_t* labels_mix, void* stream);
+int clhip_softmax_ce_segments(const float* logits, const int64_t* labels_i64, int N, int ld, const clhip_ce_segment* segs,
+                              int n_segs, float* dlogits, float* loss_out, double* stats, void* stream);
+int clhip_net_loss_step_segments(void* handle, const float* params, float* grads, const float* x, const int64_t* labels_i64,
+                                 int N, const clhip_ce_segment* segs, int n_segs, void* ws, float* loss_out, double* stats,
+                                 float* logits_out, void* stream);
+
 #ifdef CLHIP_VISIBILITY_PUSHED
 #pragma GCC visibility pop
 #undef CLHIP_VISIBILITY_PUSHED
