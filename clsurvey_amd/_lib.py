@@ -151,6 +151,8 @@ SIGNATURES = {
     "clhip_rehearsal_assemble": (_i, [_p, _p, _i, _z, _p, _p, _l, _l, _i, _p, _i, _p, _p, _p]),
     "clhip_softmax_ce_segments": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
     "clhip_net_loss_step_segments": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "clhip_gather_tasks": (_i, [_p, _i, _z, _p, _i, _p, _p, _p]),
+    "clhip_slice_argmax_count": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

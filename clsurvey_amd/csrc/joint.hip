@@ -1,0 +1,135 @@
+// Joint baseline (methods/method.py:1185-1235): one model on all tasks at once.
+//   gather_tasks        a batch out of T per-task tensors by GLOBAL sample number (data/imgfolder.py:244-272
+//                       ConcatDatasetDynamicLabels.__getitem__) — no merged copy of the sequence in HBM.
+//   slice_argmax_count  framework/inference.py:141-149 for one batch: arg-max inside the task's output slice against the
+//                       task-local label, per-class correct / total counters.
+#include "common.hpp"
+
+namespace {
+
+constexpr int GT_BLOCK = 256;
+constexpr int GT_VEC_PER_THREAD = 4;      // float4 per thread, all in flight at once: 16 KB per block, 3 blocks per 3x64x64 row
+constexpr int SA_BLOCK = 256;             // 4 waves, one logits row each
+
+// blockIdx.y = destination row, blockIdx.x walks the row in 16 KB segments.  Everything that selects the source is
+// block-uniform (scalar loads of idx / the table).  A sample number outside [0, total) copies nothing and writes label -1
+// (the host checks the permutation before it is uploaded; this only keeps a bad one from faulting).
+__global__ __launch_bounds__(GT_BLOCK) void gather_tasks_kernel(const clhip_task_src* __restrict__ tasks, int T, size_t row_elems,
+                                                                 const int64_t* __restrict__ idx, float* __restrict__ x_out,
+                                                                 int64_t* __restrict__ labels_out) {
+    const int r = blockIdx.y;
+    const int64_t g = idx[r];
+    // first task whose cumulative count exceeds g (bisect_right): lane j of every wave looks at task j (T <= 64) and the
+    // counts are monotone, so it is the number of lanes that answer "not yet" — one load latency, not a chain of T
+    const int lane = threadIdx.x & 63;
+    const int64_t cum = lane < T ? tasks[lane].cum_rows : INT64_MAX;
+    const int t = __popcll(__ballot(cum <= g));
+    if (g < 0 || t >= T) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) labels_out[r] = -1;
+        return;
+    }
+    const int64_t local = g - (t ? tasks[t - 1].cum_rows : 0);
+    const float* src = tasks[t].x + (size_t)local * row_elems;
+    float* dst = x_out + (size_t)r * row_elems;
+    if (blockIdx.x == 0 && threadIdx.x == 0) labels_out[r] = tasks[t].labels[local] + tasks[t].label_shift;
+    const size_t seg = (size_t)GT_BLOCK * GT_VEC_PER_THREAD * 4;          // elements per block
+    if (row_elems % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
+        const size_t nvec = row_elems / 4;
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        const size_t base = (size_t)blockIdx.x * GT_BLOCK * GT_VEC_PER_THREAD + threadIdx.x;
+        float4 v[GT_VEC_PER_THREAD];
+#pragma unroll
+        for (int k = 0; k < GT_VEC_PER_THREAD; ++k) {                     // all loads in flight before the first store
+            const size_t i = base + (size_t)k * GT_BLOCK;
+            if (i < nvec) v[k] = s4[i];
+        }
+#pragma unroll
+        for (int k = 0; k < GT_VEC_PER_THREAD; ++k) {
+            const size_t i = base + (size_t)k * GT_BLOCK;
+            if (i < nvec) d4[i] = v[k];
+        }
+    } else {
+        const size_t end = min(row_elems, ((size_t)blockIdx.x + 1) * seg);
+        for (size_t i = (size_t)blockIdx.x * seg + threadIdx.x; i < end; i += GT_BLOCK) dst[i] = src[i];
+    }
+}
+
+// torch.max over a row on the CPU: the first NaN wins, otherwise the largest value, lowest position on ties.
+__device__ __forceinline__ bool sa_better(float a, int ia, float b, int ib) {
+    const bool na = a != a, nb = b != b;
+    if (na != nb) return na;
+    if (!na && a != b) return a > b;
+    return ia < ib;
+}
+
+// One wave per row: lanes stride the K columns of the slice, butterfly over (value, position), lane 0 counts.
+__global__ __launch_bounds__(SA_BLOCK) void slice_argmax_count_kernel(const float* __restrict__ logits, int N, int ld,
+                                                                       const int* __restrict__ cols, int K,
+                                                                       const int64_t* __restrict__ labels,
+                                                                       unsigned long long* __restrict__ correct,
+                                                                       unsigned long long* __restrict__ total,
+                                                                       unsigned long long* __restrict__ out_of_range) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (SA_BLOCK / 64) + (threadIdx.x >> 6);
+    if (row >= N) return;                            // wave-uniform
+    const float* z = logits + (size_t)row * ld;
+    float best = -INFINITY;
+    int at = 0x7fffffff;
+    bool bad_col = false;
+    for (int k = lane; k < K; k += 64) {
+        const int c = cols[k];
+        if (c < 0 || c >= ld) { bad_col = true; continue; }               // never read outside the row
+        const float v = z[c];
+        if (at == 0x7fffffff || sa_better(v, k, best, at)) { best = v; at = k; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oa = __shfl_xor(at, o, 64);
+        if (oa != 0x7fffffff && (at == 0x7fffffff || sa_better(ov, oa, best, at))) { best = ov; at = oa; }
+    }
+    const bool any_bad_col = __any(bad_col);
+    if (lane == 0) {
+        const int64_t y = labels[row];
+        if (y < 0 || y >= K || any_bad_col) {
+            atomicAdd(out_of_range, 1ULL);
+        } else {
+            atomicAdd(total + y, 1ULL);
+            if ((int64_t)at == y) atomicAdd(correct + y, 1ULL);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int clhip_gather_tasks(const clhip_task_src* tasks_dev, int T, size_t row_elems, const int64_t* idx, int B, float* x_out,
+                       int64_t* labels_out, void* stream) {
+    if (!tasks_dev || T < 1 || T > CLHIP_MAX_TASKS || row_elems == 0 || B < 0) return CLHIP_EINVAL;
+    if (B == 0) return 0;
+    if (!idx || !x_out || !labels_out || B > 65535) return CLHIP_EINVAL;
+    const size_t seg = (size_t)GT_BLOCK * GT_VEC_PER_THREAD * 4;
+    const size_t segs = (row_elems + seg - 1) / seg;
+    if (segs > 0x7fffffffull) return CLHIP_EINVAL;
+    hipLaunchKernelGGL(gather_tasks_kernel, dim3((unsigned)segs, (unsigned)B), dim3(GT_BLOCK), 0, as_stream(stream), tasks_dev, T,
+                       row_elems, idx, x_out, labels_out);
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols, int K, const int64_t* labels_i64,
+                             int64_t* correct, int64_t* total, int64_t* out_of_range, void* stream) {
+    if (!logits || !cols || !labels_i64 || !correct || !total || !out_of_range) return CLHIP_EINVAL;
+    if (N < 0 || ld < 1 || K < 1 || K > ld) return CLHIP_EINVAL;
+    if (N == 0) return 0;
+    const int rows_per_block = SA_BLOCK / 64;
+    hipLaunchKernelGGL(slice_argmax_count_kernel, dim3((unsigned)((N + rows_per_block - 1) / rows_per_block)), dim3(SA_BLOCK), 0,
+                       as_stream(stream), logits, N, ld, cols, K, labels_i64, reinterpret_cast<unsigned long long*>(correct),
+                       reinterpret_cast<unsigned long long*>(total), reinterpret_cast<unsigned long long*>(out_of_range));
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -117,6 +117,73 @@ class DeviceLoader:
                 yield self.x.index_select(0, idx), self.y.index_select(0, idx)
 
 
+class TaskList(Dataset):
+    """Several tasks as ONE dataset without a merged copy (data/imgfolder.py:244-272 ConcatDatasetDynamicLabels): it holds
+    references to the per-task tensors `load_task_datasets` caches, labels of task j are shifted by the class counts of the
+    tasks before it, global sample number -> (task, row) as torch's ConcatDataset does it (first task whose cumulative
+    size exceeds the number)."""
+
+    def __init__(self, dsets, classes_len=None):
+        import itertools
+        self.datasets = list(dsets)
+        assert self.datasets, "TaskList needs at least one task"
+        classes_len = [len(d.classes) for d in self.datasets] if classes_len is None else list(classes_len)
+        self.cumulative_sizes = list(itertools.accumulate(len(d) for d in self.datasets))
+        self.cumulative_classes_len = list(itertools.accumulate(classes_len))
+        self.label_shifts = [0] + self.cumulative_classes_len[:-1]
+        self.classes = [c for d in self.datasets for c in d.classes]
+
+    def __len__(self):
+        return self.cumulative_sizes[-1]
+
+    def locate(self, idx):
+        """int64 tensor of global sample numbers -> (task, local row, label shift) tensors; IndexError outside [0, len)."""
+        idx = torch.as_tensor(idx, dtype=torch.int64)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
+            raise IndexError("TaskList: sample number outside [0, %d)" % len(self))
+        cum = torch.tensor(self.cumulative_sizes, dtype=torch.int64)
+        task = torch.bucketize(idx, cum, right=True)
+        start = torch.cat([torch.zeros(1, dtype=torch.int64), cum[:-1]])
+        return task, idx - start[task], torch.tensor(self.label_shifts, dtype=torch.int64)[task]
+
+    def __getitem__(self, i):
+        task, row, shift = (int(v) for v in self.locate([int(i)]))
+        x, y = self.datasets[task][row]
+        return x, y + shift
+
+
+class MultiTaskLoader(DeviceLoader):
+    """DeviceLoader over a TaskList: same length, order and consumption of the global RNG, but a batch is gathered straight
+    out of the per-task tensors (clhip_gather_tasks) — the merged copy `ConcatTasks` makes (a second copy in HBM of every
+    task the cache already holds) is never built."""
+
+    def __init__(self, dataset, batch_size, shuffle, device="cuda"):
+        from . import ops
+        self.dataset = dataset
+        self.batch_size = int(batch_size)
+        self.shuffle = bool(shuffle)
+        self.device = torch.device(device)
+        self.n = len(dataset)
+        xs = [d.x for d in dataset.datasets]
+        ys = [d.y for d in dataset.datasets]
+        self.row_shape = tuple(xs[0].shape[1:])
+        assert all(tuple(x.shape[1:]) == self.row_shape for x in xs), "tasks of one sequence share the image shape"
+        self.row_elems = int(xs[0][0].numel())
+        self.x = xs[0][:0]                      # (row shape only: what engine_for reads; no memory)
+        self.table = ops.task_table(xs, ys, dataset.cumulative_sizes, dataset.label_shifts, self.device)
+
+    def __iter__(self):
+        from . import ops
+        perm = self.order()
+        if perm is None:
+            perm = torch.arange(self.n)
+        self.dataset.locate(perm[[int(perm.argmin()), int(perm.argmax())]] if self.n else perm)   # host check, before any launch
+        perm = perm.to(self.device)
+        for s in range(0, self.n, self.batch_size):
+            x, y = ops.gather_tasks(self.table, self.row_elems, perm[s:s + self.batch_size])
+            yield x.view((x.shape[0],) + self.row_shape), y
+
+
 def synthetic_task(n_train, n_val, n_test, n_classes, hw=64, seed=7, noise=1.0, device="cpu", kind="protos", blobs=None):
     """Learnable synthetic task, SURVEY §8d.
 

@@ -511,8 +511,68 @@ def framework_single_task(args, manager, train_node=None):
 
 
 # ------------------------------------------------------------------ eval
-def get_perf_output_filename(method_name, dataset_index):
-    return "test_method_performances" + method_name + str(dataset_index) + ".pth"      # utils.py:225-230
+def get_perf_output_filename(method_name, dataset_index, joint_full_batch=False):
+    if joint_full_batch:                                                                # utils.py:220-230
+        return "test_method_performancesJOINT_FULL_BATCH.pth"
+    return "test_method_performances" + method_name + str(dataset_index) + ".pth"
+
+
+def _train_classes(dataset_path, device):
+    from ..data import load_task_datasets
+    return list(load_task_datasets(dataset_path, device)["train"].classes)
+
+
+def eval_single_model_all_tasks(args, manager, ds_paths):
+    """eval.py:69-143: ONE model (Joint) scored on every task inside the task's slice of the shared head.  The slice of task
+    i is found by class NAME through the class list of the pre-merged joint file when the dataset has one (any order, not
+    contiguous), else by the cumulative class counts of the composed task list.  One result file holding
+    {eval_name: {'seq_res': [accuracy per task of the window]}}; a failing evaluation saves nothing.  Returns that dict,
+    or None when nothing was (or, in debug mode, would have been) saved."""
+    device = getattr(args, "device", "cuda")
+    args.task_counter = manager.dataset.task_count
+    args.task_name = "TEST ALL"
+    joint_ds_path = manager.method.grid_datafetch(args, manager.dataset)
+    joint_dataloader = joint_class_to_fc_idx = None
+    if not isinstance(joint_ds_path, list):
+        joint_classes = _train_classes(joint_ds_path, device)          # (not sorted: the file's own order is the head's)
+        joint_class_to_fc_idx = {class_name: idx for idx, class_name in enumerate(joint_classes)}
+    else:
+        joint_dataloader, _, dset_classes = manager.method.compose_dataset(joint_ds_path, args.batch_size, device)
+        joint_classes = sum(dset_classes["train"], [])
+    args.tasks_idxes = []
+    tasks_output_count = 0
+    for dataset_idx, dataset_path in enumerate(ds_paths):
+        task_classes = _train_classes(dataset_path, device)
+        if joint_class_to_fc_idx is not None:
+            task_idxes = [joint_class_to_fc_idx[c] for c in task_classes if c in joint_class_to_fc_idx]
+        else:
+            first = 0 if dataset_idx == 0 else joint_dataloader["train"].dataset.cumulative_classes_len[dataset_idx - 1]
+            task_idxes = [idx + first for idx in range(len(task_classes))]
+        args.tasks_idxes.append(sorted(task_idxes))
+        tasks_output_count += len(task_classes)
+    print("{} classes in joint set, {} classes in separate sets".format(len(joint_classes), tasks_output_count))
+    assert len(joint_classes) == tasks_output_count
+    method_performances = {manager.method.eval_name: {}}
+    out_filepath = os.path.join(args.out_path, get_perf_output_filename(manager.method.eval_name, None, joint_full_batch=True))
+    try:
+        for dataset_index in range(args.test_starting_task_count - 1, args.test_max_task_count):
+            args.dataset_index = dataset_index
+            args.dataset_path = ds_paths[dataset_index]
+            from . import shard
+            with shard.busy("eval", device=device):
+                acc = manager.method.inference_eval(args, manager)
+            method_performances[manager.method.eval_name].setdefault("seq_res", []).append(acc)
+        if not getattr(args, "debug", False):
+            os.makedirs(args.out_path, exist_ok=True)
+            torch.save(method_performances, out_filepath)
+            print("Saved results to: ", out_filepath)
+        print("FINAL RESULTS: ", method_performances[manager.method.eval_name]["seq_res"])
+    except Exception as e:
+        print("TESTING ERROR: ", e)
+        print("No results saved...")
+        traceback.print_exc()
+        return None
+    return method_performances
 
 
 def eval_all_models_all_tasks(args, manager, ds_paths, model_paths):
@@ -674,6 +734,10 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
             raise ValueError("--methods creates its own method objects")
         return main_methods(argv, names, dataset=dataset)
     speculative = sequential_on_rank0 = False
+    if args.shard and args.test and "joint" in (args.method_name, getattr(method, "name", None)):
+        # the grid would shard like any grid-only method's; the single-model evaluation has no sharded form yet
+        raise SystemExit("--shard --test is not supported for --method_name joint: train with --shard, then evaluate with "
+                         "--test in a run without --shard")
     if args.shard:
         from . import shard
         rank, world = shard.init_from_env()
@@ -791,7 +855,13 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         if hasattr(method, "eval_model_preprocessing"):          # eval.py:45-46 (IMM: merged models)
             args.models_path, args.datasets_path = model_paths, ds_paths
             model_paths = method.eval_model_preprocessing(args)
-        results = eval_all_models_all_tasks(args, manager, ds_paths, model_paths)
+        if method.name == "joint":                               # eval.py:22, 59-61
+            ds_paths = ds_paths[0] if len(ds_paths) == 1 and isinstance(ds_paths[0], list) else ds_paths
+            args.task_lengths = [len(v) for v in dataset.classes_per_task.values()]
+            args.model_path = model_paths[0]
+            results = eval_single_model_all_tasks(args, manager, ds_paths)
+        else:
+            results = eval_all_models_all_tasks(args, manager, ds_paths, model_paths)
     return {"manager": manager, "frameworks": frameworks, "ds_paths": ds_paths, "model_paths": model_paths,
             "results": results, "args": args}
 
@@ -799,7 +869,10 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
 if __name__ == "__main__":
     out = main()
     from . import shard as _shard
-    if _shard.rank_world()[0] == 0 and out["results"] is not None:
+    if out["manager"].method.name == "joint":
+        if out["results"] is not None:
+            print("joint: acc per task %s" % ["%.2f" % a for a in out["results"]["joint"]["seq_res"]])
+    elif _shard.rank_world()[0] == 0 and out["results"] is not None:
         for i, r in sorted(out["results"].items()):
             print("task %d: acc %s  forgetting %s" % (i + 1, ["%.2f" % a for a in r["seq_res"][i]],
                                                       ["%.2f" % f for f in r["seq_forgetting"][i]]))

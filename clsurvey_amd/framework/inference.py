@@ -48,3 +48,46 @@ def test_model(method, model, dataset_path, target_task_head_idx, target_head=No
     accuracy = 100.0 * float(hits.item()) / seen
     print("Overall Accuracy: " + str(accuracy))
     return accuracy
+
+
+def test_task_joint_model(model_path, dataset_path, task_idx, task_lengths, batch_size=200, subset="test", tasks_idxes=None,
+                          device="cuda", per_class_stats=False):
+    """Accuracy (percent) of ONE task in a model trained jointly on all tasks — framework/inference.py:90-164: shared output
+    layer, the outputs of the other tasks are left out: arg-max inside `tasks_idxes[task_idx]` (or, without it, the
+    contiguous slice the class counts `task_lengths` give) against the task-local label.  Per batch one plan forward and
+    one clhip_slice_argmax_count launch; the per-class counters stay on the device and are read once per task.
+    per_class_stats=True returns (accuracy, correct[K], total[K]).  The counters have one entry per output index of the
+    slice, K = len(tasks_idxes[task_idx]), and a label outside [0, K) raises IndexError.  The reference sizes its counters by
+    the task's own class list instead; the two differ only when the by-name mapping drops classes the joint file does not
+    have: there the reference counts such a label as a miss, this stops."""
+    from .. import ops
+    from ..net import NetEngine
+    print("==> TESTING TASK {}".format(task_idx + 1))
+    model = tc.load_model(model_path)
+    model.eval()
+    model = model.to(device)
+    dsets = load_task_datasets(dataset_path, device)
+    split = subset if "test" in dsets else "val"            # a task file without a test split is scored on val (:113-120)
+    if tasks_idxes is None:
+        cols = [c + sum(task_lengths[0:task_idx]) for c in range(task_lengths[task_idx])]
+    else:
+        cols = tasks_idxes[task_idx]
+        assert isinstance(cols, list)
+    loader = DeviceLoader(dsets[split], batch_size, True, device)
+    engine = NetEngine(model, batch_size, tuple(loader.x.shape[1:]), device)
+    if not cols or min(cols) < 0 or max(cols) >= engine.n_classes:
+        raise IndexError("task %d: output indices %s outside the model's %d outputs" % (task_idx + 1, cols, engine.n_classes))
+    K = len(cols)
+    cols_dev = torch.tensor(cols, dtype=torch.int32).to(device)
+    counters = torch.zeros(2 * K + 1, dtype=torch.int64, device=device)
+    correct, total, bad = counters[:K], counters[K:2 * K], counters[2 * K:]
+    for images, labels in loader:
+        ops.slice_argmax_count(engine.forward(images), cols_dev, labels, correct, total, bad)
+    host = counters.cpu()                                    # the only host read of the task
+    if int(host[2 * K]):
+        raise IndexError("task %d: %d labels outside [0, %d)" % (task_idx + 1, int(host[2 * K]), K))
+    accuracy = float(host[:K].sum()) * 100 / float(host[K:2 * K].sum())
+    print("Accuracy: " + str(accuracy))
+    if per_class_stats:
+        return accuracy, host[:K].clone(), host[K:2 * K].clone()
+    return accuracy

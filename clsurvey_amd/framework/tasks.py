@@ -48,7 +48,10 @@ class SyntheticTaskSequence(object):
     def get_task_dataset_path(self, task_name=None, rnd_transform=False):
         """Task files are cached under root/name/; a sidecar task_N.spec.json records what they were generated from.  A cached
         file of ANOTHER spec (other kind / blobs / noise / sizes / seed under the same results root) is an error, not a hit:
-        the results tree beside it holds success tokens and models of that other data."""
+        the results tree beside it holds success tokens and models of that other data.
+        task_name=None asks for a pre-merged file of ALL tasks (Joint.grid_datafetch, method.py:1204): there is none."""
+        if task_name is None:
+            return None
         path = os.path.join(self.root, self.name, "task_%s.pth.tar" % task_name)
         side = os.path.join(self.root, self.name, "task_%s.spec.json" % task_name)
         want = self.spec(task_name)

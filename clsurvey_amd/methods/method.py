@@ -27,7 +27,7 @@ from enum import Enum, auto
 
 import torch
 
-from ..data import DeviceLoader, TensorTaskDataset, load_task_datasets
+from ..data import DeviceLoader, MultiTaskLoader, TaskList, TensorTaskDataset, load_task_datasets
 from . import ebll as _ebll
 from . import ewc as _ewc
 from . import finetune as _ft
@@ -163,7 +163,12 @@ def _out_hat_gated(method, images, args):
     return eng.forward(args.task_idx, images, args.model.smax)
 
 
-OUTPUT = {"swap_head": _out_swap_head, "own_heads": _out_own_heads, "gem_slice": _out_gem_slice, "hat_gated": _out_hat_gated}
+def _out_joint(method, images, args):
+    raise NotImplementedError("JOINT has custom testing method for shared head.")
+
+
+OUTPUT = {"swap_head": _out_swap_head, "own_heads": _out_own_heads, "gem_slice": _out_gem_slice, "hat_gated": _out_hat_gated,
+          "joint": _out_joint}
 
 
 def _test(manager, model, args, head_idx, heads):
@@ -202,8 +207,16 @@ def _eval_packnet(args, manager):
                               batch_size=args.batch_size, current_dataset_idx=args.eval_dset_idx + 1), device=_dev(args))
 
 
+def _eval_joint(args, manager):
+    """The one jointly trained model on one task, scored inside the task's slice of the shared head (method.py:1232-1235)."""
+    from ..framework import inference
+    return inference.test_task_joint_model(args.model_path, args.dataset_path, args.dataset_index, args.task_lengths,
+                                           batch_size=args.batch_size, subset="test", tasks_idxes=args.tasks_idxes,
+                                           device=_dev(args))
+
+
 EVALUATE = {"swap_head": _eval_swap_head, "as_is": _eval_as_is, "wrapper_after_first": _eval_wrapper_after_first,
-            "packnet": _eval_packnet}
+            "packnet": _eval_packnet, "joint": _eval_joint}
 
 
 # ------------------------------------------------------------------------------------------------ shared phase 1 (SGD)
@@ -228,10 +241,28 @@ def compose_dataset(dataset_path, batch_size, device="cuda"):
     return loaders, {s: sum(len(d) for d in per[s]) for s in splits}, {s: [d.classes for d in per[s]] for s in splits}
 
 
+def compose_joint_dataset(dataset_path, batch_size, device="cuda"):
+    """compose_dataset's triple for the Joint baseline: the same batches for the same RNG state, gathered per batch out of
+    the cached per-task tensors (data.MultiTaskLoader) instead of out of a merged copy of the whole sequence."""
+    splits = ("train", "val")
+    tasks = [load_task_datasets(p, device) for p in dataset_path]
+    per = {s: [t[s] for t in tasks] for s in splits}
+    loaders = {s: MultiTaskLoader(TaskList(per[s]), batch_size, True, device) for s in splits}
+    return loaders, {s: sum(len(d) for d in per[s]) for s in splits}, {s: [d.classes for d in per[s]] for s in splits}
+
+
+# Finetune's `compose_dataset` hook is this function object, bound when the class is made.  _phase1_sgd treats that hook as
+# "no hook of its own" and looks the module-level name up at call time, so code that replaces `method.compose_dataset`
+# (the recorders of the trainer-call tests) still reaches finetuning's phase 1.
+_COMPOSE_DEFAULT = compose_dataset
+
+
 def _phase1_sgd(method, args, manager, lr):
     """One LR-grid node of the maximal-plasticity search: plain SGD finetune from the previous task's model."""
     paths = manager.current_task_dataset_path
-    loaders, sizes, classes = compose_dataset(paths if isinstance(paths, list) else [paths], args.batch_size, _dev(args))
+    hook = getattr(method, "compose_dataset", None)              # a method's own way to build its loaders (Joint)
+    compose = compose_dataset if hook is None or hook is _COMPOSE_DEFAULT else hook
+    loaders, sizes, classes = compose(paths if isinstance(paths, list) else [paths], args.batch_size, _dev(args))
     return _ft.fine_tune_SGD(loaders, sizes, classes, model_path=manager.previous_task_model_path,
                              exp_dir=manager.gridsearch_exp_dir, num_epochs=args.num_epochs, lr=lr,
                              weight_decay=args.weight_decay, enable_resume=True, save_models_mode=True,
@@ -246,6 +277,24 @@ def _adopt_grid_winner(args, manager):
     if os.path.islink(link) or os.path.exists(link):
         os.unlink(link)
     os.symlink(os.path.relpath(manager.best_exp_grid_node_dirname, os.path.dirname(link)), link)
+
+
+# ------------------------------------------------------------------------------------------------ Joint
+def _joint_datafetch(args, dataset):
+    """The pre-merged file of all tasks when the dataset has one, else the list of every task's file (method.py:1203-1216)."""
+    path = dataset.get_task_dataset_path(task_name=None, rnd_transform=True)
+    if path is not None:
+        print("Running JOINT for all tasks as 1 batch, dataset = ", path)
+        return path
+    paths = [dataset.get_task_dataset_path(task_name=dataset.get_taskname(t), rnd_transform=False)
+             for t in range(1, dataset.task_count + 1)]
+    print("Running JOINT for task ", args.task_name, " on datasets: ", paths)
+    return paths
+
+
+def _joint_train_args_overwrite(args):
+    args.starting_task_count = 1                # one training over everything (method.py:1227-1229)
+    args.max_task_count = args.starting_task_count
 
 
 # ------------------------------------------------------------------------------------------------ PackNet
@@ -468,6 +517,12 @@ SPECS = [
     _spec("finetuning", Category.BASELINE, flags=("grid_chkpt", "start_scratch", "no_framework"),
           hooks={"grid_poststep": staticmethod(_adopt_grid_winner), "compose_dataset": staticmethod(compose_dataset)},
           doc="plain SGD per task, no forgetting-related mechanism (method.py:994); grid only"),
+    _spec("joint", Category.BASELINE, flags=("grid_chkpt", "start_scratch", "no_framework"), output="joint", evaluate="joint",
+          hooks={"grid_datafetch": staticmethod(_joint_datafetch), "grid_poststep": staticmethod(_adopt_grid_winner),
+                 "compose_dataset": staticmethod(compose_joint_dataset),
+                 "train_args_overwrite": staticmethod(_joint_train_args_overwrite)},
+          doc="upper bound: ONE model trained from scratch on all tasks at once, one shared head, each task scored on its own "
+              "slice of it (method.py:1185-1235); grid only"),
     _spec("EWC", Category.MODEL_BASED, hyper=[("lambda", 400)], phase2="EWC", doc="method.py:663"),
     _spec("MAS", Category.MODEL_BASED, hyper=[("lambda", 3)], phase2="MAS", doc="method.py:726"),
     _spec("SI", Category.MODEL_BASED, hyper=[("lambda", 400)], phase2="SI", doc="method.py:695"),
@@ -556,7 +611,7 @@ def _build_class(spec):
     ns.update(spec["hooks"])
     if spec["phase2"] is None and "train" not in spec["hooks"]:
         ns["train"] = None                      # grid-only methods have no phase 2; the drivers never ask for it
-    cls_name = {"finetuning": "Finetune", "packnet": "PackNet", "finetuning_rehearsal_partial_mem": "FinetuneRehearsalPartialMem",
+    cls_name = {"finetuning": "Finetune", "joint": "Joint", "packnet": "PackNet", "finetuning_rehearsal_partial_mem": "FinetuneRehearsalPartialMem",
                 "finetuning_rehearsal_full_mem": "FinetuneRehearsalFullMem"}.get(spec["name"], spec["name"])
     return type(cls_name, (Method,), ns)
 

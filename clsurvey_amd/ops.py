@@ -760,3 +760,45 @@ def linear(x, w, b, relu=False):
 
 def cross_entropy(logits, labels, reduction="mean"):
     return SoftmaxCEFn.apply(logits, labels, reduction)
+
+
+# ------------------------------------------------------------------ Joint baseline
+def task_table(xs, ys, cum_rows, label_shifts, device):
+    """Device table of clhip_task_src rows (x pointer, label pointer, cumulative row count, label shift) as int64[T, 4]."""
+    _chk(*xs, *ys)
+    T = len(xs)
+    assert 1 <= T <= 64 and len(ys) == len(cum_rows) == len(label_shifts) == T, "clhip_gather_tasks takes 1..64 tasks"
+    assert all(x.dtype == torch.float32 for x in xs) and all(y.dtype == torch.int64 for y in ys)
+    rows = [[x.data_ptr(), y.data_ptr(), int(c), int(s)] for x, y, c, s in zip(xs, ys, cum_rows, label_shifts)]
+    return torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+def gather_tasks(table, row_elems, idx, x_out=None, labels_out=None):
+    """clhip_gather_tasks: rows idx (device int64, GLOBAL sample numbers, checked by the caller) of the tasks in `table`.
+    Returns (x_out [B, row_elems], labels_out [B])."""
+    _chk(table, idx, x_out, labels_out)
+    assert idx.dtype == torch.int64 and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 4
+    B = idx.shape[0]
+    if x_out is None:
+        x_out = torch.empty((B, row_elems), dtype=torch.float32, device=idx.device)
+    if labels_out is None:
+        labels_out = torch.empty((B,), dtype=torch.int64, device=idx.device)
+    assert x_out.numel() >= B * row_elems and labels_out.numel() >= B
+    xf, step = x_out.view(-1), 65535                     # one launch takes at most 65535 rows (grid y): larger batches in pieces
+    for s in range(0, B, step):
+        n = min(step, B - s)
+        check(_lib.lib().clhip_gather_tasks(_ptr(table), table.shape[0], row_elems, _ptr(idx[s:s + n]), n,
+                                            _ptr(xf[s * row_elems:]), _ptr(labels_out[s:]), _stream()), "clhip_gather_tasks")
+    return x_out, labels_out
+
+
+def slice_argmax_count(logits, cols, labels, correct, total, out_of_range):
+    """clhip_slice_argmax_count: adds one batch to the per-class counters (int64[K], int64[K], int64[1])."""
+    _chk(logits, cols, labels, correct, total, out_of_range)
+    N, ld = logits.shape
+    K = cols.shape[0]
+    assert logits.dtype == torch.float32 and cols.dtype == torch.int32 and labels.dtype == torch.int64
+    assert all(t.dtype == torch.int64 for t in (correct, total, out_of_range))
+    assert labels.shape[0] == N and correct.numel() == K and total.numel() == K and out_of_range.numel() == 1
+    check(_lib.lib().clhip_slice_argmax_count(_ptr(logits), N, ld, _ptr(cols), K, _ptr(labels), _ptr(correct), _ptr(total),
+                                              _ptr(out_of_range), _stream()), "clhip_slice_argmax_count")

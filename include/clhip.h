@@ -501,6 +501,30 @@ int clhip_net_loss_step_segments(void* handle, const float* params, float* grads
                                  int N, const clhip_ce_segment* segs, int n_segs, void* ws, float* loss_out, double* stats,
                                  float* logits_out, void* stream);
 
+/* ------------------------------------------------------------------ Joint baseline
+ * methods/method.py:1185-1235: one model trained on all tasks at once, one shared output layer, each task scored on its
+ * own slice of that layer.
+ *
+ *   gather_tasks        a batch out of T <= CLHIP_MAX_TASKS per-task tensors WITHOUT a merged copy of the sequence
+ *                       (data/imgfolder.py:244-272 ConcatDatasetDynamicLabels): tasks_dev is a DEVICE table, cum_rows the
+ *                       cumulative sample counts, label_shift the class counts of the tasks before.  idx (device int64[B],
+ *                       B <= 65535) holds GLOBAL sample numbers; number g belongs to the first task whose cum_rows exceeds
+ *                       it.  x_out[b] = the row (bitwise; 16-byte vectors when row_elems % 4 == 0 and both rows are
+ *                       16-byte aligned, scalar otherwise), labels_out[b] = label + label_shift.  A number outside
+ *                       [0, cum_rows[T-1]) copies nothing and writes label -1: callers check the numbers on the host.
+ *   slice_argmax_count  framework/inference.py:141-149 for one batch in one launch: row i's prediction is the position k of
+ *                       the largest logits[i][cols[k]], k < K (cols: device int32[K], any order, not necessarily
+ *                       contiguous; the first NaN wins, lowest k on ties — torch.max on the CPU); for a label y in [0, K)
+ *                       total[y] += 1 and correct[y] += (prediction == y), integer atomics: the result does not depend on
+ *                       order.  A label outside [0, K) (the reference stops with IndexError there) or a column outside
+ *                       [0, ld) adds 1 to *out_of_range and nothing else for that row.  Counters accumulate over calls. */
+#define CLHIP_MAX_TASKS 64
+typedef struct clhip_task_src { const float* x; const int64_t* labels; int64_t cum_rows; int64_t label_shift; } clhip_task_src;
+int clhip_gather_tasks(const clhip_task_src* tasks_dev, int T, size_t row_elems, const int64_t* idx, int B, float* x_out,
+                       int64_t* labels_out, void* stream);
+int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols, int K, const int64_t* labels_i64,
+                             int64_t* correct, int64_t* total, int64_t* out_of_range, void* stream);
+
 #ifdef CLHIP_VISIBILITY_PUSHED
 #pragma GCC visibility pop
 #undef CLHIP_VISIBILITY_PUSHED
