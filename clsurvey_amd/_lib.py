@@ -33,6 +33,10 @@ class HatEmbJob(C.Structure):                      # clhip_hat_emb_job
     _fields_ = [("dgate", _p), ("gate", _p), ("mask_pre", _p), ("demb", _p), ("n", _i), ("rows", _i), ("t", _i), ("reserved", _i)]
 
 
+class IcarlClass(C.Structure):                     # clhip_icarl_class
+    _fields_ = [("row_begin", _i), ("row_end", _i), ("k", _i), ("out_off", _i)]
+
+
 class LayerDesc(C.Structure):
     _fields_ = [("type", _i), ("cin", _i), ("cout", _i), ("relu", _i), ("pool", _i),
                 ("w_off", _l), ("b_off", _l), ("ksize", _i), ("stride", _i), ("pad", _i), ("pool_k", _i), ("pool_s", _i),
@@ -153,6 +157,10 @@ SIGNATURES = {
     "clhip_net_loss_step_segments": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p]),
     "clhip_gather_tasks": (_i, [_p, _i, _z, _p, _i, _p, _p, _p]),
     "clhip_slice_argmax_count": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "clhip_icarl_herd": (_i, [_p, _l, _i, _p, C.POINTER(IcarlClass), _i, _p, _l, _p]),
+    "clhip_icarl_loss_segments": (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _f, _p, _p, _p, _p]),
+    "clhip_net_loss_step_icarl": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _f, _p, _p, _p, _p, _p]),
+    "clhip_icarl_nme": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

@@ -818,6 +818,9 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
     else:
         prev = os.path.join(parent_exp_dir, "task_{}".format(args.starting_task_count - 1), "TASK_TRAINING",
                             "best_model.pth.tar")
+        post = getattr(method, "postprocessed_model_name", None)  # iCaRL: a later task's model is the postprocessed file
+        if post is not None and os.path.exists(os.path.join(os.path.dirname(prev), post)):
+            prev = os.path.join(os.path.dirname(prev), post)
     if not os.path.exists(prev) and not args.first_task_basemodel_dump:
         raise Exception("NOT EXISTING previous_task_model_path = " + prev)
     if args.first_task_basemodel_dump:                          # main.py:255-263 (check_dump)

@@ -148,7 +148,7 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         args.finetune = True
         args.full_mem_mode = args.method == "baseline_rehearsal_full_mem"
     elif args.method != "gem":
-        raise NotImplementedError("rehearsal method %r (iCaRL is out of scope)" % args.method)
+        raise NotImplementedError("rehearsal method %r (iCaRL has its own entry: methods.icarl_main.main)" % args.method)
     assert args.n_outputs == sum(args.nc_per_task)
     assert args.n_tasks == len(nc_per_task)
     if args.task_count == 1 and not baseline:

@@ -1,0 +1,514 @@
+"""iCaRL on the HIP path — mirror of src/methods/rehearsal/model/icarl.py (Net.manage_memory / update_representation /
+forward), the survey's variant: one total memory shared out per class (K/m), distillation per past task, nearest-mean-of-
+exemplars evaluation inside the task's slice.
+
+The reference stores exemplar *paths* and, to rank the exemplars of one class, recomputes the features of every class
+image and of every exemplar chosen so far once per pick (:394-427).  Here the exemplars are device tensors (the store) and
+
+    manage_memory   features of the task's training set ONCE (chunks through the plan, NetEngine.layer_input of the first
+                    Linear layer), then clhip_icarl_herd: the ranked lists of all classes of the task in one launch
+    observe         host draws exactly as the reference makes them, clhip_rehearsal_assemble (images; a second launch
+                    gathers the stored distillation rows), then ONE clhip_net_loss_step_icarl over
+                    [current batch | distillation chunks] and one fused SGD step
+    forward         class means from the stored exemplars once per (model, task), clhip_icarl_nme per batch
+
+A plan with BatchNorm, or a step over the loss kernel's limits, takes the segmented path: one pass per chunk in the
+reference's order (as RehearsalNet does).  Herding needs features that do not depend on the batch: manage_memory refuses a
+net with BatchNorm in `features`.
+"""
+import random
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .._lib import check
+from ..net import NetEngine
+from ..optim import SGD
+from .gem import compute_offsets, extend_head
+from .rehearsal import FUSED_MAX_ROWS, FUSED_MAX_SEGS, _Order
+
+T_DISTILL = 2.0                 # update_representation(..., T=2)
+HERD_MAX_CLASSES, HERD_MAX_FEATS = 128, 4096        # CLHIP_ICARL_MAX_CLASSES / _FEATS (include/clhip.h)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def init_head(model, n_outputs):
+    """icarl.py:84-103: an n_outputs-way Linear whose first rows are the old head."""
+    return extend_head(model, n_outputs)
+
+
+def mean_weights(n, batch_size):
+    """Per-row weights of get_mean_feat (:303-311) over n rows in order, batches of batch_size: the mean of batch means
+    is sum_i w_i f_i with w_i = 1 / (n_batches * size of i's batch) — a short last batch weighs more per row."""
+    n_batches = (n + batch_size - 1) // batch_size
+    w = np.empty(n, dtype=np.float32)
+    for b in range(n_batches):
+        lo, hi = b * batch_size, min(n, (b + 1) * batch_size)
+        w[lo:hi] = 1.0 / (n_batches * (hi - lo))
+    return w
+
+
+def exemplar_draws(t, n_append, class_len, exemplar_count, nc_per_task, cum_nc_per_task, total_batch_size):
+    """The host draws of update_representation (:507-562) for one step at task index t, on Python `random`, numpy's global
+    generator and the global torch CPU generator, in the reference's order.  class_len[c] = exemplars stored for class c
+    (every class stored so far).  Returns (counts per class, [(task, chunks)]) with chunks = lists of (class, exemplar
+    index) in the order the task's DataLoader(shuffle=True, batch_size=total_batch_size) yields them."""
+    n_classes = len(class_len)
+    if exemplar_count <= 0 or n_classes == 0:
+        return [], []
+    n_fixed = int(np.floor(n_append / n_classes))
+    if n_fixed > exemplar_count:                       # :511-513: capped, no random leftovers
+        counts = [exemplar_count] * n_classes
+    else:
+        counts = [n_fixed] * n_classes
+        n_random = n_append % n_classes
+        if n_random > sum(exemplar_count - c for c in counts):
+            raise ValueError("icarl: %d leftover exemplars do not fit %d classes of %d (the reference's redraw loop would "
+                             "never end)" % (n_random, n_classes, exemplar_count))
+        rnd = 0
+        while rnd < n_random:
+            idx = random.randint(0, n_classes - 1)
+            if counts[idx] < exemplar_count:
+                counts[idx] += 1
+                rnd += 1
+    out = []
+    for task in range(t):
+        o1, _ = compute_offsets(task, cum_nc_per_task)
+        rows = []
+        for local in range(nc_per_task[task]):
+            c = local + o1
+            if c < n_classes and counts[c] > 0:
+                picks = np.random.permutation(class_len[c])[:counts[c]].tolist()
+                rows.extend((c, int(e)) for e in picks)
+        if not rows:
+            continue
+        if total_batch_size <= 0:
+            raise ValueError("icarl: distillation chunk size %d" % total_batch_size)
+        ordered = [rows[i] for i in _Order(len(rows)).order().tolist()]
+        out.append((task, [ordered[s:s + total_batch_size] for s in range(0, len(ordered), total_batch_size)]))
+    return counts, out
+
+
+def segment_scales(chunk_counts, reg):
+    """The accumulation of :505-592 AS WRITTEN: total_ex_loss and its counter are not reset between past tasks and
+    reg * total / count is added once per past task.  With A_j the sum of task j's chunk losses and c_j its chunk count:
+    T_1 = reg A_1 / c_1, T_j = reg (T_{j-1} + A_j) / (c_1 + ... + c_j), loss += sum_j T_j.  Linear in the chunk losses:
+    returns the factor of one chunk loss of each task (same order as chunk_counts)."""
+    n = len(chunk_counts)
+    coef = [0.0] * n                  # factor of A_i inside the running total
+    scale = [0.0] * n
+    count = 0
+    for j in range(n):
+        count += chunk_counts[j]
+        coef[j] += 1.0
+        coef = [reg * c / count for c in coef[:j + 1]] + coef[j + 1:]
+        for i in range(j + 1):
+            scale[i] += coef[i]
+    return scale
+
+
+class IcarlNet:
+    """icarl.Net.  Picklable like GemNet / RehearsalNet: the pickle carries the net, the counters, the stored exemplar rows
+    and their distillation targets only; engine / workspaces / optimizer are rebuilt on load (init_setup)."""
+
+    _TRANSIENT = ("engine", "A", "stats", "opt", "x_mix", "y_mix", "t_mix", "_acc", "store_x", "store_t", "_store_lab", "_means",
+                  "_draw_mask", "_scratch_lab", "last_ranking")
+
+    def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, memory_strength=0.0,
+                 batch_size=200, in_shape=(3, 64, 64), device="cuda"):
+        self.net = init_head(model, n_outputs).to(device)
+        self.device = torch.device(device)
+        self.n_outputs, self.n_tasks = n_outputs, n_tasks
+        self.n_memories_per_task = int(n_memories)
+        self.n_total_memories = int(n_memories) * n_tasks            # :41, fixed at creation
+        self.batch_size = batch_size
+        self.in_shape = tuple(in_shape)
+        self.nc_per_task = list(nc_per_task)
+        self.cum_nc_per_task = [sum(nc_per_task[:i + 1]) for i in range(len(nc_per_task))]
+        self.exemplar_count = 0          # K/m of the last manage_memory = the row stride of a class block in the store
+        self.class_len = []              # exemplars stored per class, classes in head order
+        self.observed_tasks, self.old_task = [], -1
+        self.n_append, self.chunk_size, self.total_batch_size = 0, batch_size, batch_size
+        self.force_segmented = False                                 # tests: run the BatchNorm path on any plan
+        self.last_path = None                                        # 'fused' | 'segmented' | None (no observe yet)
+        self._alloc_store()
+        self._bind()
+        self.init_setup(lr=lr, weight_decay=weight_decay, memory_strength=memory_strength)
+
+    # ------------------------------------------------------------------ state
+    def _alloc_store(self):
+        n = self.n_total_memories
+        self.store_x = torch.zeros((n,) + self.in_shape, dtype=torch.float32, device=self.device)
+        self.store_t = torch.zeros((n, self.n_outputs), dtype=torch.float32, device=self.device)     # mem_class_y rows
+        self._store_lab = torch.zeros((n,), dtype=torch.int64, device=self.device)      # (the assemble kernel copies a label per row)
+
+    def _bind(self):
+        self.engine = NetEngine(self.net, max(self.batch_size, 1), self.in_shape, self.device)
+        self.engine.auto_dropout = False        # one mask per step over the MIXED batch, drawn here (_dropout)
+        self.fc_first = next(i for i, sp in enumerate(self.engine.layers) if sp[0] == "fc")
+        self.A = self.engine.arena
+        self.stats = torch.zeros(2, dtype=torch.float64, device=self.device)
+        rows = max(self.batch_size, 1)
+        self.x_mix = torch.empty((rows,) + self.in_shape, dtype=torch.float32, device=self.device)
+        self.y_mix = torch.empty((rows,), dtype=torch.int64, device=self.device)
+        self.t_mix = torch.zeros((rows, self.n_outputs), dtype=torch.float32, device=self.device)
+        self._scratch_lab = torch.empty((rows,), dtype=torch.int64, device=self.device)
+        self._acc = None
+        self._means = {}
+        self.last_ranking = None      # (device int32 ranking, class offsets) of the last manage_memory; not pickled
+
+    def init_setup(self, args=None, lr=None, weight_decay=None, memory_strength=None, n_append=None, chunk_size=None,
+                   total_batch_size=None):
+        """:105-124: fresh SGD(momentum 0.9) and reg at every main() call; the step composition of this call."""
+        if args is not None:
+            lr, weight_decay, memory_strength = args.lr, args.weight_decay, args.memory_strength
+            n_append = getattr(args, "n_exemplars_to_append_per_batch", 0)
+            chunk_size = args.batch_size
+            total_batch_size = getattr(args, "total_batch_size", args.batch_size)
+            if args.n_outputs != self.n_outputs:
+                raise NotImplementedError("icarl: the head is sized for every task at creation (%d outputs, asked %d)"
+                                          % (self.n_outputs, args.n_outputs))
+            if args.n_tasks != self.n_tasks:
+                self.n_tasks = args.n_tasks                        # :115-119: the memory keeps its initial capacity
+            self.nc_per_task = list(args.nc_per_task)
+            self.cum_nc_per_task = [sum(self.nc_per_task[:i + 1]) for i in range(len(self.nc_per_task))]
+        if n_append is not None:
+            self.n_append = int(n_append)
+        if chunk_size is not None:
+            self.chunk_size = int(chunk_size)
+        if total_batch_size is not None:
+            self.total_batch_size = int(total_batch_size)
+        self.opt = SGD(self.net.parameters(), lr, momentum=0.9, weight_decay=weight_decay)
+        if memory_strength is not None:
+            self.reg = memory_strength
+
+    def _block(self, c):
+        """(first store row, length) of class c."""
+        return c * self.exemplar_count, self.class_len[c]
+
+    def stored_rows(self):
+        """Store rows that hold an exemplar, class after class."""
+        return [c * self.exemplar_count + e for c in range(len(self.class_len)) for e in range(self.class_len[c])]
+
+    def __getstate__(self):
+        state = {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
+        idx = torch.tensor(self.stored_rows(), dtype=torch.int64, device=self.device)
+        state["_rows_x"] = self.store_x.index_select(0, idx)          # a view would pickle the whole store
+        state["_rows_t"] = self.store_t.index_select(0, idx)
+        return state
+
+    def __setstate__(self, state):
+        rows_x, rows_t = state.pop("_rows_x"), state.pop("_rows_t")
+        self.__dict__.update(state)
+        self.device = torch.device(self.device)
+        self.net = self.net.to(self.device)
+        self._alloc_store()
+        if rows_x.shape[0]:
+            idx = torch.tensor(self.stored_rows(), dtype=torch.int64, device=self.device)
+            self.store_x[idx] = rows_x.to(self.device)
+            self.store_t[idx] = rows_t.to(self.device)
+        self._bind()
+        self.opt = None
+
+    def compute_offsets(self, task_idx, cum_nc_per_task=None):
+        return compute_offsets(task_idx, self.cum_nc_per_task if cum_nc_per_task is None else cum_nc_per_task)
+
+    def parameters(self):
+        return self.net.parameters()
+
+    def eval(self):
+        return self
+
+    def to(self, device):
+        return self
+
+    def _slice(self, task):
+        o1, o2 = compute_offsets(task, self.cum_nc_per_task)
+        return (o1, o2 - o1)
+
+    # ------------------------------------------------------------------ dropout (nn.Dropout of net_classifier)
+    def _draw_mask(self, layer, n, elems, p):
+        """nn.Dropout in training mode: Bernoulli(1 - p) / (1 - p) per element and row (device generator)."""
+        keep = 1.0 - p
+        return torch.empty((n, elems), dtype=torch.float32, device=self.device).bernoulli_(keep).div_(keep)
+
+    def _dropout(self, n):
+        """Masks of one pass over n rows, or none in eval mode.  Returns {layer: mask}."""
+        masks = {}
+        for li, m in self.engine.drops.items():
+            if self.net.training and m.p > 0:
+                masks[li] = self._draw_mask(li, n, self.engine.in_elems[li], m.p)
+                self.engine.set_dropout(li, masks[li])
+            else:
+                self.engine.set_dropout(li, None)
+        return masks
+
+    # ------------------------------------------------------------------ features / training output
+    def features(self, x):
+        """get_feature (:203-207) of any number of rows: the un-masked input of the first Linear layer, [n][n_feat]."""
+        out = []
+        for s in range(0, x.shape[0], self.engine.max_batch):
+            xb = x[s:s + self.engine.max_batch].contiguous()
+            self.engine.forward(xb)
+            out.append(self.engine.layer_input(self.fc_first, xb.shape[0]).clone())
+        return torch.cat(out)
+
+    def forward_training(self, x, t):
+        """:188-201: the head's output, -10e10 outside the task's slice."""
+        out = []
+        for s in range(0, x.shape[0], self.engine.max_batch):
+            xb = x[s:s + self.engine.max_batch].contiguous()
+            self._dropout(xb.shape[0])
+            out.append(self.engine.forward(xb))
+        logits = torch.cat(out)
+        o1, o2 = compute_offsets(t, self.cum_nc_per_task)
+        res = torch.full_like(logits, -10e10)
+        res[:, o1:o2] = logits[:, o1:o2]
+        return res
+
+    # ------------------------------------------------------------------ memory (:314-479)
+    def init_new_task(self, t):
+        self.observed_tasks.append(t)
+        self.old_task = t
+
+    def _truncate(self, new_count):
+        """Every stored class keeps its first new_count entries; blocks compacted in place, ascending (a destination
+        never overtakes its source, pieces no longer than the gap: no piece overlaps its own source)."""
+        old = self.exemplar_count
+        for c in range(len(self.class_len)):
+            keep = min(self.class_len[c], new_count)
+            src, dst = c * old, c * new_count
+            gap = src - dst
+            s = 0
+            while gap > 0 and s < keep:
+                e = min(keep, s + gap)
+                self.store_x[dst + s:dst + e] = self.store_x[src + s:src + e]
+                self.store_t[dst + s:dst + e] = self.store_t[src + s:src + e]
+                s = e
+            self.class_len[c] = keep
+        self.exemplar_count = new_count
+
+    def herd(self, feats, ranges, weights, ks):
+        """clhip_icarl_herd over feats [n_rows][F] (device fp32): ranges = [(row_begin, row_end)] per class, weights the
+        per-row mean weights (device fp32 [n_rows]), ks the picks per class.  Returns the device int32 ranking (classes
+        back to back) and the offsets of the classes in it.  No synchronisation."""
+        if not feats.is_cuda or feats.dtype != torch.float32 or not feats.is_contiguous():
+            raise RuntimeError("herding needs a contiguous fp32 HIP tensor")
+        offs = np.concatenate([[0], np.cumsum(ks)]).astype(np.int64)
+        ranking = torch.empty(max(int(offs[-1]), 1), dtype=torch.int32, device=self.device)
+        L = _lib.lib()
+        for s in range(0, len(ranges), HERD_MAX_CLASSES):
+            part = ranges[s:s + HERD_MAX_CLASSES]
+            tab = (_lib.IcarlClass * len(part))()
+            for i, (lo, hi) in enumerate(part):
+                tab[i].row_begin, tab[i].row_end, tab[i].k, tab[i].out_off = int(lo), int(hi), int(ks[s + i]), int(offs[s + i])
+            check(L.clhip_icarl_herd(feats.data_ptr(), feats.shape[0], feats.shape[1], weights.data_ptr(), tab, len(part),
+                                     ranking.data_ptr(), ranking.shape[0], _stream()), "clhip_icarl_herd")
+        return ranking, offs
+
+    def manage_memory(self, t, args):
+        """:314-479 for task t: truncate the stored classes to K/m entries, rank K_c = min(K/m, class size) exemplars of
+        every class of the task (features once, one herding launch), store them with their distillation targets."""
+        if self.engine.bns:
+            raise NotImplementedError("icarl: herding ranks features computed once, which a net with BatchNorm in `features` "
+                                      "does not have (they depend on the batch)")
+        if t != self.old_task:
+            self.init_new_task(t)
+        count = int(self.n_total_memories / self.cum_nc_per_task[t])          # K/m
+        assert count > 0, "Each class should get at least 1 exemplar"
+        o1, o2 = compute_offsets(t, self.cum_nc_per_task)
+        if len(self.class_len) != o1:
+            raise RuntimeError("icarl: manage_memory(%d) needs the classes of the earlier tasks stored (%d of %d)"
+                               % (t, len(self.class_len), o1))
+        self._truncate(count)
+        train = args.task_imgfolders["train"]
+        x, y = train.x, train.y
+        order = torch.sort(y, stable=True)[1]                                   # classes back to back, dataset order inside
+        sizes = torch.bincount(y, minlength=o2 - o1).cpu().tolist()
+        if len(sizes) != o2 - o1 or min(sizes) <= 0:
+            raise ValueError("icarl: every class of the task needs at least one training image, got sizes %s" % sizes)
+        F = self.engine.layer_input(self.fc_first, 1).shape[1]
+        if F > HERD_MAX_FEATS:
+            raise NotImplementedError("icarl: %d features > %d of the herding kernel" % (F, HERD_MAX_FEATS))
+        was_training = self.net.training
+        self.net.train(False)
+        self._dropout(1)
+        feats = self.features(x).index_select(0, order)     # features in dataset order; only the small matrix is put in class order
+        bounds = np.concatenate([[0], np.cumsum(sizes)])
+        ranges = [(int(bounds[c]), int(bounds[c + 1])) for c in range(o2 - o1)]
+        ks = [min(count, n) for n in sizes]
+        w = torch.from_numpy(np.concatenate([mean_weights(n, int(args.batch_size)) for n in sizes])).to(self.device)
+        ranking, offs = self.herd(feats, ranges, w, ks)
+        base = torch.from_numpy(np.repeat(bounds[:-1], ks)).to(self.device)
+        rows = base + ranking[:int(offs[-1])].long()                            # rows in class order, class after class
+        dst = torch.from_numpy(np.concatenate([(o1 + c) * count + np.arange(ks[c]) for c in range(o2 - o1)])).to(self.device)
+        exemplars = x.index_select(0, order.index_select(0, rows))
+        self.store_x[dst] = exemplars
+        self.store_t[dst] = self.forward_training(exemplars, t)                 # :476-479, eval mode
+        self.class_len.extend(ks)
+        self.last_ranking = (ranking, offs)
+        self.net.train(was_training)
+        self._means = {}
+
+    # ------------------------------------------------------------------ the steps
+    def observe_FT(self, x, t, y):
+        """:209-223: CE on the task's slice of the current batch only, SGD step."""
+        self.net.train(True)
+        self._means = {}
+        self.stats.zero_()
+        self._dropout(x.shape[0])
+        loss, _ = self.engine.loss_step(x, y, "ce_mean", True, self.stats, class_slice=compute_offsets(t, self.cum_nc_per_task))
+        self.opt.step()
+        return loss, self.stats[1]
+
+    def plan(self, t):
+        return exemplar_draws(t, self.n_append, self.class_len, self.exemplar_count, self.nc_per_task, self.cum_nc_per_task,
+                              self.total_batch_size)
+
+    def _upload(self, gather, segs):
+        """Gather rows (int32) and the clhip_icarl_segment tables (mixed-batch rows; then each segment alone from row 0)
+        in ONE pinned host buffer, one non-blocking copy."""
+        n = len(segs)
+        host = np.empty(len(gather) + 12 * n, dtype=np.int32)
+        host[:len(gather)] = gather
+        tab = host[len(gather):].reshape(2 * n, 6)
+        for i, (r0, r1, o, nc, sc, kind) in enumerate(segs):
+            f = np.array([sc], dtype=np.float32).view(np.int32)[0]
+            tab[i] = (r0, r1, o, nc, f, kind)
+            tab[n + i] = (0, r1 - r0, o, nc, f, kind)
+        pinned = torch.empty(host.shape[0], dtype=torch.int32, pin_memory=True)
+        pinned.numpy()[:] = host
+        dev = pinned.to(self.device, non_blocking=True)
+        return dev[:len(gather)], dev[len(gather):len(gather) + 6 * n], dev[len(gather) + 6 * n:]
+
+    def observe(self, x, t, y):
+        """:229-246 -> update_representation (:482-598).  Returns device (loss, hits on the current batch) and the batch_stats
+        dictionary the shared training loop reads (no projections here)."""
+        self.net.train(True)
+        self._means = {}
+        if t != self.old_task:
+            self.init_new_task(t)
+        B = int(y.shape[0])
+        _, plan = self.plan(t)
+        scales = segment_scales([len(chunks) for _, chunks in plan], float(self.reg))
+        segs = [(0, B) + self._slice(t) + (1.0, 0)]
+        gather = []
+        for (past, chunks), sc in zip(plan, scales):
+            for ch in chunks:
+                segs.append((B + len(gather), B + len(gather) + len(ch)) + self._slice(past) + (sc, 1))
+                gather.extend(c * self.exemplar_count + e for c, e in ch)
+        E, N = len(gather), B + len(gather)
+        if N > self.batch_size:
+            raise RuntimeError("icarl: step of %d rows > engine batch %d" % (N, self.batch_size))
+        gather_dev, segs_dev, segs_local = self._upload(gather, segs)
+        L = _lib.lib()
+        check(L.clhip_rehearsal_assemble(
+            x.data_ptr(), y.data_ptr(), B, int(np.prod(self.in_shape)), self.store_x.data_ptr(), self._store_lab.data_ptr(),
+            self.store_x.shape[0], 0, 0, gather_dev.data_ptr() if E else None, E, self.x_mix.data_ptr(), self.y_mix.data_ptr(),
+            _stream()), "clhip_rehearsal_assemble")
+        if E:                      # the stored distillation rows of the same exemplars -> t_mix[B:N)
+            check(L.clhip_rehearsal_assemble(
+                None, None, 0, self.n_outputs, self.store_t.data_ptr(), self._store_lab.data_ptr(), self.store_t.shape[0], 0, 0,
+                gather_dev.data_ptr(), E, self.t_mix[B:].data_ptr(), self._scratch_lab.data_ptr(), _stream()),
+                "clhip_rehearsal_assemble")
+        xm, ym = self.x_mix[:N], self.y_mix[:N]
+        masks = self._dropout(N)
+        self.stats.zero_()
+        if self.engine.bns or self.force_segmented or N > FUSED_MAX_ROWS or len(segs) > FUSED_MAX_SEGS:
+            loss = self._segmented(xm, ym, segs, segs_local, masks)
+            self.last_path = "segmented"
+        else:
+            self.engine._check_x(xm)
+            self.engine._mode()
+            check(L.clhip_net_loss_step_icarl(
+                self.engine._h, self.A.theta.data_ptr(), self.A.grad.data_ptr(), xm.data_ptr(), ym.data_ptr(),
+                self.t_mix.data_ptr(), self.n_outputs, N, segs_dev.data_ptr(), len(segs), T_DISTILL, self.engine.ws.data_ptr(),
+                self.engine.loss.data_ptr(), self.stats.data_ptr(), None, _stream()), "clhip_net_loss_step_icarl")
+            loss = self.engine.loss.clone()
+            self.last_path = "fused"
+        self.opt.step()
+        return loss, self.stats[1], {"projected_grads": []}
+
+    def _segmented(self, xm, ym, segs, segs_local, masks):
+        """The reference's order: the current batch, then every chunk (tasks ascending); one forward / loss / backward per
+        segment (its rows of the step's masks, its own one-row segment table), gradients summed with clhip_axpy."""
+        L = _lib.lib()
+        if self._acc is None:
+            self._acc = torch.empty(self.A.numel, dtype=torch.float32, device=self.device)
+        total = torch.zeros(1, dtype=torch.float32, device=self.device)
+        loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        for g, (r0, r1, o, nc, sc, kind) in enumerate(segs):
+            n = r1 - r0
+            for li, m in masks.items():
+                self.engine.set_dropout(li, m[r0:r1])
+            xs = xm[r0:r1]
+            logits = self.engine.forward(xs)
+            dz = torch.empty_like(logits)
+            check(L.clhip_icarl_loss_segments(
+                logits.data_ptr(), ym[r0:r1].data_ptr(), self.t_mix[r0:r1].data_ptr(), self.n_outputs, n, logits.shape[1],
+                segs_local[6 * g:].data_ptr(), 1, T_DISTILL, dz.data_ptr(), loss.data_ptr(),
+                self.stats.data_ptr() if g == 0 else None, _stream()), "clhip_icarl_loss_segments")
+            self.engine.backward(xs, dz)
+            total += loss
+            check(L.clhip_axpy(self._acc.data_ptr(), self.A.grad.data_ptr(), self.A.numel, 1.0, int(g == 0), _stream()), "clhip_axpy")
+        self.A.grad.copy_(self._acc)
+        return total
+
+    # ------------------------------------------------------------------ evaluation
+    def eval_batch(self, x, y, t, stats):
+        """main_rehearsal.py:18-35: CE and hits of the training head on the task slice (validation during training)."""
+        self.net.train(False)
+        self._dropout(x.shape[0])
+        return self.engine.loss_step(x, y, "ce_mean", False, stats, class_slice=compute_offsets(t, self.cum_nc_per_task))[0]
+
+    def class_means(self, t, batch_size):
+        """[nc_t][n_feat] means of the stored exemplars of task t: per class the mean of batch means (:160-167) over the
+        exemplars in STORED order in batches of batch_size; None while the task's first class has no exemplars."""
+        key = (t, int(batch_size))
+        if key not in self._means:
+            o1, o2 = compute_offsets(t, self.cum_nc_per_task)
+            if o1 >= len(self.class_len):
+                self._means[key] = None
+            else:
+                if o2 > len(self.class_len):
+                    raise RuntimeError("icarl: task %d is stored in part only" % t)
+                rows = [c * self.exemplar_count + e for c in range(o1, o2) for e in range(self.class_len[c])]
+                feats = self.features(self.store_x.index_select(0, torch.tensor(rows, dtype=torch.int64, device=self.device)))
+                means, lo = [], 0
+                for c in range(o1, o2):
+                    n = self.class_len[c]
+                    w = torch.from_numpy(mean_weights(n, int(batch_size))).to(self.device).double()
+                    means.append((feats[lo:lo + n].double() * w[:, None]).sum(0).float())
+                    lo += n
+                self._means[key] = torch.stack(means).contiguous()
+        return self._means[key]
+
+    def __call__(self, x, t, args=None, train_mode=False, **kw):
+        return self.forward(x, t, args, train_mode)
+
+    def forward(self, x, t, args=None, train_mode=False):
+        """:130-186 (eval): the 1-of-C code of the nearest class mean among the classes of task t (zeros, 1 at the class);
+        for a task without exemplars -10e10 everywhere and 1/nc inside its slice.
+
+        The class means are computed once per (model, task, evaluation batch size) and cached, not once per batch.  One
+        difference from the reference: its exemplar loader is shuffled, this one takes the stored order; the mean of batch
+        means depends on the order only when a class holds more exemplars than one batch and the last batch is short."""
+        if train_mode:
+            return self.forward_training(x, t)
+        self.net.train(False)
+        self._dropout(1)
+        bs = int(getattr(args, "batch_size", self.batch_size)) if args is not None else self.batch_size
+        means = self.class_means(t, bs)
+        o1, o2 = compute_offsets(t, self.cum_nc_per_task)
+        N = x.shape[0]
+        out = torch.empty((N, self.n_outputs), dtype=torch.float32, device=self.device)
+        feats = self.features(x) if means is not None else None
+        check(_lib.lib().clhip_icarl_nme(feats.data_ptr() if feats is not None else None,
+                                         means.data_ptr() if means is not None else None, N,
+                                         feats.shape[1] if feats is not None else 0, o2 - o1, o1, self.n_outputs, out.data_ptr(),
+                                         _stream()), "clhip_icarl_nme")
+        return out

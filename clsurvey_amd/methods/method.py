@@ -33,6 +33,7 @@ from . import ewc as _ewc
 from . import finetune as _ft
 from . import gem_main as _gem
 from . import hat_main as _hat
+from . import icarl_main as _icarl
 from . import imm as _imm
 from . import lwf as _lwf
 from . import mas as _mas
@@ -153,6 +154,12 @@ def _out_gem_slice(method, images, args):
     return args.model(images, args.current_head_idx)[:, lo:hi]
 
 
+def _out_icarl_nme(method, images, args):
+    """The nearest-mean-of-exemplars code of the wrapper, sliced to the task (method.py:345-350)."""
+    lo, hi = args.model.compute_offsets(args.current_head_idx, args.model.cum_nc_per_task)
+    return args.model(images, args.current_head_idx, args=args)[:, lo:hi]
+
+
 def _out_hat_gated(method, images, args):
     from . import hat as H
     head = args.heads[args.current_head_idx]
@@ -168,7 +175,7 @@ def _out_joint(method, images, args):
 
 
 OUTPUT = {"swap_head": _out_swap_head, "own_heads": _out_own_heads, "gem_slice": _out_gem_slice, "hat_gated": _out_hat_gated,
-          "joint": _out_joint}
+          "joint": _out_joint, "icarl_nme": _out_icarl_nme}
 
 
 def _test(manager, model, args, head_idx, heads):
@@ -415,6 +422,47 @@ def _gem_poststep(self, args, manager):
     manager.best_model_path = target
 
 
+# ------------------------------------------------------------------------------------------------ iCaRL
+ICARL_POSTPROCESSED = "best_model_postprocessed.pth.tar"
+
+
+def _icarl_run(self, args, manager, strength, out_dir, prev=None, finetune=False, postprocess=False):
+    """_rehearsal_accespoint (method.py:383-413) with method 'icarl', into the iCaRL trainer."""
+    nc = _classes_per_task(manager)
+    kw = {k: _resolve(v, self, args, manager, None, None) for k, v in _GEM_ARGS.items()}
+    kw.update(method="icarl", prev_model_path=manager.previous_task_model_path if prev is None else prev, save_path=out_dir,
+              n_outputs=sum(nc), memory_strength=strength, n_tasks=manager.dataset.task_count, finetune=finetune,
+              is_scratch_model=args.task_counter == 1, postprocess=postprocess)
+    manager.overwrite_args = kw
+    return _icarl.main(kw, nc, device=_dev(args))
+
+
+def _icarl_grid_train(self, args, manager, lr):
+    args.lr = lr
+    return _icarl_run(self, args, manager, 0, manager.gridsearch_exp_dir, finetune=True)
+
+
+def _icarl_train(self, args, manager, hyperparams):
+    return _icarl_run(self, args, manager, hyperparams["lambda"], manager.heuristic_exp_dir)
+
+
+def _icarl_poststep(self, args, manager):
+    """iCaRL collects exemplars after EVERY task (method.py:352-371): task 1 wraps the shared SI model into
+    manager.best_model_path, later tasks write best_model_postprocessed.pth.tar beside the trained model; either becomes
+    the model the next task and the evaluation load.  (As for GEM, the reference reads manager.best_model_path at task 1
+    before anything set it — the driver points it at task_1's slot — and args.lr, which only a training sets.)"""
+    t0 = time.time()
+    if args.task_counter == 1:
+        target, prev = manager.best_model_path, manager.previous_task_model_path
+    else:
+        target, prev = os.path.join(manager.heuristic_exp_dir, ICARL_POSTPROCESSED), manager.best_model_path
+    if not os.path.exists(target):
+        args.lr = getattr(args, "lr", None) or 0.0           # the wrapper's optimizer is rebuilt at the next task
+        _icarl_run(self, args, manager, self.hyperparams["lambda"], target, prev=prev, postprocess=True)
+    args.postprocess_time = time.time() - t0
+    manager.best_model_path = target
+
+
 # ------------------------------------------------------------------------------------------------ rehearsal baselines
 def _rehearsal_grid_train(self, args, manager, lr):
     """FinetuneRehearsalFullMem.grid_train (method.py:1139-1165; the partial-memory class calls the same).  Two of its
@@ -556,6 +604,12 @@ SPECS = [
           flags=("wrap_first_task_model",), phase1=None, output="gem_slice", evaluate="as_is",
           hooks={"grid_train": _gem_grid_train, "train": _gem_train, "poststep": _gem_poststep},
           doc="gradient episodic memory; task 1 only wraps the shared SI model with its exemplars (method.py:281-412)"),
+    _spec("ICARL", Category.REHEARSAL_BASED, hyper=[("lambda", 10)], static=[("mem_per_task", 1024)],
+          flags=("wrap_first_task_model",), phase1=None, output="icarl_nme", evaluate="as_is",
+          attrs={"postprocessed_model_name": ICARL_POSTPROCESSED},
+          hooks={"grid_train": _icarl_grid_train, "train": _icarl_train, "poststep": _icarl_poststep},
+          doc="iCaRL: herded exemplar sets shared out per class, distillation on the exemplars of every past task, nearest-"
+              "mean-of-exemplars evaluation; exemplars are collected after every task (method.py:331-380)"),
     _spec("finetuning_rehearsal_partial_mem", Category.BASELINE, flags=("grid_chkpt", "start_scratch", "no_framework"),
           output="gem_slice", evaluate="as_is", attrs={"arg_string": "baseline_rehearsal_partial_mem"},
           hooks={"grid_train": _rehearsal_grid_train, "grid_poststep": staticmethod(_adopt_grid_winner)},

@@ -802,3 +802,57 @@ def slice_argmax_count(logits, cols, labels, correct, total, out_of_range):
     assert labels.shape[0] == N and correct.numel() == K and total.numel() == K and out_of_range.numel() == 1
     check(_lib.lib().clhip_slice_argmax_count(_ptr(logits), N, ld, _ptr(cols), K, _ptr(labels), _ptr(correct), _ptr(total),
                                               _ptr(out_of_range), _stream()), "clhip_slice_argmax_count")
+
+
+# ------------------------------------------------------------------ iCaRL
+def icarl_herd(feats, weights, ranges, ks):
+    """clhip_icarl_herd: feats [n_rows, F] fp32, weights [n_rows] fp32 (per-row mean weights), ranges = [(row_begin, row_end)]
+    per class (at most 128 per call), ks the picks per class.  Returns [ranking of class c] as device int32 tensors (row
+    numbers relative to the class's first row)."""
+    _chk(feats, weights)
+    assert feats.dtype == torch.float32 and weights.dtype == torch.float32 and feats.dim() == 2 and weights.numel() == feats.shape[0]
+    offs = [0]
+    for k in ks:
+        offs.append(offs[-1] + int(k))
+    ranking = torch.empty(max(offs[-1], 1), dtype=torch.int32, device=feats.device)
+    tab = (_lib.IcarlClass * len(ranges))()
+    for i, (lo, hi) in enumerate(ranges):
+        tab[i].row_begin, tab[i].row_end, tab[i].k, tab[i].out_off = int(lo), int(hi), int(ks[i]), offs[i]
+    check(_lib.lib().clhip_icarl_herd(_ptr(feats), feats.shape[0], feats.shape[1], _ptr(weights), tab, len(ranges), _ptr(ranking),
+                                      ranking.shape[0], _stream()), "clhip_icarl_herd")
+    return [ranking[offs[i]:offs[i + 1]] for i in range(len(ranges))]
+
+
+def icarl_segments(segs, device):
+    """Device clhip_icarl_segment table from [(row_begin, row_end, col_off, ncols, scale, kind)]."""
+    import numpy as np
+    host = np.zeros((len(segs), 6), dtype=np.int32)
+    for i, (r0, r1, o, nc, sc, kind) in enumerate(segs):
+        host[i] = (r0, r1, o, nc, np.array([sc], dtype=np.float32).view(np.int32)[0], kind)
+    return torch.from_numpy(host).to(device)
+
+
+def icarl_loss_segments(logits, labels, targets, segs, n_segs, T=2.0, stats=None):
+    """clhip_icarl_loss_segments over logits [N, ld]: returns (loss[1], dlogits [N, ld]); targets [N, ld_t] or None."""
+    _chk(logits, labels, targets, segs, stats)
+    assert logits.dtype == torch.float32 and labels.dtype == torch.int64 and segs.dtype == torch.int32
+    N, ld = logits.shape
+    dz = torch.empty_like(logits)
+    loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
+    check(_lib.lib().clhip_icarl_loss_segments(_ptr(logits), _ptr(labels), _ptr(targets) if targets is not None else None,
+                                               targets.shape[1] if targets is not None else 0, N, ld, _ptr(segs), int(n_segs), float(T),
+                                               _ptr(dz), _ptr(loss), _ptr(stats) if stats is not None else None, _stream()),
+          "clhip_icarl_loss_segments")
+    return loss, dz
+
+
+def icarl_nme(feats, means, offset1, nc, n_outputs, n_rows=None):
+    """clhip_icarl_nme: the 1-of-C rows [N, n_outputs]; means None = the task has no exemplars yet (n_rows rows)."""
+    _chk(feats, means)
+    N = feats.shape[0] if feats is not None else int(n_rows)
+    dev = feats.device if feats is not None else torch.device("cuda")
+    out = torch.empty((N, n_outputs), dtype=torch.float32, device=dev)
+    check(_lib.lib().clhip_icarl_nme(_ptr(feats) if means is not None else None, _ptr(means) if means is not None else None, N,
+                                     feats.shape[1] if means is not None else 0, int(nc), int(offset1), int(n_outputs), _ptr(out),
+                                     _stream()), "clhip_icarl_nme")
+    return out

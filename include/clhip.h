@@ -525,6 +525,47 @@ int clhip_gather_tasks(const clhip_task_src* tasks_dev, int T, size_t row_elems,
 int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols, int K, const int64_t* labels_i64,
                              int64_t* correct, int64_t* total, int64_t* out_of_range, void* stream);
 
+/* ------------------------------------------------------------------ iCaRL
+ * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471), the loss of update_representation (:482-598) over
+ * one mixed batch, and the nearest-mean-of-exemplars classifier of Net.forward (:142-186).
+ *
+ *   icarl_herd          the prioritised exemplar lists of ALL classes of a task in one launch, one workgroup per class,
+ *                       over features computed ONCE (the reference recomputes them K (n/B + 1) times per class).
+ *                       feats[n_rows][F] fp32 (device), w[n_rows] the per-row mean weights (device), classes_host: HOST table
+ *                       of n_classes <= CLHIP_ICARL_MAX_CLASSES row ranges (checked here, passed by value): class c owns
+ *                       rows [row_begin, row_end) (at most CLHIP_ICARL_MAX_CLASS_ROWS), picks k <= rows of them and writes
+ *                       ranking[out_off .. out_off + k) (device int32, row numbers RELATIVE to row_begin).
+ *                       mu = sum_i w_i f_i (f64 sums).  Pick k = the row not yet taken with the smallest
+ *                       || mu - (f_i + S_k) / (k + 1) ||, S_k the fp32 sum of the features already chosen; evaluated as
+ *                       || r - f_i ||, r = (k + 1) mu - S_k (the same quantity times k + 1: no Gram matrix, no expanded
+ *                       square), differences in fp32, squares summed in f64; the lowest row wins a tie.
+ *                       F <= CLHIP_ICARL_MAX_FEATS (mu, S and r live in LDS).
+ *   icarl_loss_segments as softmax_ce_segments (N <= 1024 rows, n_segs <= CLHIP_CE_MAX_SEGS, fixed summation order, hits of
+ *                       segment 0 into stats[1], malformed segment or label => NaN loss) with a kind per segment:
+ *                         kind 0  scale * mean_i CE_i over the class slice against labels           (the current batch)
+ *                         kind 1  scale * T^2 * KLDiv_batchmean(log_softmax(z / T), softmax(target / T)) over the slice,
+ *                                 target = targets[row][ld_t] (same row numbers as logits); a segment whose OWN value is
+ *                                 negative (rounding, :584-587) adds nothing and gets zero gradient — decided on the device.
+ *   net_loss_step_icarl net_loss_step_segments with that loss: forward, icarl_loss_segments, backward in one call.
+ *   icarl_nme           out[N][n_outputs] = 0, and 1 at offset1 + argmin_c || means[c] - feats[i] || (c < C, the first
+ *                       minimum wins; squares summed in f64, distances compared in fp32).  means == NULL: the task has no
+ *                       exemplars yet, out = -10e10 everywhere and 1 / C inside [offset1, offset1 + C) (:146-155).        */
+#define CLHIP_ICARL_MAX_CLASSES 128
+#define CLHIP_ICARL_MAX_FEATS 4096
+#define CLHIP_ICARL_MAX_CLASS_ROWS 65536
+typedef struct clhip_icarl_class { int row_begin; int row_end; int k; int out_off; } clhip_icarl_class;
+typedef struct clhip_icarl_segment { int row_begin; int row_end; int col_off; int ncols; float scale; int kind; } clhip_icarl_segment;
+int clhip_icarl_herd(const float* feats, long n_rows, int F, const float* w, const clhip_icarl_class* classes_host,
+                     int n_classes, int* ranking, long ranking_len, void* stream);
+int clhip_icarl_loss_segments(const float* logits, const int64_t* labels_i64, const float* targets, int ld_t, int N, int ld,
+                              const clhip_icarl_segment* segs, int n_segs, float T, float* dlogits, float* loss_out,
+                              double* stats, void* stream);
+int clhip_net_loss_step_icarl(void* handle, const float* params, float* grads, const float* x, const int64_t* labels_i64,
+                              const float* targets, int ld_t, int N, const clhip_icarl_segment* segs, int n_segs, float T,
+                              void* ws, float* loss_out, double* stats, float* logits_out, void* stream);
+int clhip_icarl_nme(const float* feats, const float* means, int N, int F, int C, int offset1, int n_outputs, float* out,
+                    void* stream);
+
 #ifdef CLHIP_VISIBILITY_PUSHED
 #pragma GCC visibility pop
 #undef CLHIP_VISIBILITY_PUSHED
