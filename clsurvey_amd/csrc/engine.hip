@@ -1070,40 +1070,21 @@ int clhip_net_loss_step_slice(void* handle, const float* params, float* grads, c
     return rc;
 }
 
-// forward (every layer: the fused fc_tail knows one slice only) + segmented cross-entropy + backward: the rehearsal
-// baselines' whole step over [current batch | exemplar chunks] (csrc/rehearsal.hip).
-int clhip_net_loss_step_segments(void* handle, const float* params, float* grads, const float* x, const int64_t* labels,
-                                 int N, const clhip_ce_segment* segs, int n_segs, void* ws, float* loss_out, double* stats,
-                                 float* logits_out, void* stream) {
+// forward (every layer: the fused fc_tail knows one slice only) + segmented loss (loss.hip) + backward: the whole step of
+// an exemplar method over [current batch | exemplar chunks].
+int clhip_net_loss_step_loss_segments(void* handle, const float* params, float* grads, const float* x, const int64_t* labels,
+                                      const float* targets, int ld_t, int N, const clhip_loss_segment* segs, int n_segs, float T,
+                                      void* ws, float* loss_out, double* stats, float* logits_out, void* stream) {
     NetPlan* p = static_cast<NetPlan*>(handle);
-    if (!p || !ws || !labels || !segs || n_segs < 1 || n_segs > CLHIP_CE_MAX_SEGS) return CLHIP_EINVAL;
-    if (!params || !x || N <= 0 || N > p->max_batch || N > 1024) return CLHIP_EINVAL;
+    if (!p || !ws || !labels || !segs || n_segs < 1 || n_segs > CLHIP_LOSS_MAX_SEGS) return CLHIP_EINVAL;
+    if (!params || !x || N <= 0 || N > p->max_batch || N > CLHIP_LOSS_MAX_ROWS) return CLHIP_EINVAL;
     char* base = static_cast<char*>(ws);
     float* dlogits = reinterpret_cast<float*>(base + p->off_dlogits);
     float* loss_dev = loss_out ? loss_out : reinterpret_cast<float*>(base + p->off_loss);
     int rc = net_forward_impl(handle, params, x, N, ws, logits_out, stream, 0, nullptr, grads != nullptr);
     if (rc) return rc;
     const float* logits = reinterpret_cast<float*>(base + p->off_acts) + p->layers.back().act_off;
-    rc = clhip_softmax_ce_segments(logits, labels, N, p->n_classes, segs, n_segs, dlogits, loss_dev, stats, stream);
-    if (rc) return rc;
-    if (grads) rc = net_backward_impl(handle, params, grads, x, N, ws, dlogits, stream, false, true);
-    return rc;
-}
-
-// the same pass with iCaRL's loss (csrc/icarl.hip): update_representation over [current batch | distillation chunks]
-int clhip_net_loss_step_icarl(void* handle, const float* params, float* grads, const float* x, const int64_t* labels,
-                              const float* targets, int ld_t, int N, const clhip_icarl_segment* segs, int n_segs, float T,
-                              void* ws, float* loss_out, double* stats, float* logits_out, void* stream) {
-    NetPlan* p = static_cast<NetPlan*>(handle);
-    if (!p || !ws || !labels || !segs || n_segs < 1 || n_segs > CLHIP_CE_MAX_SEGS) return CLHIP_EINVAL;
-    if (!params || !x || N <= 0 || N > p->max_batch || N > 1024) return CLHIP_EINVAL;
-    char* base = static_cast<char*>(ws);
-    float* dlogits = reinterpret_cast<float*>(base + p->off_dlogits);
-    float* loss_dev = loss_out ? loss_out : reinterpret_cast<float*>(base + p->off_loss);
-    int rc = net_forward_impl(handle, params, x, N, ws, logits_out, stream, 0, nullptr, grads != nullptr);
-    if (rc) return rc;
-    const float* logits = reinterpret_cast<float*>(base + p->off_acts) + p->layers.back().act_off;
-    rc = clhip_icarl_loss_segments(logits, labels, targets, ld_t, N, p->n_classes, segs, n_segs, T, dlogits, loss_dev, stats, stream);
+    rc = clhip_loss_segments(logits, labels, targets, ld_t, N, p->n_classes, segs, n_segs, T, dlogits, loss_dev, stats, stream);
     if (rc) return rc;
     if (grads) rc = net_backward_impl(handle, params, grads, x, N, ws, dlogits, stream, false, true);
     return rc;

@@ -1,21 +1,11 @@
-// Loss kernels: softmax cross-entropy (mean / sum) and the MAS sum-of-squares objective.
+// Loss kernels: softmax cross-entropy (mean / sum), the MAS sum-of-squares objective, LwF's stacked heads and the
+// segmented CE / distillation loss of the exemplar methods.
 // Tiny tensors ([N<=~1k][C<=1k]); one block, fixed reduction order => deterministic.
 #include "common.hpp"
 
 namespace {
 
 constexpr int LOSS_BLOCK = 1024;  // 16 waves
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // One wave per row, rows strided over the 16 waves of the single block.  The tensor is tiny, so
 // the kernel is pure latency: rows are fetched RB at a time per wave (all loads in flight
@@ -69,9 +59,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void softmax_ce_kernel(
             }
             float gm = wave_max(m);
             // first index attaining the max (torch.max tie rule: lowest index)
-            int cand = (m == gm) ? am : 0x7fffffff;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+            const int cand = wave_min((m == gm) ? am : 0x7fffffff);
             float se = 0.f, zy;
             if (narrow) {
                 float ex = lane < C ? expf(zr[b] - gm) : 0.f;
@@ -307,6 +295,159 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lwf_loss_kernel(const float* __res
     }
 }
 
+// The segmented loss of the exemplar methods (clhip_loss_segments).  Phase 1: one wave per row (rows strided over the 16
+// waves) computes the row's value over its class slice; a cross-entropy row also writes its gradient row (a slice of <= 64
+// classes is loaded once and kept in registers), a distillation row keeps its softmax statistics in LDS; phase 2: one wave
+// per segment sums its rows in f64 (fixed lane assignment + butterfly) and decides the segment's gate (a distillation
+// segment whose own value is negative counts as the integer 0 of icarl.py:584-587: no loss, no gradient); phase 3: the
+// gradient rows of the distillation segments and zeros for rows of no segment; thread 0 sums the segments in order => the
+// loss does not depend on scheduling.
+__global__ __launch_bounds__(LOSS_BLOCK) void loss_segments_kernel(
+    const float* __restrict__ logits, const int64_t* __restrict__ labels, const float* __restrict__ targets, int ld_t, int N, int ld,
+    const clhip_loss_segment* __restrict__ segs, int n_segs, float T, float* __restrict__ dlogits, float* __restrict__ loss_out,
+    double* __restrict__ stats) {
+    __shared__ clhip_loss_segment s_seg[CLHIP_LOSS_MAX_SEGS];
+    __shared__ int s_valid[CLHIP_LOSS_MAX_SEGS];
+    __shared__ float s_gate[CLHIP_LOSS_MAX_SEGS];
+    __shared__ double s_part[CLHIP_LOSS_MAX_SEGS];
+    __shared__ float s_val[CLHIP_LOSS_MAX_ROWS];
+    __shared__ float s_zm[CLHIP_LOSS_MAX_ROWS], s_zl[CLHIP_LOSS_MAX_ROWS], s_tm[CLHIP_LOSS_MAX_ROWS], s_tl[CLHIP_LOSS_MAX_ROWS];
+    __shared__ short s_rowseg[CLHIP_LOSS_MAX_ROWS];
+    __shared__ unsigned char s_hit[CLHIP_LOSS_MAX_ROWS];
+    __shared__ int s_bad, s_hits;
+    if (threadIdx.x == 0) { s_bad = 0; s_hits = 0; }
+    for (int g = threadIdx.x; g < n_segs; g += LOSS_BLOCK) {
+        const clhip_loss_segment sg = segs[g];
+        s_seg[g] = sg;
+        s_valid[g] = sg.row_begin >= 0 && sg.row_begin < sg.row_end && sg.row_end <= N && sg.col_off >= 0 && sg.ncols > 0 &&
+                     sg.col_off + sg.ncols <= ld && (sg.kind == 0 || (sg.kind == 1 && targets && sg.col_off + sg.ncols <= ld_t));
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float invT = 1.f / T;
+    for (int row = wave; row < N; row += LOSS_BLOCK / 64) {
+        int g = -1;                                    // first valid segment that holds the row (wave-uniform scan)
+        for (int k = 0; k < n_segs; ++k)
+            if (s_valid[k] && row >= s_seg[k].row_begin && row < s_seg[k].row_end) { g = k; break; }
+        if (lane == 0) s_rowseg[row] = (short)g;
+        if (g < 0) {
+            if (lane == 0) { s_val[row] = 0.f; s_hit[row] = 0; }
+            continue;
+        }
+        const int o = s_seg[g].col_off, C = s_seg[g].ncols;
+        const float* z = logits + (size_t)row * ld + o;
+        if (s_seg[g].kind == 0) {                      // never gated: the gradient row is written here, from the same loads
+            const int y = (int)labels[row];
+            const bool ok = y >= 0 && y < C;
+            const float w = s_seg[g].scale / (float)(s_seg[g].row_end - s_seg[g].row_begin);
+            float* dz = dlogits + (size_t)row * ld;
+            float gm, lse, zy;
+            int am;
+            if (C <= 64) {                             // the task heads: ONE load of the slice, everything from registers
+                const float zv = lane < C ? z[lane] : -INFINITY;
+                gm = wave_max(zv);
+                am = wave_min((lane < C && zv == gm) ? lane : 0x7fffffff);      // torch.max tie rule: lowest index
+                lse = logf(wave_sum(lane < C ? expf(zv - gm) : 0.f));
+                zy = __shfl(zv, ok ? y : 0, 64);
+                for (int c0 = 0; c0 < ld; c0 += 64) {   // wave-uniform trip count: every lane takes part in the shuffle
+                    const int c = c0 + lane, cc = c - o;
+                    const float zc = __shfl(zv, (cc >= 0 && cc < 64) ? cc : 0, 64);
+                    if (c < ld) dz[c] = (cc >= 0 && cc < C) ? (expf(zc - gm - lse) - (cc == y ? 1.f : 0.f)) * w : 0.f;
+                }
+            } else {
+                float m = -INFINITY, se = 0.f;
+                am = 0x7fffffff;
+                for (int c = lane; c < C; c += 64) {
+                    const float v = z[c];
+                    if (v > m) { m = v; am = c; }
+                }
+                gm = wave_max(m);
+                am = wave_min(m == gm ? am : 0x7fffffff);
+                for (int c = lane; c < C; c += 64) se += expf(z[c] - gm);
+                lse = logf(wave_sum(se));
+                for (int c = lane; c < ld; c += 64) {
+                    const int cc = c - o;
+                    dz[c] = (cc >= 0 && cc < C) ? (expf(z[cc] - gm - lse) - (cc == y ? 1.f : 0.f)) * w : 0.f;
+                }
+                zy = ok ? z[y] : 0.f;
+            }
+            if (lane == 0) {
+                if (!ok) s_bad = 1;
+                s_val[row] = ok ? -(zy - gm - lse) : 0.f;
+                s_hit[row] = (unsigned char)(g == 0 && am == y);
+            }
+        } else {
+            const float* tr = targets + (size_t)row * ld_t + o;
+            float zm = -INFINITY, tm = -INFINITY;
+            for (int c = lane; c < C; c += 64) { zm = fmaxf(zm, z[c] * invT); tm = fmaxf(tm, tr[c] * invT); }
+            zm = wave_max(zm); tm = wave_max(tm);
+            float zs = 0.f, ts = 0.f;
+            for (int c = lane; c < C; c += 64) { zs += expf(z[c] * invT - zm); ts += expf(tr[c] * invT - tm); }
+            const float zl = logf(wave_sum(zs)), tl = logf(wave_sum(ts));
+            float kl = 0.f;                                       // sum_c p (log p - log q), p = softmax(target / T), q = softmax(z / T)
+            for (int c = lane; c < C; c += 64) {
+                const float lp = tr[c] * invT - tm - tl, lq = z[c] * invT - zm - zl;
+                const float p = expf(lp);
+                kl += p > 0.f ? p * (lp - lq) : 0.f;
+            }
+            kl = wave_sum(kl);
+            if (lane == 0) {
+                s_val[row] = kl * T * T;
+                s_hit[row] = 0;
+                s_zm[row] = zm; s_zl[row] = zl; s_tm[row] = tm; s_tl[row] = tl;
+            }
+        }
+    }
+    __syncthreads();
+    for (int g = wave; g < n_segs; g += LOSS_BLOCK / 64) {
+        double t = 0.0;
+        int h = 0;
+        if (s_valid[g]) {
+            for (int r = s_seg[g].row_begin + lane; r < s_seg[g].row_end; r += 64) {
+                if (s_rowseg[r] == g) { t += (double)s_val[r]; h += s_hit[r]; }    // a row counts for the first segment that holds it
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { t += __shfl_xor(t, off, 64); h += __shfl_xor(h, off, 64); }
+        if (lane == 0) {
+            double v = s_valid[g] ? t / (double)(s_seg[g].row_end - s_seg[g].row_begin) : 0.0;
+            const bool off_ = s_valid[g] && s_seg[g].kind == 1 && (float)v < 0.f;
+            s_gate[g] = off_ ? 0.f : 1.f;
+            s_part[g] = (s_valid[g] && !off_) ? (double)s_seg[g].scale * v : 0.0;
+            if (g == 0) s_hits = h;
+        }
+    }
+    __syncthreads();
+    for (int row = wave; row < N; row += LOSS_BLOCK / 64) {
+        const int g = s_rowseg[row];
+        float* dz = dlogits + (size_t)row * ld;
+        if (g < 0 || s_gate[g] == 0.f) {
+            for (int c = lane; c < ld; c += 64) dz[c] = 0.f;
+            continue;
+        }
+        if (s_seg[g].kind == 0) continue;              // written in phase 1
+        const int o = s_seg[g].col_off, C = s_seg[g].ncols;
+        const float wT = s_seg[g].scale / (float)(s_seg[g].row_end - s_seg[g].row_begin) * T;      // d/dz of T^2 KL = T (q - p)
+        const float* zr = logits + (size_t)row * ld;
+        const float* tr = targets + (size_t)row * ld_t;
+        const float zm = s_zm[row], zl = s_zl[row], tm = s_tm[row], tl = s_tl[row];
+        for (int c = lane; c < ld; c += 64) {
+            const int cc = c - o;
+            dz[c] = (cc >= 0 && cc < C) ? (expf(zr[c] * invT - zm - zl) - expf(tr[c] * invT - tm - tl)) * wT : 0.f;
+        }
+    }
+    if (threadIdx.x == 0) {
+        double td = 0.0;
+        for (int g = 0; g < n_segs; ++g) td += s_part[g];
+        float t = (float)td;
+        bool bad = s_bad != 0;
+        for (int g = 0; g < n_segs; ++g) bad = bad || !s_valid[g];
+        if (bad) t = __int_as_float(0x7fc00000);      // a malformed table or label is reported as a NaN loss
+        loss_out[0] = t;
+        if (stats) { stats[0] += (double)t; stats[1] += (double)s_hits; }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -352,6 +493,18 @@ int clhip_lwf_loss(const float* logits, const int64_t* labels_i64, const float* 
 int clhip_mse_zero_sum(const float* logits, size_t n, float* dlogits, float* loss_out, void* stream) {
     if (!logits || !dlogits || !loss_out || n == 0) return CLHIP_EINVAL;
     hipLaunchKernelGGL(mse_zero_sum_kernel, dim3(1), dim3(LOSS_BLOCK), 0, as_stream(stream), logits, n, dlogits, loss_out);
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+int clhip_loss_segments(const float* logits, const int64_t* labels_i64, const float* targets, int ld_t, int N, int ld,
+                        const clhip_loss_segment* segs, int n_segs, float T, float* dlogits, float* loss_out, double* stats,
+                        void* stream) {
+    if (!logits || !labels_i64 || !segs || !dlogits || !loss_out) return CLHIP_EINVAL;
+    if (N <= 0 || N > CLHIP_LOSS_MAX_ROWS || ld <= 0 || n_segs < 1 || n_segs > CLHIP_LOSS_MAX_SEGS || !(T > 0.f)) return CLHIP_EINVAL;
+    if (targets && ld_t <= 0) return CLHIP_EINVAL;
+    hipLaunchKernelGGL(loss_segments_kernel, dim3(1), dim3(LOSS_BLOCK), 0, as_stream(stream), logits, labels_i64, targets, ld_t, N, ld,
+                       segs, n_segs, T, dlogits, loss_out, stats);
     CLHIP_LAUNCH_CHECK();
     return 0;
 }

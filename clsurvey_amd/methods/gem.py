@@ -16,18 +16,8 @@ import torch.nn as nn
 from .. import _lib
 from .._lib import check
 from ..data import DeviceLoader, TensorTaskDataset
-from ..net import NetEngine
 from ..optim import SGD
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def compute_offsets(task_idx, cum_nc_per_task):
-    """rehearsal/model/common.py:106-118."""
-    o1 = 0 if task_idx == 0 else int(cum_nc_per_task[task_idx - 1])
-    return o1, int(cum_nc_per_task[task_idx])
+from .exemplar import ExemplarNet, SharedRowDropout, _stream, compute_offsets  # noqa: F401  (compute_offsets: imported from here)
 
 
 def extend_head(model, n_outputs):
@@ -42,10 +32,11 @@ def extend_head(model, n_outputs):
     return model
 
 
-class GemNet:
-    """gem.Net (gem.py:83-387). Picklable like the reference's nn.Module (torch.save(model) /
-    copy.deepcopy(model) in train_rehearsal.py:176-180): the pickle carries the wrapped net, the exemplar
-    tensors and the counters; engine / workspaces are rebuilt on load (init_setup)."""
+class GemNet(SharedRowDropout, ExemplarNet):
+    """gem.Net (gem.py:83-387).  The pickle carries the wrapped net, the exemplar tensors (memory_x / memory_labels, whole)
+    and the counters.  Dropout: one shared mask row per layer (gem.py:166-196), reset at every observe."""
+
+    _TRANSIENT_EXTRA = ("G", "_gram_ws", "_gram", "_v", "_info", "_qp_bad", "host_qp")
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, memory_strength=1.0,
                  batch_size=200, in_shape=(3, 64, 64), device="cuda"):
@@ -62,10 +53,7 @@ class GemNet:
         self.init_setup(lr=lr, weight_decay=weight_decay, memory_strength=memory_strength)
 
     def _bind(self):
-        self.engine = NetEngine(self.net, max(self.batch_size, 1), self.in_shape, self.device)
-        self.engine.auto_dropout = False        # Dropout masks are GEM's own (below), not nn.Dropout's
-        self.dropout_masks = {}
-        self.A = self.engine.arena
+        super()._bind(mix=False)
         self.G = torch.zeros((self.n_tasks, self.A.numel), dtype=torch.float32, device=self.device)   # gem.py:131
         L = _lib.lib()
         self._gram_ws = torch.zeros(L.clhip_gem_gram_ws(16), dtype=torch.uint8, device=self.device)
@@ -74,7 +62,6 @@ class GemNet:
         self._info = torch.zeros(2, dtype=torch.int32, device=self.device)          # {violated constraints, status}
         self._qp_bad = torch.zeros(1, dtype=torch.int32, device=self.device)        # sticky: solves that did not report 'ok'
         self.host_qp = None          # tests only: a host solver f(gram, t, rows, margin) -> v replaces the device QP
-        self.stats = torch.zeros(2, dtype=torch.float64, device=self.device)
 
     def init_setup(self, args=None, lr=None, weight_decay=None, memory_strength=None):
         """gem.py:146-155: fresh SGD(momentum 0.9) and margin; called after construction and after torch.load."""
@@ -84,55 +71,7 @@ class GemNet:
         self.opt = SGD(self.net.parameters(), lr, momentum=0.9, weight_decay=weight_decay)       # gem.py:153
         self.margin = memory_strength
 
-    # ------------------------------------------------------------------ gem.py:166-196 (manual dropout)
-    def reset_dropout_config(self):
-        self.dropout_masks = {}
-
-    def _dropout(self, train, p_retain_unit=0.5):
-        """Training mode: every Dropout of the plan multiplies its input by ONE mask row Bernoulli(p_retain)/p_retain of a
-        single sample's shape, drawn when first needed after a reset and shared by all samples and passes until the next
-        reset (gem.py:180-191; p_retain is the fixed 0.5 of the reference's signature, not module.p).  Eval: identity."""
-        for li in self.engine.drops:
-            if not train:
-                self.engine.set_dropout(li, None)
-                continue
-            if li not in self.dropout_masks:
-                self.dropout_masks[li] = self._draw_mask(li, self.engine.in_elems[li], p_retain_unit)
-            self.engine.set_dropout(li, self.dropout_masks[li])
-
-    def _draw_mask(self, layer, n, p_retain_unit):
-        """gem.py:183-186: torch.bernoulli(fill(p_retain)) / p_retain over one sample's features (device generator)."""
-        return torch.full((n,), p_retain_unit, dtype=torch.float32, device=self.device).bernoulli_().div_(p_retain_unit)
-
-    _TRANSIENT = ("engine", "A", "G", "_gram_ws", "_gram", "_v", "_info", "_qp_bad", "host_qp", "stats", "opt", "dropout_masks")
-
-    def __getstate__(self):
-        return {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
-
-    def __setstate__(self, state):
-        self.__dict__.update(state)
-        self.device = torch.device(self.device)
-        self.net = self.net.to(self.device)
-        self._bind()
-        self.opt = None
-
-    def compute_offsets(self, task_idx, cum_nc_per_task):
-        return compute_offsets(task_idx, cum_nc_per_task)
-
-    def parameters(self):
-        return self.net.parameters()
-
-    def eval(self):
-        return self
-
-    def to(self, device):
-        return self
-
     # ------------------------------------------------------------------ memory
-    def init_new_task(self, t):
-        self.observed_tasks.append(t)
-        self.old_task = t
-
     def fill_buffer(self, t, x, y):
         """gem.py:322-345 (ring buffer; exemplar tensors instead of paths)."""
         bsz = y.shape[0]
@@ -244,21 +183,3 @@ class GemNet:
         loss, _ = self.engine.loss_step(x, y, "ce_mean", True, self.stats, class_slice=sl)
         self.opt.step()
         return loss, self.stats[1]
-
-    def eval_batch(self, x, y, t, stats):
-        """main_rehearsal.py:18-35: CE and hits on the task slice (accumulated into stats on the device)."""
-        sl = compute_offsets(t, self.cum_nc_per_task)
-        self._dropout(False)
-        return self.engine.loss_step(x, y, "ce_mean", False, stats, class_slice=sl)[0]
-
-    def __call__(self, x, t, **kw):
-        return self.forward(x, t)
-
-    def forward(self, x, t):
-        """gem.py:169-204 (eval): logits with everything outside the task slice at -1e11."""
-        self._dropout(False)
-        logits = self.engine.forward(x)
-        o1, o2 = compute_offsets(t, self.cum_nc_per_task)
-        out = torch.full_like(logits, -10e10)
-        out[:, o1:o2] = logits[:, o1:o2]
-        return out

@@ -8,7 +8,7 @@ image and of every exemplar chosen so far once per pick (:394-427).  Here the ex
     manage_memory   features of the task's training set ONCE (chunks through the plan, NetEngine.layer_input of the first
                     Linear layer), then clhip_icarl_herd: the ranked lists of all classes of the task in one launch
     observe         host draws exactly as the reference makes them, clhip_rehearsal_assemble (images; a second launch
-                    gathers the stored distillation rows), then ONE clhip_net_loss_step_icarl over
+                    gathers the stored distillation rows), then ONE clhip_net_loss_step_loss_segments over
                     [current batch | distillation chunks] and one fused SGD step
     forward         class means from the stored exemplars once per (model, task), clhip_icarl_nme per batch
 
@@ -21,19 +21,15 @@ import random
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, ops
 from .._lib import check
-from ..net import NetEngine
 from ..optim import SGD
-from .gem import compute_offsets, extend_head
-from .rehearsal import FUSED_MAX_ROWS, FUSED_MAX_SEGS, _Order
+from .exemplar import ExemplarNet, PerRowDropout, _stream, compact_blocks, compute_offsets
+from .gem import extend_head
+from .rehearsal import _Order
 
 T_DISTILL = 2.0                 # update_representation(..., T=2)
-HERD_MAX_CLASSES, HERD_MAX_FEATS = 128, 4096        # CLHIP_ICARL_MAX_CLASSES / _FEATS (include/clhip.h)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+HERD_MAX_FEATS = 4096           # CLHIP_ICARL_MAX_FEATS (include/clhip.h)
 
 
 def init_head(model, n_outputs):
@@ -111,12 +107,11 @@ def segment_scales(chunk_counts, reg):
     return scale
 
 
-class IcarlNet:
-    """icarl.Net.  Picklable like GemNet / RehearsalNet: the pickle carries the net, the counters, the stored exemplar rows
-    and their distillation targets only; engine / workspaces / optimizer are rebuilt on load (init_setup)."""
+class IcarlNet(PerRowDropout, ExemplarNet):
+    """icarl.Net.  The pickle carries the net, the counters, the stored exemplar rows and their distillation targets only.
+    Dropout: the net's own nn.Dropout, one mask per step over the MIXED batch."""
 
-    _TRANSIENT = ("engine", "A", "stats", "opt", "x_mix", "y_mix", "t_mix", "_acc", "store_x", "store_t", "_store_lab", "_means",
-                  "_draw_mask", "_scratch_lab", "last_ranking")
+    _TRANSIENT_EXTRA = ("t_mix", "store_x", "store_t", "_store_lab", "_means", "_scratch_lab", "last_ranking")
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, memory_strength=0.0,
                  batch_size=200, in_shape=(3, 64, 64), device="cuda"):
@@ -135,29 +130,17 @@ class IcarlNet:
         self.n_append, self.chunk_size, self.total_batch_size = 0, batch_size, batch_size
         self.force_segmented = False                                 # tests: run the BatchNorm path on any plan
         self.last_path = None                                        # 'fused' | 'segmented' | None (no observe yet)
-        self._alloc_store()
+        self._load_rows({})
         self._bind()
         self.init_setup(lr=lr, weight_decay=weight_decay, memory_strength=memory_strength)
 
     # ------------------------------------------------------------------ state
-    def _alloc_store(self):
-        n = self.n_total_memories
-        self.store_x = torch.zeros((n,) + self.in_shape, dtype=torch.float32, device=self.device)
-        self.store_t = torch.zeros((n, self.n_outputs), dtype=torch.float32, device=self.device)     # mem_class_y rows
-        self._store_lab = torch.zeros((n,), dtype=torch.int64, device=self.device)      # (the assemble kernel copies a label per row)
-
     def _bind(self):
-        self.engine = NetEngine(self.net, max(self.batch_size, 1), self.in_shape, self.device)
-        self.engine.auto_dropout = False        # one mask per step over the MIXED batch, drawn here (_dropout)
+        super()._bind()
         self.fc_first = next(i for i, sp in enumerate(self.engine.layers) if sp[0] == "fc")
-        self.A = self.engine.arena
-        self.stats = torch.zeros(2, dtype=torch.float64, device=self.device)
-        rows = max(self.batch_size, 1)
-        self.x_mix = torch.empty((rows,) + self.in_shape, dtype=torch.float32, device=self.device)
-        self.y_mix = torch.empty((rows,), dtype=torch.int64, device=self.device)
+        rows = self.engine.max_batch
         self.t_mix = torch.zeros((rows, self.n_outputs), dtype=torch.float32, device=self.device)
         self._scratch_lab = torch.empty((rows,), dtype=torch.int64, device=self.device)
-        self._acc = None
         self._means = {}
         self.last_ranking = None      # (device int32 ranking, class offsets) of the last manage_memory; not pickled
 
@@ -194,58 +177,19 @@ class IcarlNet:
         """Store rows that hold an exemplar, class after class."""
         return [c * self.exemplar_count + e for c in range(len(self.class_len)) for e in range(self.class_len[c])]
 
-    def __getstate__(self):
-        state = {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
+    def _rows_state(self):
         idx = torch.tensor(self.stored_rows(), dtype=torch.int64, device=self.device)
-        state["_rows_x"] = self.store_x.index_select(0, idx)          # a view would pickle the whole store
-        state["_rows_t"] = self.store_t.index_select(0, idx)
-        return state
+        return {"_rows_x": self.store_x.index_select(0, idx), "_rows_t": self.store_t.index_select(0, idx)}
 
-    def __setstate__(self, state):
-        rows_x, rows_t = state.pop("_rows_x"), state.pop("_rows_t")
-        self.__dict__.update(state)
-        self.device = torch.device(self.device)
-        self.net = self.net.to(self.device)
-        self._alloc_store()
-        if rows_x.shape[0]:
+    def _load_rows(self, rows):
+        n = self.n_total_memories
+        self.store_x = torch.zeros((n,) + self.in_shape, dtype=torch.float32, device=self.device)
+        self.store_t = torch.zeros((n, self.n_outputs), dtype=torch.float32, device=self.device)     # mem_class_y rows
+        self._store_lab = torch.zeros((n,), dtype=torch.int64, device=self.device)      # (the assemble kernel copies a label per row)
+        if rows and rows["_rows_x"].shape[0]:
             idx = torch.tensor(self.stored_rows(), dtype=torch.int64, device=self.device)
-            self.store_x[idx] = rows_x.to(self.device)
-            self.store_t[idx] = rows_t.to(self.device)
-        self._bind()
-        self.opt = None
-
-    def compute_offsets(self, task_idx, cum_nc_per_task=None):
-        return compute_offsets(task_idx, self.cum_nc_per_task if cum_nc_per_task is None else cum_nc_per_task)
-
-    def parameters(self):
-        return self.net.parameters()
-
-    def eval(self):
-        return self
-
-    def to(self, device):
-        return self
-
-    def _slice(self, task):
-        o1, o2 = compute_offsets(task, self.cum_nc_per_task)
-        return (o1, o2 - o1)
-
-    # ------------------------------------------------------------------ dropout (nn.Dropout of net_classifier)
-    def _draw_mask(self, layer, n, elems, p):
-        """nn.Dropout in training mode: Bernoulli(1 - p) / (1 - p) per element and row (device generator)."""
-        keep = 1.0 - p
-        return torch.empty((n, elems), dtype=torch.float32, device=self.device).bernoulli_(keep).div_(keep)
-
-    def _dropout(self, n):
-        """Masks of one pass over n rows, or none in eval mode.  Returns {layer: mask}."""
-        masks = {}
-        for li, m in self.engine.drops.items():
-            if self.net.training and m.p > 0:
-                masks[li] = self._draw_mask(li, n, self.engine.in_elems[li], m.p)
-                self.engine.set_dropout(li, masks[li])
-            else:
-                self.engine.set_dropout(li, None)
-        return masks
+            self.store_x[idx] = rows["_rows_x"]
+            self.store_t[idx] = rows["_rows_t"]
 
     # ------------------------------------------------------------------ features / training output
     def features(self, x):
@@ -258,57 +202,27 @@ class IcarlNet:
         return torch.cat(out)
 
     def forward_training(self, x, t):
-        """:188-201: the head's output, -10e10 outside the task's slice."""
+        """:188-201: the head's output of any number of rows, -10e10 outside the task's slice (dropout as the net's mode
+        says, fresh masks per pass)."""
         out = []
         for s in range(0, x.shape[0], self.engine.max_batch):
             xb = x[s:s + self.engine.max_batch].contiguous()
             self._dropout(xb.shape[0])
             out.append(self.engine.forward(xb))
-        logits = torch.cat(out)
-        o1, o2 = compute_offsets(t, self.cum_nc_per_task)
-        res = torch.full_like(logits, -10e10)
-        res[:, o1:o2] = logits[:, o1:o2]
-        return res
+        return self._mask_slice(torch.cat(out), t)
 
     # ------------------------------------------------------------------ memory (:314-479)
-    def init_new_task(self, t):
-        self.observed_tasks.append(t)
-        self.old_task = t
-
     def _truncate(self, new_count):
-        """Every stored class keeps its first new_count entries; blocks compacted in place, ascending (a destination
-        never overtakes its source, pieces no longer than the gap: no piece overlaps its own source)."""
-        old = self.exemplar_count
-        for c in range(len(self.class_len)):
-            keep = min(self.class_len[c], new_count)
-            src, dst = c * old, c * new_count
-            gap = src - dst
-            s = 0
-            while gap > 0 and s < keep:
-                e = min(keep, s + gap)
-                self.store_x[dst + s:dst + e] = self.store_x[src + s:src + e]
-                self.store_t[dst + s:dst + e] = self.store_t[src + s:src + e]
-                s = e
-            self.class_len[c] = keep
+        """Every stored class keeps its first new_count entries; the class blocks are compacted in place."""
+        self.class_len = [min(n, new_count) for n in self.class_len]
+        compact_blocks((self.store_x, self.store_t), self.exemplar_count, new_count, self.class_len)
         self.exemplar_count = new_count
 
     def herd(self, feats, ranges, weights, ks):
-        """clhip_icarl_herd over feats [n_rows][F] (device fp32): ranges = [(row_begin, row_end)] per class, weights the
+        """ops.icarl_herd over feats [n_rows][F] (device fp32): ranges = [(row_begin, row_end)] per class, weights the
         per-row mean weights (device fp32 [n_rows]), ks the picks per class.  Returns the device int32 ranking (classes
         back to back) and the offsets of the classes in it.  No synchronisation."""
-        if not feats.is_cuda or feats.dtype != torch.float32 or not feats.is_contiguous():
-            raise RuntimeError("herding needs a contiguous fp32 HIP tensor")
-        offs = np.concatenate([[0], np.cumsum(ks)]).astype(np.int64)
-        ranking = torch.empty(max(int(offs[-1]), 1), dtype=torch.int32, device=self.device)
-        L = _lib.lib()
-        for s in range(0, len(ranges), HERD_MAX_CLASSES):
-            part = ranges[s:s + HERD_MAX_CLASSES]
-            tab = (_lib.IcarlClass * len(part))()
-            for i, (lo, hi) in enumerate(part):
-                tab[i].row_begin, tab[i].row_end, tab[i].k, tab[i].out_off = int(lo), int(hi), int(ks[s + i]), int(offs[s + i])
-            check(L.clhip_icarl_herd(feats.data_ptr(), feats.shape[0], feats.shape[1], weights.data_ptr(), tab, len(part),
-                                     ranking.data_ptr(), ranking.shape[0], _stream()), "clhip_icarl_herd")
-        return ranking, offs
+        return ops.icarl_herd(feats, weights, ranges, ks, flat=True)
 
     def manage_memory(self, t, args):
         """:314-479 for task t: truncate the stored classes to K/m entries, rank K_c = min(K/m, class size) exemplars of
@@ -369,22 +283,6 @@ class IcarlNet:
         return exemplar_draws(t, self.n_append, self.class_len, self.exemplar_count, self.nc_per_task, self.cum_nc_per_task,
                               self.total_batch_size)
 
-    def _upload(self, gather, segs):
-        """Gather rows (int32) and the clhip_icarl_segment tables (mixed-batch rows; then each segment alone from row 0)
-        in ONE pinned host buffer, one non-blocking copy."""
-        n = len(segs)
-        host = np.empty(len(gather) + 12 * n, dtype=np.int32)
-        host[:len(gather)] = gather
-        tab = host[len(gather):].reshape(2 * n, 6)
-        for i, (r0, r1, o, nc, sc, kind) in enumerate(segs):
-            f = np.array([sc], dtype=np.float32).view(np.int32)[0]
-            tab[i] = (r0, r1, o, nc, f, kind)
-            tab[n + i] = (0, r1 - r0, o, nc, f, kind)
-        pinned = torch.empty(host.shape[0], dtype=torch.int32, pin_memory=True)
-        pinned.numpy()[:] = host
-        dev = pinned.to(self.device, non_blocking=True)
-        return dev[:len(gather)], dev[len(gather):len(gather) + 6 * n], dev[len(gather) + 6 * n:]
-
     def observe(self, x, t, y):
         """:229-246 -> update_representation (:482-598).  Returns device (loss, hits on the current batch) and the batch_stats
         dictionary the shared training loop reads (no projections here)."""
@@ -401,10 +299,12 @@ class IcarlNet:
             for ch in chunks:
                 segs.append((B + len(gather), B + len(gather) + len(ch)) + self._slice(past) + (sc, 1))
                 gather.extend(c * self.exemplar_count + e for c, e in ch)
-        E, N = len(gather), B + len(gather)
+        E, N, n = len(gather), B + len(gather), len(segs)
         if N > self.batch_size:
             raise RuntimeError("icarl: step of %d rows > engine batch %d" % (N, self.batch_size))
-        gather_dev, segs_dev, segs_local = self._upload(gather, segs)
+        # two tables in the one upload: the mixed batch's rows, then each segment alone from row 0 (the segmented path)
+        local = [(0, sg[1] - sg[0]) + sg[2:] for sg in segs]
+        gather_dev, tabs = self._upload(gather, ops.loss_segment_rows(segs + local))
         L = _lib.lib()
         check(L.clhip_rehearsal_assemble(
             x.data_ptr(), y.data_ptr(), B, int(np.prod(self.in_shape)), self.store_x.data_ptr(), self._store_lab.data_ptr(),
@@ -418,53 +318,30 @@ class IcarlNet:
         xm, ym = self.x_mix[:N], self.y_mix[:N]
         masks = self._dropout(N)
         self.stats.zero_()
-        if self.engine.bns or self.force_segmented or N > FUSED_MAX_ROWS or len(segs) > FUSED_MAX_SEGS:
-            loss = self._segmented(xm, ym, segs, segs_local, masks)
-            self.last_path = "segmented"
+        if self._fused(N, n):
+            loss = self.engine.loss_step_segments(xm, ym, tabs[:6 * n], n, self.stats, targets=self.t_mix, T=T_DISTILL)[0].clone()
         else:
-            self.engine._check_x(xm)
-            self.engine._mode()
-            check(L.clhip_net_loss_step_icarl(
-                self.engine._h, self.A.theta.data_ptr(), self.A.grad.data_ptr(), xm.data_ptr(), ym.data_ptr(),
-                self.t_mix.data_ptr(), self.n_outputs, N, segs_dev.data_ptr(), len(segs), T_DISTILL, self.engine.ws.data_ptr(),
-                self.engine.loss.data_ptr(), self.stats.data_ptr(), None, _stream()), "clhip_net_loss_step_icarl")
-            loss = self.engine.loss.clone()
-            self.last_path = "fused"
+            loss = self._segmented(xm, ym, segs, tabs[6 * n:], masks)
         self.opt.step()
         return loss, self.stats[1], {"projected_grads": []}
 
     def _segmented(self, xm, ym, segs, segs_local, masks):
         """The reference's order: the current batch, then every chunk (tasks ascending); one forward / loss / backward per
-        segment (its rows of the step's masks, its own one-row segment table), gradients summed with clhip_axpy."""
-        L = _lib.lib()
-        if self._acc is None:
-            self._acc = torch.empty(self.A.numel, dtype=torch.float32, device=self.device)
-        total = torch.zeros(1, dtype=torch.float32, device=self.device)
+        segment (its rows of the step's masks, its own one-row segment table)."""
         loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        for g, (r0, r1, o, nc, sc, kind) in enumerate(segs):
-            n = r1 - r0
+
+        def one_pass(g):
+            r0, r1 = segs[g][:2]
             for li, m in masks.items():
                 self.engine.set_dropout(li, m[r0:r1])
-            xs = xm[r0:r1]
-            logits = self.engine.forward(xs)
-            dz = torch.empty_like(logits)
-            check(L.clhip_icarl_loss_segments(
-                logits.data_ptr(), ym[r0:r1].data_ptr(), self.t_mix[r0:r1].data_ptr(), self.n_outputs, n, logits.shape[1],
-                segs_local[6 * g:].data_ptr(), 1, T_DISTILL, dz.data_ptr(), loss.data_ptr(),
-                self.stats.data_ptr() if g == 0 else None, _stream()), "clhip_icarl_loss_segments")
-            self.engine.backward(xs, dz)
-            total += loss
-            check(L.clhip_axpy(self._acc.data_ptr(), self.A.grad.data_ptr(), self.A.numel, 1.0, int(g == 0), _stream()), "clhip_axpy")
-        self.A.grad.copy_(self._acc)
-        return total
+            logits = self.engine.forward(xm[r0:r1])
+            _, dz = ops.loss_segments(logits, ym[r0:r1], self.t_mix[r0:r1], segs_local[6 * g:], 1, T_DISTILL,
+                                      self.stats if g == 0 else None, loss=loss)
+            self.engine.backward(xm[r0:r1], dz)
+            return loss, 1.0
+        return self._accumulate(range(len(segs)), one_pass)
 
     # ------------------------------------------------------------------ evaluation
-    def eval_batch(self, x, y, t, stats):
-        """main_rehearsal.py:18-35: CE and hits of the training head on the task slice (validation during training)."""
-        self.net.train(False)
-        self._dropout(x.shape[0])
-        return self.engine.loss_step(x, y, "ce_mean", False, stats, class_slice=compute_offsets(t, self.cum_nc_per_task))[0]
-
     def class_means(self, t, batch_size):
         """[nc_t][n_feat] means of the stored exemplars of task t: per class the mean of batch means (:160-167) over the
         exemplars in STORED order in batches of batch_size; None while the task's first class has no exemplars."""
@@ -499,8 +376,7 @@ class IcarlNet:
         means depends on the order only when a class holds more exemplars than one batch and the last batch is short."""
         if train_mode:
             return self.forward_training(x, t)
-        self.net.train(False)
-        self._dropout(1)
+        self._eval_dropout(1)
         bs = int(getattr(args, "batch_size", self.batch_size)) if args is not None else self.batch_size
         means = self.class_means(t, bs)
         o1, o2 = compute_offsets(t, self.cum_nc_per_task)

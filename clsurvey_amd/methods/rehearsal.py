@@ -5,9 +5,9 @@ Every training batch of task t also carries n_append stored exemplars of the ear
 forward / backward per exemplar chunk of every past task and one for the current batch (:205-247): t + 1 engine passes
 per step at task t.  Here the exemplars are device tensors (the store), and a step of a plan without BatchNorm is
 
-    clhip_rehearsal_assemble      current batch + ring-buffer update + exemplar gather, one launch
-    clhip_net_loss_step_segments  ONE forward / segmented CE / backward over [current batch | exemplar chunks]
-    SGD                           one fused kernel over the parameter arena
+    clhip_rehearsal_assemble           current batch + ring-buffer update + exemplar gather, one launch
+    clhip_net_loss_step_loss_segments  ONE forward / segmented CE / backward over [current batch | exemplar chunks]
+    SGD                                one fused kernel over the parameter arena
 
 with the sample plan (which exemplars, in which chunk order) drawn on the host exactly as the reference draws it and
 copied to the device in one non-blocking copy.  A plan with BatchNorm normalises every chunk with its own batch
@@ -20,19 +20,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, ops
 from .._lib import check
 from ..data import DeviceLoader
-from ..net import NetEngine
 from ..optim import SGD
-from .gem import compute_offsets
-
-
-FUSED_MAX_ROWS, FUSED_MAX_SEGS = 1024, 256        # clhip_softmax_ce_segments' limits (N, CLHIP_CE_MAX_SEGS)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+from .exemplar import ExemplarNet, SharedRowDropout, _stream, compact_blocks, compute_offsets  # noqa: F401
 
 
 def replace_head(model, n_outputs):
@@ -85,11 +77,11 @@ def sample_plan(t, n_append, observed_tasks, n_memories, chunk_size, filled=None
     return counts, out
 
 
-class RehearsalNet:
-    """baseline_rehearsal_{partial,full}_mem.Net.  Picklable like GemNet: the pickle carries the net, the counters and the
-    stored rows of the observed tasks only; engine / workspaces / optimizer are rebuilt on load (init_setup)."""
+class RehearsalNet(SharedRowDropout, ExemplarNet):
+    """baseline_rehearsal_{partial,full}_mem.Net.  The pickle carries the net, the counters and the stored rows of the
+    observed tasks only.  Dropout: GEM's shared mask rows (:97-111), reset at every step."""
 
-    _TRANSIENT = ("engine", "A", "stats", "opt", "dropout_masks", "x_mix", "y_mix", "_acc", "store_x", "store_y", "_draw_mask")
+    _TRANSIENT_EXTRA = ("store_x", "store_y")
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, full_mem_mode=False,
                  batch_size=200, in_shape=(3, 64, 64), device="cuda"):
@@ -97,12 +89,9 @@ class RehearsalNet:
         self.device = torch.device(device)
         self.n_outputs, self.n_tasks = n_outputs, n_tasks
         self.full_mem_mode = bool(full_mem_mode)
-        if self.full_mem_mode:
-            self.n_total_memories = n_memories * n_tasks            # :48-51: one pool, all of it for the first task
-            self.n_memories = self.n_total_memories
-        else:
-            self.n_total_memories = n_memories * n_tasks            # [n_tasks][n_memories] rows
-            self.n_memories = n_memories
+        self.n_total_memories = n_memories * n_tasks                # [n_tasks][n_memories] rows
+        # :48-51: full mode is one pool, all of it for the first task
+        self.n_memories = self.n_total_memories if self.full_mem_mode else n_memories
         self.batch_size = batch_size
         self.in_shape = tuple(in_shape)
         self.cum_nc_per_task = [sum(nc_per_task[:i + 1]) for i in range(len(nc_per_task))]
@@ -111,27 +100,9 @@ class RehearsalNet:
         self.n_append, self.chunk_size = 0, batch_size
         self.force_segmented = False                                 # tests: run the BatchNorm path on any plan
         self.last_path = None                                        # 'fused' | 'segmented' | None (no step yet)
-        self._alloc_store()
+        self._load_rows({})
         self._bind()
         self.init_setup(lr=lr, weight_decay=weight_decay)
-
-    def _alloc_store(self, rows_x=None, rows_y=None):
-        n = self.n_total_memories
-        self.store_x = torch.zeros((n,) + self.in_shape, dtype=torch.float32, device=self.device)
-        self.store_y = torch.zeros((n,), dtype=torch.int64, device=self.device)
-        if rows_x is not None:
-            self.store_x[:rows_x.shape[0]].copy_(rows_x)
-            self.store_y[:rows_y.shape[0]].copy_(rows_y)
-
-    def _bind(self):
-        self.engine = NetEngine(self.net, max(self.batch_size, 1), self.in_shape, self.device)
-        self.engine.auto_dropout = False        # the step's mask rows are the wrapper's own (below), not nn.Dropout's
-        self.dropout_masks = {}
-        self.A = self.engine.arena
-        self.stats = torch.zeros(2, dtype=torch.float64, device=self.device)
-        self.x_mix = torch.empty((self.batch_size,) + self.in_shape, dtype=torch.float32, device=self.device)
-        self.y_mix = torch.empty((self.batch_size,), dtype=torch.int64, device=self.device)
-        self._acc = None
 
     def init_setup(self, args=None, lr=None, weight_decay=None, n_append=None, chunk_size=None):
         """:70-79: fresh SGD(momentum 0.9) at every main() call; the step composition of this call
@@ -147,83 +118,36 @@ class RehearsalNet:
         self.dropout_masks = {}
         self.opt = SGD(self.net.parameters(), lr, momentum=0.9, weight_decay=weight_decay)
 
-    def __getstate__(self):
-        state = {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
-        rows = self._used_rows()
-        state["_rows_x"] = self.store_x[:rows].clone()           # a view would pickle the whole store
-        state["_rows_y"] = self.store_y[:rows].clone()
-        return state
+    def _rows_state(self):
+        rows = (max(self.observed_tasks) + 1) * self.n_memories if self.observed_tasks else 0
+        return {"_rows_x": self.store_x[:rows].clone(), "_rows_y": self.store_y[:rows].clone()}
 
-    def __setstate__(self, state):
-        rows_x, rows_y = state.pop("_rows_x"), state.pop("_rows_y")
-        self.__dict__.update(state)
-        self.device = torch.device(self.device)
-        self.net = self.net.to(self.device)
-        self._alloc_store(rows_x.to(self.device), rows_y.to(self.device))
-        self._bind()
-        self.opt = None
-
-    def _used_rows(self):
-        return (max(self.observed_tasks) + 1) * self.n_memories if self.observed_tasks else 0
+    def _load_rows(self, rows):
+        n = self.n_total_memories
+        self.store_x = torch.zeros((n,) + self.in_shape, dtype=torch.float32, device=self.device)
+        self.store_y = torch.zeros((n,), dtype=torch.int64, device=self.device)
+        if rows:
+            self.store_x[:rows["_rows_x"].shape[0]].copy_(rows["_rows_x"])
+            self.store_y[:rows["_rows_y"].shape[0]].copy_(rows["_rows_y"])
 
     def _row(self, task, slot):
         return task * self.n_memories + slot
 
-    def compute_offsets(self, task_idx, cum_nc_per_task):
-        return compute_offsets(task_idx, cum_nc_per_task)
-
-    def parameters(self):
-        return self.net.parameters()
-
-    def eval(self):
-        return self
-
-    def to(self, device):
-        return self
-
-    # ------------------------------------------------------------------ dropout (:97-111)
-    def reset_dropout_config(self):
-        self.dropout_masks = {}
-
-    def _dropout(self, train, p_retain_unit=0.5):
-        """One Bernoulli(p_retain)/p_retain mask row per Dropout of the plan, drawn (device generator) on the first forward
-        after a reset and shared by every pass of the step; identity in eval mode."""
-        for li in self.engine.drops:
-            if not train:
-                self.engine.set_dropout(li, None)
-                continue
-            if li not in self.dropout_masks:
-                self.dropout_masks[li] = self._draw_mask(li, self.engine.in_elems[li], p_retain_unit)
-            self.engine.set_dropout(li, self.dropout_masks[li])
-
-    def _draw_mask(self, layer, n, p_retain_unit):
-        """:101-104: torch.bernoulli(fill(p_retain)) / p_retain over one sample's features (device generator)."""
-        return torch.full((n,), p_retain_unit, dtype=torch.float32, device=self.device).bernoulli_().div_(p_retain_unit)
+    def _eval_dropout(self, n):
+        self.net.train(False)
+        super()._eval_dropout(n)
 
     # ------------------------------------------------------------------ memory (:140-186)
     def switch_task(self, t):
         """:140-167: new task t; the ring counter restarts; full mode shares the pool out among the observed tasks and
         keeps the first n_per_task rows of every task, compacted in place in ascending task order."""
-        self.observed_tasks.append(t)
-        self.old_task = t
+        self.init_new_task(t)
         self.mem_cnt = 0
         if not self.full_mem_mode:
             return
-        n_old = self.n_memories
         n_new = int(self.n_total_memories / len(self.observed_tasks))
-        for k in range(self.n_tasks):            # destinations k*n_new never overtake the sources k*n_old
-            keep = min(self.filled[k], n_new)
-            src, dst = k * n_old, k * n_new
-            gap = src - dst
-            if keep == 0 or gap == 0:
-                continue
-            s = 0
-            while s < keep:                      # pieces no longer than the gap: no piece overlaps its own source
-                e = min(keep, s + gap)
-                self.store_x[dst + s:dst + e] = self.store_x[src + s:src + e]
-                self.store_y[dst + s:dst + e] = self.store_y[src + s:src + e]
-                s = e
         self.filled = [min(f, n_new) for f in self.filled]
+        compact_blocks((self.store_x, self.store_y), self.n_memories, n_new, self.filled)
         self.n_memories = n_new
 
     def ring_update(self, t, B):
@@ -241,19 +165,6 @@ class RehearsalNet:
     def plan(self, t):
         return sample_plan(t, self.n_append, self.observed_tasks, self.n_memories, self.chunk_size, self.filled)
 
-    def _upload(self, gather, segs):
-        """Gather rows (int32) and the clhip_ce_segment table in ONE pinned host buffer, one non-blocking copy."""
-        host = np.empty(len(gather) + 5 * len(segs), dtype=np.int32)
-        host[:len(gather)] = gather
-        tab = host[len(gather):].reshape(-1, 5)
-        for i, (r0, r1, o, nc, sc) in enumerate(segs):
-            tab[i, :4] = (r0, r1, o, nc)
-            tab[i, 4] = np.array([sc], dtype=np.float32).view(np.int32)[0]
-        pinned = torch.empty(host.shape[0], dtype=torch.int32, pin_memory=True)
-        pinned.numpy()[:] = host
-        dev = pinned.to(self.device, non_blocking=True)     # the caching host allocator keeps `pinned` until the copy ran
-        return dev[:len(gather)], dev[len(gather):]
-
     # ------------------------------------------------------------------ the step (:125-253)
     def observe_FT(self, x, t, y):
         """One rehearsal step: returns device (loss, hits on the current batch)."""
@@ -264,18 +175,16 @@ class RehearsalNet:
         B = int(y.shape[0])
         ring_row0, eff = self.ring_update(t, B)
         _, plan = self.plan(t)
-        segs = [(0, B) + self._slice(t) + (1.0,)]
+        chunks = [(past, ch) for past, _, chs in plan for ch in chs]
+        segs = [(0, B) + self._slice(t) + (1.0, 0)]                 # every segment is of kind 0: cross-entropy
         gather = []
-        for past, _, chunks in plan:
-            for ch in chunks:
-                segs.append((B + len(gather), B + len(gather) + len(ch)) + self._slice(past) + (None,))
-                gather.extend(self._row(past, s) for s in ch)
-        count = len(segs) - 1
-        segs = [s[:4] + ((1.0 / count) if s[4] is None else s[4],) for s in segs]
+        for past, ch in chunks:
+            segs.append((B + len(gather), B + len(gather) + len(ch)) + self._slice(past) + (1.0 / len(chunks), 0))
+            gather.extend(self._row(past, s) for s in ch)
         E, N = len(gather), B + len(gather)
         if N > self.batch_size:
             raise RuntimeError("rehearsal: step of %d rows > engine batch %d" % (N, self.batch_size))
-        gather_dev, segs_dev = self._upload(gather, segs)
+        gather_dev, segs_dev = self._upload(gather, ops.loss_segment_rows(segs))
         row_elems = int(np.prod(self.in_shape))
         check(_lib.lib().clhip_rehearsal_assemble(
             x.data_ptr(), y.data_ptr(), B, row_elems, self.store_x.data_ptr(), self.store_y.data_ptr(), self.store_x.shape[0],
@@ -284,56 +193,19 @@ class RehearsalNet:
         self._dropout(True)
         self.stats.zero_()
         xm, ym = self.x_mix[:N], self.y_mix[:N]
-        # the fused loss takes N <= 1024 rows and CLHIP_CE_MAX_SEGS segments (include/clhip.h); a larger step (a late task
-        # with a big batch, or a chunk size near 1) runs segment by segment instead
-        if self.engine.bns or self.force_segmented or N > FUSED_MAX_ROWS or len(segs) > FUSED_MAX_SEGS:
-            loss = self._segmented(xm, ym, segs)
-            self.last_path = "segmented"
+        if self._fused(N, len(segs)):
+            loss = self.engine.loss_step_segments(xm, ym, segs_dev, len(segs), self.stats)[0].clone()
         else:
-            loss, _ = self.engine.loss_step_segments(xm, ym, segs_dev, len(segs), self.stats)
-            loss = loss.clone()
-            self.last_path = "fused"
+            loss = self._segmented(xm, ym, segs)
         self.opt.step()
         return loss, self.stats[1]
 
-    def _slice(self, task):
-        o1, o2 = compute_offsets(task, self.cum_nc_per_task)
-        return (o1, o2 - o1)
-
     def _segmented(self, xm, ym, segs):
         """The reference's order: every exemplar chunk (tasks ascending), then the current batch; one loss_step per
-        segment with its class slice; gradients accumulated as sum_g scale_g * grad_g (clhip_axpy)."""
-        L = _lib.lib()
-        if self._acc is None:
-            self._acc = torch.empty(self.A.numel, dtype=torch.float32, device=self.device)
-        total = torch.zeros(1, dtype=torch.float32, device=self.device)
-        order = list(range(1, len(segs))) + [0]
-        for k, g in enumerate(order):
-            r0, r1, o, nc, sc = segs[g]
+        segment with its class slice."""
+        def one_pass(g):
+            r0, r1, o, nc, sc, _ = segs[g]
             loss, _ = self.engine.loss_step(xm[r0:r1], ym[r0:r1], "ce_mean", True, self.stats if g == 0 else None,
                                             class_slice=(o, o + nc))
-            total += loss * sc
-            check(L.clhip_axpy(self._acc.data_ptr(), self.A.grad.data_ptr(), self.A.numel, float(sc), int(k == 0), _stream()),
-                  "clhip_axpy")
-        self.A.grad.copy_(self._acc)
-        return total
-
-    # ------------------------------------------------------------------ evaluation
-    def eval_batch(self, x, y, t, stats):
-        """main_rehearsal.py:18-35: CE and hits on the task slice (accumulated into stats on the device)."""
-        self.net.train(False)
-        self._dropout(False)
-        return self.engine.loss_step(x, y, "ce_mean", False, stats, class_slice=compute_offsets(t, self.cum_nc_per_task))[0]
-
-    def __call__(self, x, t, **kw):
-        return self.forward(x, t)
-
-    def forward(self, x, t):
-        """:113-123 (eval): logits with everything outside the task slice at -1e11."""
-        self.net.train(False)
-        self._dropout(False)
-        logits = self.engine.forward(x)
-        o1, o2 = compute_offsets(t, self.cum_nc_per_task)
-        out = torch.full_like(logits, -10e10)
-        out[:, o1:o2] = logits[:, o1:o2]
-        return out
+            return loss, sc
+        return self._accumulate(list(range(1, len(segs))) + [0], one_pass)

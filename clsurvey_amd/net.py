@@ -383,16 +383,18 @@ class NetEngine:
             "clhip_net_loss_step_slice")
         return self.loss, logits
 
-    def loss_step_segments(self, x, y, segs, n_segs, stats=None, backward=True, want_logits=False):
-        """forward + segmented cross-entropy (segs: device clhip_ce_segment[n_segs], csrc/rehearsal.hip) + backward into
-        arena.grad.  Returns (loss[1] device tensor, logits|None); no host synchronisation."""
+    def loss_step_segments(self, x, y, segs, n_segs, stats=None, backward=True, want_logits=False, targets=None, T=1.0):
+        """forward + segmented loss (segs: device clhip_loss_segment[n_segs], csrc/loss.hip; targets [rows >= N, ld_t] for
+        the distillation segments, temperature T) + backward into arena.grad.  Returns (loss[1] device tensor, logits|None);
+        no host synchronisation."""
         self._check_x(x)
         self._mode()
         self._auto_drop(x.shape[0])
         logits = torch.empty((x.shape[0], self.n_classes), dtype=torch.float32, device=self.device) if want_logits else None
-        check(_lib.lib().clhip_net_loss_step_segments(
+        check(_lib.lib().clhip_net_loss_step_loss_segments(
             self._h, self.arena.theta.data_ptr(), self.arena.grad.data_ptr() if backward else None, x.data_ptr(),
-            y.data_ptr(), x.shape[0], segs.data_ptr(), int(n_segs), self.ws.data_ptr(), self.loss.data_ptr(),
+            y.data_ptr(), targets.data_ptr() if targets is not None else None, targets.shape[1] if targets is not None else 0,
+            x.shape[0], segs.data_ptr(), int(n_segs), float(T), self.ws.data_ptr(), self.loss.data_ptr(),
             stats.data_ptr() if stats is not None else None, logits.data_ptr() if logits is not None else None,
-            torch.cuda.current_stream().cuda_stream), "clhip_net_loss_step_segments")
+            torch.cuda.current_stream().cuda_stream), "clhip_net_loss_step_loss_segments")
         return self.loss, logits

@@ -804,46 +804,61 @@ def slice_argmax_count(logits, cols, labels, correct, total, out_of_range):
                                               _ptr(out_of_range), _stream()), "clhip_slice_argmax_count")
 
 
-# ------------------------------------------------------------------ iCaRL
-def icarl_herd(feats, weights, ranges, ks):
-    """clhip_icarl_herd: feats [n_rows, F] fp32, weights [n_rows] fp32 (per-row mean weights), ranges = [(row_begin, row_end)]
-    per class (at most 128 per call), ks the picks per class.  Returns [ranking of class c] as device int32 tensors (row
-    numbers relative to the class's first row)."""
-    _chk(feats, weights)
-    assert feats.dtype == torch.float32 and weights.dtype == torch.float32 and feats.dim() == 2 and weights.numel() == feats.shape[0]
-    offs = [0]
-    for k in ks:
-        offs.append(offs[-1] + int(k))
-    ranking = torch.empty(max(offs[-1], 1), dtype=torch.int32, device=feats.device)
-    tab = (_lib.IcarlClass * len(ranges))()
-    for i, (lo, hi) in enumerate(ranges):
-        tab[i].row_begin, tab[i].row_end, tab[i].k, tab[i].out_off = int(lo), int(hi), int(ks[i]), offs[i]
-    check(_lib.lib().clhip_icarl_herd(_ptr(feats), feats.shape[0], feats.shape[1], _ptr(weights), tab, len(ranges), _ptr(ranking),
-                                      ranking.shape[0], _stream()), "clhip_icarl_herd")
-    return [ranking[offs[i]:offs[i + 1]] for i in range(len(ranges))]
+# ------------------------------------------------------------------ segmented loss of the exemplar methods
+LOSS_MAX_ROWS, LOSS_MAX_SEGS = 1024, 256        # CLHIP_LOSS_MAX_ROWS / CLHIP_LOSS_MAX_SEGS (include/clhip.h)
 
 
-def icarl_segments(segs, device):
-    """Device clhip_icarl_segment table from [(row_begin, row_end, col_off, ncols, scale, kind)]."""
+def loss_segment_rows(segs):
+    """Host clhip_loss_segment table, int32 [n, 6], from [(row_begin, row_end, col_off, ncols, scale, kind)]."""
     import numpy as np
     host = np.zeros((len(segs), 6), dtype=np.int32)
     for i, (r0, r1, o, nc, sc, kind) in enumerate(segs):
         host[i] = (r0, r1, o, nc, np.array([sc], dtype=np.float32).view(np.int32)[0], kind)
-    return torch.from_numpy(host).to(device)
+    return host
 
 
-def icarl_loss_segments(logits, labels, targets, segs, n_segs, T=2.0, stats=None):
-    """clhip_icarl_loss_segments over logits [N, ld]: returns (loss[1], dlogits [N, ld]); targets [N, ld_t] or None."""
-    _chk(logits, labels, targets, segs, stats)
+def loss_segment_table(segs, device):
+    """Device clhip_loss_segment table from [(row_begin, row_end, col_off, ncols, scale, kind)]."""
+    return torch.from_numpy(loss_segment_rows(segs)).to(device)
+
+
+def loss_segments(logits, labels, targets, segs, n_segs, T=2.0, stats=None, dlogits=None, loss=None):
+    """clhip_loss_segments over logits [N, ld]: returns (loss[1], dlogits [N, ld]); targets [N, ld_t] or None."""
+    _chk(logits, labels, targets, segs, stats, dlogits, loss)
     assert logits.dtype == torch.float32 and labels.dtype == torch.int64 and segs.dtype == torch.int32
     N, ld = logits.shape
-    dz = torch.empty_like(logits)
-    loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
-    check(_lib.lib().clhip_icarl_loss_segments(_ptr(logits), _ptr(labels), _ptr(targets) if targets is not None else None,
-                                               targets.shape[1] if targets is not None else 0, N, ld, _ptr(segs), int(n_segs), float(T),
-                                               _ptr(dz), _ptr(loss), _ptr(stats) if stats is not None else None, _stream()),
-          "clhip_icarl_loss_segments")
+    dz = torch.empty_like(logits) if dlogits is None else dlogits
+    if loss is None:
+        loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
+    check(_lib.lib().clhip_loss_segments(_ptr(logits), _ptr(labels), _ptr(targets), targets.shape[1] if targets is not None else 0,
+                                         N, ld, _ptr(segs), int(n_segs), float(T), _ptr(dz), _ptr(loss), _ptr(stats), _stream()),
+          "clhip_loss_segments")
     return loss, dz
+
+
+# ------------------------------------------------------------------ iCaRL
+ICARL_MAX_CLASSES = 128          # CLHIP_ICARL_MAX_CLASSES (include/clhip.h): classes per herding launch
+
+
+def icarl_herd(feats, weights, ranges, ks, flat=False):
+    """clhip_icarl_herd: feats [n_rows, F] fp32, weights [n_rows] fp32 (per-row mean weights), ranges = [(row_begin, row_end)]
+    per class (any number: ICARL_MAX_CLASSES per launch), ks the picks per class.  Returns [ranking of class c]
+    as device int32 tensors (row numbers relative to the class's first row); flat=True: the one ranking tensor (classes back
+    to back) and the int64 offsets of the classes in it.  No synchronisation."""
+    import numpy as np
+    _chk(feats, weights)
+    if feats.dtype != torch.float32 or weights.dtype != torch.float32 or feats.dim() != 2 or weights.numel() != feats.shape[0]:
+        raise RuntimeError("herding needs fp32 HIP tensors: feats [n_rows, F], weights [n_rows]")
+    offs = np.concatenate([[0], np.cumsum(ks)]).astype(np.int64)
+    ranking = torch.empty(max(int(offs[-1]), 1), dtype=torch.int32, device=feats.device)
+    for s in range(0, len(ranges), ICARL_MAX_CLASSES):
+        part = ranges[s:s + ICARL_MAX_CLASSES]
+        tab = (_lib.IcarlClass * len(part))()
+        for i, (lo, hi) in enumerate(part):
+            tab[i].row_begin, tab[i].row_end, tab[i].k, tab[i].out_off = int(lo), int(hi), int(ks[s + i]), int(offs[s + i])
+        check(_lib.lib().clhip_icarl_herd(_ptr(feats), feats.shape[0], feats.shape[1], _ptr(weights), tab, len(part), _ptr(ranking),
+                                          ranking.shape[0], _stream()), "clhip_icarl_herd")
+    return (ranking, offs) if flat else [ranking[int(offs[i]):int(offs[i + 1])] for i in range(len(ranges))]
 
 
 def icarl_nme(feats, means, offset1, nc, n_outputs, n_rows=None):

@@ -481,25 +481,36 @@ int clhip_gem_project_dev(const float* G, size_t ld, const int* row_idx_host, co
  *                         store[gather_rows[e]] -> x_mix[B + e], e < E                the exemplar chunks (:214-234)
  *                       gather_rows (device int32[E]) hold store row indices of PAST tasks (never the ring rows).
  *                       store rows >= store_rows are not read (label -1).  B + ring_rows + E <= 65535.
- *   softmax_ce_segments segs (device, n_segs <= CLHIP_CE_MAX_SEGS) cover rows of logits[N][ld], N <= 1024:
- *                         loss = sum_g scale_g * mean_{i in g} CE_i over row i's class slice [col_off, col_off + ncols)
- *                         dlogits[i] = scale_g / |g| * (softmax - onehot) inside the slice, 0 outside (and 0 for rows of no
- *                         segment); stats[0] += loss, stats[1] += #hits of segment 0 (arg-max, lowest index on ties).
- *                       Segment 0 = the current batch with scale 1, chunk c of `count` chunks has scale 1 / count:
- *                       new_task_loss + sum_c CE_mean(c) / count (:236, :248).  Fixed summation order.  A malformed
- *                       segment or a label outside its slice makes the loss NaN.
- *   net_loss_step_segments  per-layer forward (every layer, no fused tail) + softmax_ce_segments + backward in one call:
- *                       the whole observe_FT step of a plan without BatchNorm.                                          */
-#define CLHIP_CE_MAX_SEGS 256
-typedef struct clhip_ce_segment { int row_begin; int row_end; int col_off; int ncols; float scale; } clhip_ce_segment;
+ *   loss_segments       segs (device, n_segs <= CLHIP_LOSS_MAX_SEGS) cover rows of logits[N][ld], N <= CLHIP_LOSS_MAX_ROWS, each
+ *                       with a class slice [col_off, col_off + ncols), a scale and a kind:
+ *                         kind 0  scale * mean_i CE_i over the slice against labels (relative to the slice)
+ *                         kind 1  scale * T^2 * KLDiv_batchmean(log_softmax(z / T), softmax(target / T)) over the slice,
+ *                                 target = targets[row][ld_t] (same row numbers as logits; targets may be NULL when no
+ *                                 segment is of kind 1); a segment whose OWN value is negative (rounding, icarl.py:584-587)
+ *                                 adds nothing and gets zero gradient, decided on the device.
+ *                       loss = sum of the segments' values; dlogits[i] = its gradient inside the slice (kind 0: scale_g / |g|
+ *                       * (softmax - onehot)), 0 outside and 0 for rows of no segment; stats[0] += loss, stats[1] += #hits
+ *                       of segment 0 (arg-max, lowest index on ties).  Fixed summation order, f64 sums.  A malformed
+ *                       segment or a label outside its slice makes the loss NaN.  A row that lies in several segments
+ *                       (no caller produces one) counts for the first of them only.
+ *                       Rehearsal baselines: every kind 0, segment 0 = the current batch with scale 1, chunk c of `count`
+ *                       chunks with scale 1 / count: new_task_loss + sum_c CE_mean(c) / count (:236, :248).  iCaRL: segment 0
+ *                       the current batch, every distillation chunk of kind 1 (update_representation, icarl.py:482-598).
+ *   net_loss_step_loss_segments  per-layer forward (every layer, no fused tail) + loss_segments + backward in one call: the
+ *                       whole step of a plan without BatchNorm.                                                         */
+#define CLHIP_LOSS_MAX_ROWS 1024
+#define CLHIP_LOSS_MAX_SEGS 256
+typedef struct clhip_loss_segment { int row_begin; int row_end; int col_off; int ncols; float scale; int kind; } clhip_loss_segment;
 int clhip_rehearsal_assemble(const float* x, const int64_t* labels_i64, int B, size_t row_elems, float* store_x,
                              int64_t* store_labels, long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
                              int E, float* x_mix, int64_t* labels_mix, void* stream);
-int clhip_softmax_ce_segments(const float* logits, const int64_t* labels_i64, int N, int ld, const clhip_ce_segment* segs,
-                              int n_segs, float* dlogits, float* loss_out, double* stats, void* stream);
-int clhip_net_loss_step_segments(void* handle, const float* params, float* grads, const float* x, const int64_t* labels_i64,
-                                 int N, const clhip_ce_segment* segs, int n_segs, void* ws, float* loss_out, double* stats,
-                                 float* logits_out, void* stream);
+int clhip_loss_segments(const float* logits, const int64_t* labels_i64, const float* targets, int ld_t, int N, int ld,
+                        const clhip_loss_segment* segs, int n_segs, float T, float* dlogits, float* loss_out, double* stats,
+                        void* stream);
+int clhip_net_loss_step_loss_segments(void* handle, const float* params, float* grads, const float* x,
+                                      const int64_t* labels_i64, const float* targets, int ld_t, int N,
+                                      const clhip_loss_segment* segs, int n_segs, float T, void* ws, float* loss_out,
+                                      double* stats, float* logits_out, void* stream);
 
 /* ------------------------------------------------------------------ Joint baseline
  * methods/method.py:1185-1235: one model trained on all tasks at once, one shared output layer, each task scored on its
@@ -526,8 +537,8 @@ int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols
                              int64_t* correct, int64_t* total, int64_t* out_of_range, void* stream);
 
 /* ------------------------------------------------------------------ iCaRL
- * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471), the loss of update_representation (:482-598) over
- * one mixed batch, and the nearest-mean-of-exemplars classifier of Net.forward (:142-186).
+ * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471) and the nearest-mean-of-exemplars classifier of
+ * Net.forward (:142-186); the loss of update_representation (:482-598) over one mixed batch is clhip_loss_segments above.
  *
  *   icarl_herd          the prioritised exemplar lists of ALL classes of a task in one launch, one workgroup per class,
  *                       over features computed ONCE (the reference recomputes them K (n/B + 1) times per class).
@@ -540,13 +551,6 @@ int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols
  *                       || r - f_i ||, r = (k + 1) mu - S_k (the same quantity times k + 1: no Gram matrix, no expanded
  *                       square), differences in fp32, squares summed in f64; the lowest row wins a tie.
  *                       F <= CLHIP_ICARL_MAX_FEATS (mu, S and r live in LDS).
- *   icarl_loss_segments as softmax_ce_segments (N <= 1024 rows, n_segs <= CLHIP_CE_MAX_SEGS, fixed summation order, hits of
- *                       segment 0 into stats[1], malformed segment or label => NaN loss) with a kind per segment:
- *                         kind 0  scale * mean_i CE_i over the class slice against labels           (the current batch)
- *                         kind 1  scale * T^2 * KLDiv_batchmean(log_softmax(z / T), softmax(target / T)) over the slice,
- *                                 target = targets[row][ld_t] (same row numbers as logits); a segment whose OWN value is
- *                                 negative (rounding, :584-587) adds nothing and gets zero gradient — decided on the device.
- *   net_loss_step_icarl net_loss_step_segments with that loss: forward, icarl_loss_segments, backward in one call.
  *   icarl_nme           out[N][n_outputs] = 0, and 1 at offset1 + argmin_c || means[c] - feats[i] || (c < C, the first
  *                       minimum wins; squares summed in f64, distances compared in fp32).  means == NULL: the task has no
  *                       exemplars yet, out = -10e10 everywhere and 1 / C inside [offset1, offset1 + C) (:146-155).        */
@@ -554,15 +558,8 @@ int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols
 #define CLHIP_ICARL_MAX_FEATS 4096
 #define CLHIP_ICARL_MAX_CLASS_ROWS 65536
 typedef struct clhip_icarl_class { int row_begin; int row_end; int k; int out_off; } clhip_icarl_class;
-typedef struct clhip_icarl_segment { int row_begin; int row_end; int col_off; int ncols; float scale; int kind; } clhip_icarl_segment;
 int clhip_icarl_herd(const float* feats, long n_rows, int F, const float* w, const clhip_icarl_class* classes_host,
                      int n_classes, int* ranking, long ranking_len, void* stream);
-int clhip_icarl_loss_segments(const float* logits, const int64_t* labels_i64, const float* targets, int ld_t, int N, int ld,
-                              const clhip_icarl_segment* segs, int n_segs, float T, float* dlogits, float* loss_out,
-                              double* stats, void* stream);
-int clhip_net_loss_step_icarl(void* handle, const float* params, float* grads, const float* x, const int64_t* labels_i64,
-                              const float* targets, int ld_t, int N, const clhip_icarl_segment* segs, int n_segs, float T,
-                              void* ws, float* loss_out, double* stats, float* logits_out, void* stream);
 int clhip_icarl_nme(const float* feats, const float* means, int N, int F, int C, int offset1, int n_outputs, float* out,
                     void* stream);
 

@@ -118,7 +118,7 @@ def test_loss_segments_match_torch():
     segs = [(0, 9, 8, 4, 1.0, 0), (9, 14, 0, 4, 2.75, 1), (14, 16, 0, 4, 2.75, 1), (16, 23, 4, 4, 0.5, 1)]
     want, gwant = _loss_restatement(z, y, tg, segs)
     stats = torch.zeros(2, dtype=torch.float64, device=DEV)
-    loss, dz = ops.icarl_loss_segments(z.to(DEV), y.to(DEV), tg.to(DEV), ops.icarl_segments(segs, DEV), len(segs), 2.0, stats)
+    loss, dz = ops.loss_segments(z.to(DEV), y.to(DEV), tg.to(DEV), ops.loss_segment_table(segs, DEV), len(segs), 2.0, stats)
     assert abs(float(loss) - want) <= 5e-6 * abs(want)
     assert float((dz.double().cpu() - gwant).abs().max()) <= 1e-6
     hits = int((z[:9, 8:12].argmax(1) == y[:9]).sum())
@@ -134,7 +134,7 @@ def test_loss_segment_with_target_equal_to_logits_adds_nothing():
     y = torch.randint(0, 4, (10,), generator=gen)
     segs = [(0, 4, 0, 4, 1.0, 0), (4, 10, 4, 4, 7.0, 1)]
     only_ce, _ = _loss_restatement(z, y, z, segs[:1])
-    loss, dz = ops.icarl_loss_segments(z.to(DEV), y.to(DEV), z.clone().to(DEV), ops.icarl_segments(segs, DEV), 2)
+    loss, dz = ops.loss_segments(z.to(DEV), y.to(DEV), z.clone().to(DEV), ops.loss_segment_table(segs, DEV), 2)
     assert abs(float(loss) - only_ce) <= 1e-6 * abs(only_ce)
     assert float(dz[4:].abs().max()) <= 1e-7 and float(dz[:4].abs().max()) > 0
 
@@ -147,7 +147,7 @@ def test_negative_distillation_chunk_is_gated_on_the_device():
     candidate must be such a chunk, or this test does not reach the branch and fails); every other chunk has a gradient."""
     from clsurvey_amd import ops
     gen = torch.Generator().manual_seed(6)
-    seg = ops.icarl_segments([(0, 5, 4, 4, 1.0, 1)], DEV)
+    seg = ops.loss_segment_table([(0, 5, 4, 4, 1.0, 1)], DEV)
     y = torch.zeros(5, dtype=torch.int64, device=DEV)
     gated = 0
     for _ in range(64):
@@ -155,7 +155,7 @@ def test_negative_distillation_chunk_is_gated_on_the_device():
         tg = z + 1e-4 * torch.randn((5, 12), generator=gen)
         _, g64 = _loss_restatement(z, None, tg, [(0, 5, 4, 4, 1.0, 1)])
         assert float(g64.abs().max()) > 1e-7                       # q != p
-        loss, dz = ops.icarl_loss_segments(z.to(DEV), y, tg.to(DEV), seg, 1)
+        loss, dz = ops.loss_segments(z.to(DEV), y, tg.to(DEV), seg, 1)
         v = float(loss)
         assert v >= 0.0 and v < 1e-5
         if v == 0.0:
@@ -171,9 +171,9 @@ def test_loss_malformed_segment_is_nan():
     z = torch.randn((6, 12), device=DEV)
     y = torch.zeros(6, dtype=torch.int64, device=DEV)
     for bad in ((0, 7, 0, 4, 1.0, 0), (0, 6, 10, 4, 1.0, 1), (0, 6, 0, 4, 1.0, 2), (3, 3, 0, 4, 1.0, 0)):
-        loss, _ = ops.icarl_loss_segments(z, y, z.clone(), ops.icarl_segments([bad], DEV), 1)
+        loss, _ = ops.loss_segments(z, y, z.clone(), ops.loss_segment_table([bad], DEV), 1)
         assert bool(torch.isnan(loss).all()), bad
-    loss, _ = ops.icarl_loss_segments(z, y, None, ops.icarl_segments([(0, 6, 0, 4, 1.0, 1)], DEV), 1)      # distillation without targets
+    loss, _ = ops.loss_segments(z, y, None, ops.loss_segment_table([(0, 6, 0, 4, 1.0, 1)], DEV), 1)      # distillation without targets
     assert bool(torch.isnan(loss).all())
 
 

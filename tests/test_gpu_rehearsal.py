@@ -24,7 +24,8 @@ def rel_err(a, b):
 
 
 def _segs_dev(segs):
-    host = np.zeros((len(segs), 5), dtype=np.int32)
+    """clhip_loss_segment rows of kind 0 (cross-entropy)."""
+    host = np.zeros((len(segs), 6), dtype=np.int32)
     for i, (r0, r1, o, nc, sc) in enumerate(segs):
         host[i, :4] = (r0, r1, o, nc)
         host[i, 4] = np.array([sc], dtype=np.float32).view(np.int32)[0]
@@ -75,8 +76,8 @@ def test_segmented_ce_matches_f64(N):
         dz = torch.full((N, ld), 7.0, device=DEV)
         loss = torch.zeros(1, device=DEV)
         stats = torch.zeros(2, dtype=torch.float64, device=DEV)
-        assert L.clhip_softmax_ce_segments(z.data_ptr(), y.data_ptr(), N, ld, sd.data_ptr(), len(segs), dz.data_ptr(),
-                                           loss.data_ptr(), stats.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
+        assert L.clhip_loss_segments(z.data_ptr(), y.data_ptr(), None, 0, N, ld, sd.data_ptr(), len(segs), 1.0, dz.data_ptr(),
+                                     loss.data_ptr(), stats.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
         torch.cuda.synchronize()
         outs.append((loss.cpu(), dz.cpu(), stats.cpu()))
     lref, dref, href = _ce_ref(z, y, segs)
@@ -87,6 +88,45 @@ def test_segmented_ce_matches_f64(N):
     assert float((dz.double() - dref).abs().max()) <= 1e-6
     assert int(stats[1]) == href
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
+def test_mixed_table_segments_depend_on_their_own_rows_only():
+    """N = 70, ld = 200: segment 0 of kind 0 (40 rows, 20 classes), a kind-0 chunk of 13 rows over 65 classes and a kind-1
+    chunk of 17 rows over 20 classes (both sides of the 64-class boundary in one table).  Loss, gradient rows and hits of the
+    kind-0 segments are bitwise those of a call that holds only them (same row numbers), the kind-1 rows bitwise those of a
+    call that holds only that segment.  The kind-1 targets are the logits plus a fixed perturbation, so its KL is positive
+    (checked in float64 on the host) and the gate stays open."""
+    from clsurvey_amd import ops
+    gen = torch.Generator().manual_seed(70)
+    N, ld, T = 70, 200, 2.0
+    z = torch.randn(N, ld, generator=gen) * 3
+    tg = z + 0.5 * torch.randn(N, ld, generator=gen)
+    ce, kd = [(0, 40, 180, 20, 1.0, 0), (40, 53, 100, 65, 0.5, 0)], (53, 70, 20, 20, 2.75, 1)
+    y = torch.zeros(N, dtype=torch.int64)
+    for r0, r1, _, nc, _, _ in ce:
+        y[r0:r1] = torch.randint(0, nc, (r1 - r0,), generator=gen)
+    kl = torch.nn.KLDivLoss(reduction="batchmean")(torch.log_softmax(z[53:70, 20:40].double() / T, 1),
+                                                   torch.softmax(tg[53:70, 20:40].double() / T, 1)) * T ** 2
+    assert float(kl) > 1e-3
+    z, tg, y = z.to(DEV), tg.to(DEV), y.to(DEV)
+
+    def run(segs):
+        stats = torch.zeros(2, dtype=torch.float64, device=DEV)
+        loss, dz = ops.loss_segments(z, y, tg, ops.loss_segment_table(segs, DEV), len(segs), T, stats)
+        return loss.cpu(), dz.cpu(), stats.cpu()
+    loss_all, dz_all, st_all = run(ce + [kd])
+    loss_ce, dz_ce, st_ce = run(ce)
+    loss_kd, dz_kd, _ = run([kd])
+    assert torch.equal(dz_all[:53], dz_ce[:53]) and float(dz_ce[:53].abs().max()) > 0
+    assert torch.equal(dz_all[53:], dz_kd[53:]) and float(dz_kd[53:].abs().max()) > 0
+    assert float(dz_ce[53:].abs().max()) == 0 and float(dz_kd[:53].abs().max()) == 0
+    assert torch.equal(st_all[1], st_ce[1]) and int(st_ce[1]) == int((z[:40, 180:].argmax(1) == y[:40]).sum())
+    assert float(loss_kd) > 0
+    # the loss is one f32 rounding of the in-order f64 sum of the segments' values.  With the kind-1 segment at scale 0 its
+    # value is +0.0 and the sum is that of the kind-0 call: bitwise.  At its own scale the three roundings (this loss, the
+    # kind-0 call's, the kind-1 call's; all values positive) are half an ulp of the largest each: 1.5 * 2^-23 relative.
+    assert torch.equal(run(ce + [kd[:4] + (0.0, 1)])[0], loss_ce)
+    assert abs(float(loss_all) - (float(loss_ce) + float(loss_kd))) <= 1.5 * 2 ** -23 * float(loss_all)
 
 
 def test_assemble_is_bitwise():

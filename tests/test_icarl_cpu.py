@@ -227,8 +227,8 @@ def test_new_abi_entries_reject_bad_arguments():
     tab[0].k = 2
     assert L.clhip_icarl_herd(p, 4, 8, p, tab, 1, p, 1, None) == -1            # ranking too short
     assert L.clhip_icarl_herd(p, 4, 5000, p, tab, 1, p, 2, None) == -1         # F over the LDS budget
-    assert L.clhip_icarl_loss_segments(None, None, None, 0, 4, 8, None, 1, 2.0, None, None, None, None) == -1
-    assert L.clhip_icarl_loss_segments(p, p, None, 0, 2000, 8, p, 1, 2.0, p, p, None, None) == -1
-    assert L.clhip_net_loss_step_icarl(None, None, None, None, None, None, 0, 4, None, 1, 2.0, None, None, None, None, None) == -1
+    assert L.clhip_loss_segments(None, None, None, 0, 4, 8, None, 1, 2.0, None, None, None, None) == -1
+    assert L.clhip_loss_segments(p, p, None, 0, 2000, 8, p, 1, 2.0, p, p, None, None) == -1
+    assert L.clhip_net_loss_step_loss_segments(None, None, None, None, None, None, 0, 4, None, 1, 2.0, None, None, None, None, None) == -1
     assert L.clhip_icarl_nme(None, None, 4, 8, 4, 0, 12, None, None) == -1
     assert L.clhip_icarl_nme(None, None, 4, 8, 4, 10, 12, p, None) == -1       # slice outside the head

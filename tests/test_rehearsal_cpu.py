@@ -184,5 +184,5 @@ def test_new_abi_entries_reject_bad_arguments():
     assert L.clhip_rehearsal_assemble(None, None, -1, 16, None, None, 0, 0, 0, None, 0, None, None, None) == -1
     assert L.clhip_rehearsal_assemble(None, None, 2, 16, None, None, 0, 0, 0, None, 0, None, None, None) == -1
     assert L.clhip_rehearsal_assemble(None, None, 0, 0, None, None, 0, 0, 0, None, 0, None, None, None) == -1
-    assert L.clhip_softmax_ce_segments(None, None, 4, 8, None, 1, None, None, None, None) == -1
-    assert L.clhip_net_loss_step_segments(None, None, None, None, None, 4, None, 1, None, None, None, None, None) == -1
+    assert L.clhip_loss_segments(None, None, None, 0, 4, 8, None, 1, 1.0, None, None, None, None) == -1
+    assert L.clhip_net_loss_step_loss_segments(None, None, None, None, None, None, 0, 4, None, 1, 1.0, None, None, None, None, None) == -1

@@ -5,7 +5,7 @@
         torch_us       the same ranking by torch ops on the same device over the same features (one cost vector per pick)
         features_us    the feature pass both share (8000 images through the plan)
   (b) one update_representation step at task 10 (200 current images + 68 exemplars of 9 past tasks, N = 268):
-        fused_us       IcarlNet.observe: assemble + clhip_net_loss_step_icarl + SGD
+        fused_us       IcarlNet.observe: assemble + clhip_net_loss_step_loss_segments + SGD
         segmented_us   the same step, one pass per chunk (the BatchNorm path)
         plain_us       loss_step + SGD over 268 images: the floor
 python tools/icarl_bench.py [--rounds 7] [--iters 20] [--warmup 5] [--out profiles/icarl_bench.json]"""

@@ -1,6 +1,6 @@
 """One rehearsal-baseline step on small_VGG9_cl_128_128 at 64x64 and the task-10 shape (200 current images + 68 exemplars
 of 9 past tasks, N = 268), timed three ways with HIP events:
-  fused      RehearsalNet.observe_FT: clhip_rehearsal_assemble + clhip_net_loss_step_segments + SGD
+  fused      RehearsalNet.observe_FT: clhip_rehearsal_assemble + clhip_net_loss_step_loss_segments + SGD
   segmented  the same step, one loss_step per exemplar chunk + current batch, clhip_axpy accumulation (the BatchNorm path)
   plain      loss_step + SGD over 268 images (no plan, no assembly): the floor the fused step is held against
 python tools/rehearsal_step_bench.py [--iters 50] [--warmup 10] [--out profiles/rehearsal_step.json]"""
