@@ -9,19 +9,104 @@ raw, un-augmented sets (framework/main.py:197-202), so a whole Tiny-ImageNet tas
 for the same global torch RNG state (it consumes the global generator exactly like
 _BaseDataLoaderIter.__init__ + RandomSampler.__iter__ do), so accuracy traces can be compared with
 the reference run under the same seed (utilities/utils.py:52-58).
+
+A split may carry a `RandomCropFlip` spec (the `train` split of a RecogSeq task, the `rnd_transform` file of iNaturalist):
+its stored frames stay static in HBM and the loaders crop and mirror them inside the gather that assembles each batch
+(clhip_gather_tasks_crop_flip), a fresh draw per sample per epoch.
 """
 import torch
 from torch.utils.data import Dataset
 
 
-class TensorTaskDataset(Dataset):
-    """One split of one task. `classes` mirrors ImageFolder_Subset.classes (data/imgfolder.py)."""
+class RandomCropFlip(object):
+    """RandomCrop(size) + RandomHorizontalFlip(p) of stored frames (data/recogseq_dataprep.py:56-57,
+    data/inaturalist_dataprep.py:240-241) as a picklable spec: it holds no image tensor and does nothing by itself, the loaders
+    apply it.  size = (th, tw).  extents: optional host int tensor [n][2], the valid (h, w) of every stored frame — Resize(256)
+    fixes only the shorter side, so real frames differ in size and are stored top-left anchored in a common Hs x Ws frame;
+    None: every frame is full."""
 
-    def __init__(self, x, y, classes):
+    def __init__(self, size, p=0.5, extents=None):
+        th, tw = (int(v) for v in size)
+        if th < 1 or tw < 1 or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("RandomCropFlip: size >= 1 and 0 <= p <= 1, got %s, %s" % (size, p))
+        self.size = (th, tw)
+        self.p = float(p)
+        self.extents = None if extents is None else torch.as_tensor(extents, dtype=torch.int64).cpu().reshape(-1, 2)
+
+    def __repr__(self):
+        return "RandomCropFlip(size=%s, p=%s%s)" % (self.size, self.p, "" if self.extents is None else ", extents=[%d][2]" % len(self.extents))
+
+
+def draw_crop_flip(n, spec, frame_hw, generator, order=None):
+    """int32 [n][3] of (top, left, flip), one row per position of an epoch: top uniform on [0, h - th] and left on [0, w - tw],
+    both inclusive (RandomCrop.get_params), flip = 1 with probability spec.p (RandomHorizontalFlip: rand < p).  (h, w) is
+    frame_hw, or with spec.extents the extent of the sample served at that position: extents[order[k]] (order None: sample k).
+    One torch.rand call for the whole epoch.  Raises if an extent is smaller than spec.size or larger than the frame.
+
+    The reference draws these inside 4-8 DataLoader worker processes seeded base_seed + worker id, and which worker gets which
+    sample depends on scheduling: that stream cannot be reproduced by a batch loader.  The draws here have the same
+    distribution and are a deterministic function of the generator's seed."""
+    th, tw = spec.size
+    Hs, Ws = (int(v) for v in frame_hw)
+    n = int(n)
+    if spec.extents is None:
+        h = torch.full((n,), Hs, dtype=torch.int64)
+        w = torch.full((n,), Ws, dtype=torch.int64)
+    else:
+        ext = spec.extents if order is None else spec.extents.index_select(0, torch.as_tensor(order, dtype=torch.int64))
+        if ext.shape[0] != n:
+            raise ValueError("draw_crop_flip: %d extents for %d positions" % (ext.shape[0], n))
+        h, w = ext[:, 0], ext[:, 1]
+    if n and (int(h.min()) < th or int(w.min()) < tw):
+        raise ValueError("draw_crop_flip: a frame of %d x %d is smaller than the crop %d x %d"
+                         % (int(h.min()), int(w.min()), th, tw))
+    if n and (int(h.max()) > Hs or int(w.max()) > Ws):
+        raise ValueError("draw_crop_flip: an extent exceeds the stored frame %d x %d" % (Hs, Ws))
+    u = torch.rand((n, 3), generator=generator, dtype=torch.float64)
+    top = torch.minimum((u[:, 0] * (h - th + 1)).floor().long(), h - th)
+    left = torch.minimum((u[:, 1] * (w - tw + 1)).floor().long(), w - tw)
+    flip = (u[:, 2] < spec.p).long()
+    return torch.stack([top, left, flip], 1).to(torch.int32).contiguous()
+
+
+def _transform_of(dataset):
+    """The RandomCropFlip a dataset carries, else None (any other `transform` attribute is the dataset's own business)."""
+    t = getattr(dataset, "transform", None)
+    return t if isinstance(t, RandomCropFlip) else None
+
+
+def merged_transform(dsets):
+    """One spec for several tasks served as one dataset: all carry equal size and p (extents concatenated in task order, a task
+    without them counts as full frames), or none carries a transform."""
+    ts = [_transform_of(d) for d in dsets]
+    if all(t is None for t in ts):
+        return None
+    if any(t is None for t in ts) or any((t.size, t.p) != (ts[0].size, ts[0].p) for t in ts):
+        raise ValueError("tasks served as one dataset carry equal RandomCropFlip size and p, or none: %s" % ts)
+    if all(t.extents is None for t in ts):
+        return RandomCropFlip(ts[0].size, ts[0].p)
+    ext = [t.extents if t.extents is not None else torch.tensor(tuple(d.x.shape[-2:])).repeat(len(d), 1) for t, d in zip(ts, dsets)]
+    return RandomCropFlip(ts[0].size, ts[0].p, torch.cat(ext))
+
+
+class TensorTaskDataset(Dataset):
+    """One split of one task. `classes` mirrors ImageFolder_Subset.classes (data/imgfolder.py).  `transform`: None or a
+    RandomCropFlip.  It is applied by the loaders only (DeviceLoader, MultiTaskLoader): `dataset[i]` and `.x` stay the stored
+    frames, so code that reads them directly (the exemplar wrappers: GEM, R-PM / R-FM, iCaRL) sees what it is handed."""
+
+    transform = None          # class-level default: task files pickled before the attribute existed still load
+
+    def __init__(self, x, y, classes, transform=None):
         assert x.shape[0] == y.shape[0]
         self.x = x.contiguous().float()
         self.y = y.contiguous().long()
         self.classes = list(classes)
+        if transform is not None:
+            if not isinstance(transform, RandomCropFlip):
+                raise TypeError("TensorTaskDataset: transform is None or a RandomCropFlip")
+            if transform.extents is not None and len(transform.extents) != len(self):
+                raise ValueError("TensorTaskDataset: %d extents for %d frames" % (len(transform.extents), len(self)))
+            self.transform = transform
 
     def __len__(self):
         return self.x.shape[0]
@@ -53,7 +138,7 @@ def load_task_datasets(dataset_path, device="cuda"):
     out, nbytes = {}, 0
     for split, dset in dsets.items():
         x, y = _extract(dset)
-        out[split] = TensorTaskDataset(x.to(device), y.to(device), getattr(dset, "classes", []))
+        out[split] = TensorTaskDataset(x.to(device), y.to(device), getattr(dset, "classes", []), transform=_transform_of(dset))
         nbytes += x.numel() * 4 + y.numel() * 8
     limit = float(os.environ.get("CLHIP_DATA_CACHE_GB", "64")) * 2 ** 30
     while _TASK_CACHE and _TASK_CACHE_BYTES[0] + nbytes > limit:
@@ -79,7 +164,18 @@ def _extract(dataset):
 
 class DeviceLoader:
     """Iterates (x, y) batches of a dataset held in HBM. Same length / order semantics as
-    torch.utils.data.DataLoader(dataset, batch_size, shuffle, drop_last=False)."""
+    torch.utils.data.DataLoader(dataset, batch_size, shuffle, drop_last=False).
+
+    A dataset that carries a RandomCropFlip is served augmented: the stored frames stay under `.frames`, `.x` is a zero-row
+    tensor of the OUTPUT row shape (C, th, tw) (what callers size their engine from), and every epoch draws one (top, left, flip)
+    per position in serving order from a private CPU generator seeded with the base seed `order()` draws anyway (the
+    _BaseDataLoaderIter draw), shuffle or not.  The global generator is consumed exactly as without a transform, so an augmented
+    loader serves the same sample order as a plain one from the same RNG state.  The table is uploaded once per epoch and
+    sliced per batch: one clhip_gather_tasks_crop_flip launch per batch, no host read.  Differences from the reference: its
+    draws happen in DataLoader worker processes (see draw_crop_flip), and exemplar wrappers keep the one crop they are handed."""
+
+    transform = None
+    base_seed = None
 
     def __init__(self, dataset, batch_size, shuffle, device="cuda"):
         self.dataset = dataset
@@ -90,13 +186,33 @@ class DeviceLoader:
         self.x = x.to(self.device)
         self.y = y.to(self.device)
         self.n = self.x.shape[0]
+        transform = _transform_of(dataset)
+        if transform is not None:
+            self._augment(transform, [self.x], [self.y], [self.n], [0])
+
+    def _augment(self, transform, xs, ys, cum_rows, label_shifts):
+        """Serve `transform` of the frames xs (one tensor per task)."""
+        if xs[0].dim() != 4 or any(tuple(v.shape[1:]) != tuple(xs[0].shape[1:]) for v in xs):
+            raise ValueError("RandomCropFlip needs frames [n, C, Hs, Ws] of one shape")
+        C, Hs, Ws = (int(v) for v in xs[0].shape[1:])
+        th, tw = transform.size
+        if th > Hs or tw > Ws:
+            raise ValueError("RandomCropFlip: crop %d x %d of frames %d x %d" % (th, tw, Hs, Ws))
+        if transform.extents is not None and len(transform.extents) != self.n:
+            raise ValueError("RandomCropFlip: %d extents for %d frames" % (len(transform.extents), self.n))
+        self.transform = transform
+        self.frames = xs
+        self.geometry = (C, Hs, Ws, th, tw)
+        self.x = xs[0].new_empty((0, C, th, tw))    # (row shape only: what engine_for reads; no memory)
+        self._sources = (xs, ys, list(cum_rows), list(label_shifts))
+        self._table = None                          # device table, built at the first epoch (order() alone needs no device)
 
     def __len__(self):
         return (self.n + self.batch_size - 1) // self.batch_size
 
     def order(self):
         # _BaseDataLoaderIter.__init__ draws the worker base seed first ...
-        torch.empty((), dtype=torch.int64).random_()
+        self.base_seed = int(torch.empty((), dtype=torch.int64).random_().item())
         if not self.shuffle:
             return None
         # ... then RandomSampler.__iter__ seeds a private generator from the global one
@@ -105,8 +221,26 @@ class DeviceLoader:
         g.manual_seed(seed)
         return torch.randperm(self.n, generator=g)
 
+    def epoch_params(self, perm):
+        """Host int32 [n][3] table of the epoch whose order() returned `perm` (None: dataset order)."""
+        g = torch.Generator()
+        g.manual_seed(self.base_seed)
+        return draw_crop_flip(self.n, self.transform, self.geometry[1:3], g, order=perm)
+
+    def _augmented(self, perm):
+        from . import ops
+        if self._table is None:
+            self._table = ops.task_table(*self._sources, self.device)
+        params = self.epoch_params(perm).to(self.device)
+        idx = (torch.arange(self.n) if perm is None else perm).to(self.device)
+        for s in range(0, self.n, self.batch_size):
+            yield ops.gather_tasks_crop_flip(self._table, self.geometry, idx[s:s + self.batch_size], params[s:s + self.batch_size])
+
     def __iter__(self):
         perm = self.order()
+        if self.transform is not None:
+            yield from self._augmented(perm)
+            return
         if perm is not None:
             perm = perm.to(self.device)
         for s in range(0, self.n, self.batch_size):
@@ -155,7 +289,8 @@ class TaskList(Dataset):
 class MultiTaskLoader(DeviceLoader):
     """DeviceLoader over a TaskList: same length, order and consumption of the global RNG, but a batch is gathered straight
     out of the per-task tensors (clhip_gather_tasks) — the merged copy `ConcatTasks` makes (a second copy in HBM of every
-    task the cache already holds) is never built."""
+    task the cache already holds) is never built.  Tasks that carry a RandomCropFlip (all of equal size and p, or none) are
+    served augmented as DeviceLoader describes, the crop and flip done in the same gather."""
 
     def __init__(self, dataset, batch_size, shuffle, device="cuda"):
         from . import ops
@@ -170,11 +305,20 @@ class MultiTaskLoader(DeviceLoader):
         assert all(tuple(x.shape[1:]) == self.row_shape for x in xs), "tasks of one sequence share the image shape"
         self.row_elems = int(xs[0][0].numel())
         self.x = xs[0][:0]                      # (row shape only: what engine_for reads; no memory)
+        transform = merged_transform(dataset.datasets)
+        if transform is not None:
+            self._augment(transform, xs, ys, dataset.cumulative_sizes, dataset.label_shifts)
+            return
         self.table = ops.task_table(xs, ys, dataset.cumulative_sizes, dataset.label_shifts, self.device)
 
     def __iter__(self):
         from . import ops
         perm = self.order()
+        if self.transform is not None:
+            if perm is not None and self.n:
+                self.dataset.locate(perm[[int(perm.argmin()), int(perm.argmax())]])               # host check, before any launch
+            yield from self._augmented(perm)
+            return
         if perm is None:
             perm = torch.arange(self.n)
         self.dataset.locate(perm[[int(perm.argmin()), int(perm.argmax())]] if self.n else perm)   # host check, before any launch

@@ -83,6 +83,10 @@ def build_parser():
                    help="command-line runs: tasks,classes,train,val,test,hw[,noise[,kind[,g,amp,noise_lr,q]]] of a synthetic task "
                         "sequence (clsurvey_amd.framework.tasks; kind = protos | blobs, see data.synthetic_task), "
                         "e.g. 10,20,8000,2000,1000,64 = Tiny-ImageNet's shape")
+    p.add_argument("--rnd_margin", type=int, default=0,
+                   help="with --synthetic: images are generated M pixels larger than hw and every training pass (importance "
+                        "passes over reg_sets included) sees a fresh random hw x hw crop + horizontal flip of them, the RecogSeq "
+                        "rule (data/recogseq_dataprep.py:53-60); evaluation reads the centre crops.  0: no augmentation")
     return p
 
 
@@ -747,6 +751,8 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
             train_node_factory = train_node_factory or shard.sharded_grid_factory()
             speculative = not args.no_speculation
             sequential_on_rank0 = args.no_speculation
+    if args.rnd_margin and (dataset is not None or not args.synthetic):
+        raise SystemExit("--rnd_margin belongs to --synthetic: a dataset object says itself which of its files are augmented")
     if dataset is None and args.synthetic:
         from .tasks import SyntheticTaskSequence
         fields = args.synthetic.split(",")
@@ -755,7 +761,8 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         blobs = dict(zip(("g", "amp", "noise_lr", "q"), (float(v) for v in fields[8:12]))) or None
         dataset = SyntheticTaskSequence(os.path.join(args.results_root, "data"), task_count=n_tasks, classes_per_task=n_cls,
                                         sizes=(n_tr, n_va, n_te), hw=hw, noise=float(fields[6]) if len(fields) > 6 else 1.0,
-                                        kind=kind, blobs=blobs, seed=int(fields[12]) if len(fields) > 12 else 7)
+                                        kind=kind, blobs=blobs, seed=int(fields[12]) if len(fields) > 12 else 7,
+                                        rnd_margin=args.rnd_margin, rnd_always=True)
     set_random(7)                                                 # utils.init -> set_random()
     if method is None:
         method = methods.parse(args.method_name)

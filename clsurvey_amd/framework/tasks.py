@@ -13,12 +13,17 @@ from collections import OrderedDict
 
 import torch
 
-from ..data import synthetic_task
+from ..data import RandomCropFlip, TensorTaskDataset, synthetic_task
 
 
 class SyntheticTaskSequence(object):
     def __init__(self, root, task_count=10, classes_per_task=20, sizes=(8000, 2000, 1000), hw=64, seed=7, noise=1.0,
-                 name="synthetic_tiny_imagenet", kind="protos", blobs=None):
+                 name="synthetic_tiny_imagenet", kind="protos", blobs=None, rnd_margin=0, rnd_always=False):
+        """rnd_margin = m > 0: images are generated at (hw + m)^2; task_N.pth.tar holds their centre hw^2 crops (the Resize(256) /
+        CenterCrop(224) of get_transforms(), data/inaturalist_dataprep.py:256-277) and task_N_rndtrans.pth.tar (named after
+        data/dataset.py:108) the same images with the full frames + RandomCropFlip((hw, hw)) as `train` split.  rnd_always: the
+        RecogSeq rule, get_task_dataset_path ignores its rnd_transform argument (data/dataset.py:458-466).  rnd_margin = 0:
+        every byte written and every path returned is what it was before the option existed."""
         self.name = name
         self.argname = name
         self.test_results_dir = name
@@ -35,26 +40,53 @@ class SyntheticTaskSequence(object):
         self.kind = kind
         self.blobs = blobs
         self.n_classes = classes_per_task
+        self.rnd_margin = int(rnd_margin)
+        self.rnd_always = bool(rnd_always)
+        if self.rnd_margin < 0:
+            raise ValueError("SyntheticTaskSequence: rnd_margin >= 0")
 
     def get_taskname(self, task_index):
         return str(task_index)
 
-    def spec(self, task_name):
-        """Everything the bytes of a task file depend on."""
-        return {"sizes": [int(v) for v in self.sizes], "classes": int(self.n_classes), "hw": int(self.hw),
-                "seed": int(self.seed) * 1000 + int(task_name), "noise": float(self.noise), "kind": str(self.kind),
-                "blobs": None if self.blobs is None else {k: float(v) for k, v in sorted(dict(self.blobs).items())}}
+    def spec(self, task_name, rnd_transform=False):
+        """Everything the bytes of a task file depend on (without a margin: the same keys as ever, existing caches stay hits)."""
+        out = {"sizes": [int(v) for v in self.sizes], "classes": int(self.n_classes), "hw": int(self.hw),
+               "seed": int(self.seed) * 1000 + int(task_name), "noise": float(self.noise), "kind": str(self.kind),
+               "blobs": None if self.blobs is None else {k: float(v) for k, v in sorted(dict(self.blobs).items())}}
+        if self.rnd_margin:
+            out["rnd_margin"] = self.rnd_margin
+            if rnd_transform:
+                out["rnd_transform"] = True
+        return out
+
+    def _make(self, task_name, rnd_transform):
+        """The {'train', 'val', 'test'} dict of one file."""
+        want = self.spec(task_name)
+        m = self.rnd_margin
+        d = synthetic_task(self.sizes[0], self.sizes[1], self.sizes[2], self.n_classes, self.hw + m,
+                           seed=want["seed"], noise=self.noise, kind=self.kind, blobs=self.blobs)
+        if not m:
+            return d
+        o = int(round(m / 2.0))                    # torchvision's center_crop offset
+        out = {s: TensorTaskDataset(v.x[:, :, o:o + self.hw, o:o + self.hw], v.y, v.classes) for s, v in d.items()}
+        if rnd_transform:
+            out["train"] = TensorTaskDataset(d["train"].x, d["train"].y, d["train"].classes,
+                                             transform=RandomCropFlip((self.hw, self.hw)))
+        return out
 
     def get_task_dataset_path(self, task_name=None, rnd_transform=False):
         """Task files are cached under root/name/; a sidecar task_N.spec.json records what they were generated from.  A cached
         file of ANOTHER spec (other kind / blobs / noise / sizes / seed under the same results root) is an error, not a hit:
         the results tree beside it holds success tokens and models of that other data.
-        task_name=None asks for a pre-merged file of ALL tasks (Joint.grid_datafetch, method.py:1204): there is none."""
+        task_name=None asks for a pre-merged file of ALL tasks (Joint.grid_datafetch, method.py:1204): there is none.
+        With a margin, rnd_transform (or rnd_always) selects task_N_rndtrans.pth.tar, which has its own sidecar."""
         if task_name is None:
             return None
-        path = os.path.join(self.root, self.name, "task_%s.pth.tar" % task_name)
-        side = os.path.join(self.root, self.name, "task_%s.spec.json" % task_name)
-        want = self.spec(task_name)
+        rnd = bool(self.rnd_margin) and (bool(rnd_transform) or self.rnd_always)
+        stem = "task_%s%s" % (task_name, "_rndtrans" if rnd else "")
+        path = os.path.join(self.root, self.name, stem + ".pth.tar")
+        side = os.path.join(self.root, self.name, stem + ".spec.json")
+        want = self.spec(task_name, rnd)
         if os.path.exists(path) and os.path.exists(side):
             with open(side) as f:
                 have = json.load(f)
@@ -70,8 +102,7 @@ class SyntheticTaskSequence(object):
             if any(os.path.isdir(os.path.join(os.path.dirname(self.root), d)) for d in ("train", "test")):
                 raise RuntimeError("%s has no %s beside it but a results tree exists under %s: cannot tell what data those results "
                                    "were made from — use a fresh --results_root" % (path, os.path.basename(side), os.path.dirname(self.root)))
-        d = synthetic_task(self.sizes[0], self.sizes[1], self.sizes[2], self.n_classes, self.hw,
-                           seed=want["seed"], noise=self.noise, kind=self.kind, blobs=self.blobs)
+        d = self._make(task_name, rnd)
         tmp = "%s.tmp.%d" % (path, os.getpid())    # (torch.save is not atomic: a killed writer must not leave a truncated task file)
         torch.save(d, tmp)
         os.replace(tmp, path)

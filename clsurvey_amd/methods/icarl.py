@@ -240,6 +240,9 @@ class IcarlNet(PerRowDropout, ExemplarNet):
                                % (t, len(self.class_len), o1))
         self._truncate(count)
         train = args.task_imgfolders["train"]
+        if getattr(train, "transform", None) is not None:
+            raise NotImplementedError("icarl: herding ranks the stored images of the task; an augmented split (%r) stores frames "
+                                      "larger than the net's input" % (train.transform,))
         x, y = train.x, train.y
         order = torch.sort(y, stable=True)[1]                                   # classes back to back, dataset order inside
         sizes = torch.bincount(y, minlength=o2 - o1).cpu().tolist()

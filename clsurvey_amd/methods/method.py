@@ -27,7 +27,7 @@ from enum import Enum, auto
 
 import torch
 
-from ..data import DeviceLoader, MultiTaskLoader, TaskList, TensorTaskDataset, load_task_datasets
+from ..data import DeviceLoader, MultiTaskLoader, TaskList, TensorTaskDataset, load_task_datasets, merged_transform
 from . import ebll as _ebll
 from . import ewc as _ewc
 from . import finetune as _ft
@@ -234,7 +234,7 @@ class ConcatTasks(TensorTaskDataset):
     def __init__(self, dsets, classes_len):
         shift = [0] + list(itertools.accumulate(classes_len))[:-1]
         super().__init__(torch.cat([d.x for d in dsets]), torch.cat([d.y + s for d, s in zip(dsets, shift)]),
-                         [c for d in dsets for c in d.classes])
+                         [c for d in dsets for c in d.classes], transform=merged_transform(dsets))
 
 
 def compose_dataset(dataset_path, batch_size, device="cuda"):

@@ -536,6 +536,24 @@ int clhip_gather_tasks(const clhip_task_src* tasks_dev, int T, size_t row_elems,
 int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols, int K, const int64_t* labels_i64,
                              int64_t* correct, int64_t* total, int64_t* out_of_range, void* stream);
 
+/* ------------------------------------------------------------------ training augmentation of the task loaders
+ * data/recogseq_dataprep.py:53-60 (the `train` split of every RecogSeq task: Resize(256) -> RandomCrop(224) ->
+ * RandomHorizontalFlip -> ToTensor -> Normalize) and data/inaturalist_dataprep.py:232-253 (get_rnd_transforms, the file
+ * methods/method.py:1204 asks for): crop and flip of the stored, already normalised Resize(256) frames.  Normalize is a
+ * per-channel affine map and commutes with both, so the result is bitwise what that pipeline yields for the same draws.
+ *
+ *   gather_tasks_crop_flip   clhip_gather_tasks with one (top, left, flip) per batch position: the rows of the task table are
+ *                            frames [C][Hs][Ws], params is device int32[B][3], x_out is [B][C][th][tw] and
+ *                              x_out[b][c][y][x] = frame(idx[b])[c][top_b + y][left_b + (flip_b ? tw - 1 - x : x)]
+ *                            (torchvision's crop, then hflip), labels_out[b] = label + label_shift.  A sample number outside
+ *                            [0, cum_rows[T-1]), top outside [0, Hs - th], left outside [0, Ws - tw] or flip outside {0, 1}
+ *                            copies nothing for that row and writes label -1; no address outside the source frame is formed.
+ *                            Callers draw and check the table on the host.  CLHIP_EINVAL before any launch: the checks of
+ *                            clhip_gather_tasks, C < 1, th or tw < 1, th > Hs, tw > Ws.  B == 0 returns 0.  float4 stores
+ *                            when tw % 4 == 0 and x_out is 16-byte aligned; loads assume dword alignment only (a line starts anywhere). */
+int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const int64_t* idx,
+                                 const int* params, int B, float* x_out, int64_t* labels_out, void* stream);
+
 /* ------------------------------------------------------------------ iCaRL
  * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471) and the nearest-mean-of-exemplars classifier of
  * Net.forward (:142-186); the loss of update_representation (:482-598) over one mixed batch is clhip_loss_segments above.
