@@ -153,6 +153,7 @@ SIGNATURES = {
     "clhip_net_backward": (_i, [_p, _p, _p, _p, _i, _p, _p, _p]),
     "clhip_net_loss_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "clhip_rehearsal_assemble": (_i, [_p, _p, _i, _z, _p, _p, _l, _l, _i, _p, _i, _p, _p, _p]),
+    "clhip_rehearsal_assemble_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
     "clhip_loss_segments": (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _f, _p, _p, _p, _p]),
     "clhip_net_loss_step_loss_segments": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _f, _p, _p, _p, _p, _p]),
     "clhip_gather_tasks": (_i, [_p, _i, _z, _p, _i, _p, _p, _p]),

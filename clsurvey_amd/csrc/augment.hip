@@ -4,27 +4,17 @@
 //   gather_tasks_crop_flip   clhip_gather_tasks (joint.hip) with one (top, left, flip) per batch position:
 //                            x_out[b, c, y, x] = frame(idx[b])[c, top + y, left + (flip ? tw - 1 - x : x)]
 //                            (torchvision's crop, then hflip).  A copy: bitwise.
-#include "common.hpp"
+#include "crop_flip.hpp"
 
 namespace {
 
-constexpr int CF_BLOCK = 256;
-constexpr int CF_BATCH = 4;               // accesses per thread in flight at once (loads first, then the stores)
-constexpr int CF_SEG = 4096;              // output elements per block the host aims at (16 KB, as gather_tasks_kernel)
-
 // blockIdx.y = batch position.  blockIdx.x = (channel, chunk of `rpb` output lines): the block's destination is one contiguous
-// run of nrows * tw floats, its source a nrows x tw window of one channel plane.  Everything that selects the source is
-// block-uniform (scalar loads of idx / params / the table, the division by `chunks` on the scalar unit).  Lanes run along the
-// output line, so loads are coalesced whichever way the line is read; a flip only reverses the lane order inside a line.
-// A thread divides ONCE (its first element -> line, column); after that it steps by the block-uniform (q, rem) = stride / tw.
+// run of nrows * tw floats, its source a nrows x tw window of one channel plane, copied by cf_copy_window (crop_flip.hpp).
+// Everything that selects the source is block-uniform (scalar loads of idx / params / the table, the division by `chunks` on the
+// scalar unit).
 // A sample number outside [0, total), top outside [0, Hs - th], left outside [0, Ws - tw] or flip outside {0, 1} copies nothing
 // and writes label -1: no address outside the source frame is ever formed (the host draws valid tables; this only keeps a bad
 // one from faulting).
-// VEC: tw % 4 == 0 and x_out 16-byte aligned (decided on the host): one float4 store per 4 output columns.  The source line
-// start is arbitrarily aligned (any left, odd Ws), so the loads are written as dwords and promise 4-byte alignment only; read in
-// ascending order and mirrored in registers, the compiler fuses four of them into one 16-byte load, which the hardware takes at
-// dword alignment (measured against per-dword loads in mirrored order: 45.1 vs 48.2 us at 3 x 256^2 -> 224^2, 22.0 vs 21.2 us
-// at 72^2 -> 64^2, batch 200).
 template <bool VEC>
 __global__ __launch_bounds__(CF_BLOCK) void gather_crop_flip_kernel(const clhip_task_src* __restrict__ tasks, int T, int C, int Hs,
                                                                      int Ws, int th, int tw, int rpb, int chunks,
@@ -49,36 +39,7 @@ __global__ __launch_bounds__(CF_BLOCK) void gather_crop_flip_kernel(const clhip_
     typedef const float __attribute__((address_space(1))) gfloat;
     gfloat* src = (gfloat*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws + (size_t)(top + y0) * Ws + left);
     float* dst = x_out + (((size_t)r * C + c) * th + y0) * tw;
-    const unsigned total = (unsigned)nrows * (unsigned)tw;                 // <= max(CF_SEG, tw) < 2^31
-    constexpr int W = VEC ? 4 : 1;                                         // output columns per access
-    const int q = (CF_BLOCK * W) / tw, rem = (CF_BLOCK * W) % tw;
-    int yy = (int)(threadIdx.x * W) / tw;
-    int x = (int)(threadIdx.x * W) - yy * tw;
-    for (unsigned e = threadIdx.x * W; e < total; e += CF_BATCH * CF_BLOCK * W) {
-        float v[CF_BATCH][W];
-#pragma unroll
-        for (int k = 0; k < CF_BATCH; ++k) {                               // all loads in flight before the first store
-            if (e + (unsigned)k * CF_BLOCK * W < total) {
-                gfloat* s = src + (size_t)yy * Ws + (flip ? tw - W - x : x);
-                float a[W];
-#pragma unroll
-                for (int j = 0; j < W; ++j) a[j] = s[j];                   // ascending addresses; mirrored in registers
-#pragma unroll
-                for (int j = 0; j < W; ++j) v[k][j] = flip ? a[W - 1 - j] : a[j];
-            }
-            x += rem;
-            yy += q;
-            if (x >= tw) { x -= tw; ++yy; }
-        }
-#pragma unroll
-        for (int k = 0; k < CF_BATCH; ++k) {
-            const unsigned i = e + (unsigned)k * CF_BLOCK * W;
-            if (i < total) {
-                if constexpr (VEC) *reinterpret_cast<float4*>(dst + i) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
-                else dst[i] = v[k][0];
-            }
-        }
-    }
+    cf_copy_window<VEC>(src, Ws, dst, (unsigned)nrows * (unsigned)tw, tw, flip);      // total <= max(CF_SEG, tw) < 2^31
 }
 
 }  // namespace
@@ -90,7 +51,7 @@ int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, 
     if (!tasks_dev || T < 1 || T > CLHIP_MAX_TASKS || C < 1 || th < 1 || tw < 1 || th > Hs || tw > Ws || B < 0) return CLHIP_EINVAL;
     if (B == 0) return 0;
     if (!idx || !params || !x_out || !labels_out || B > 65535) return CLHIP_EINVAL;
-    const int rpb = tw >= CF_SEG ? 1 : CF_SEG / tw;                         // output lines per block
+    const int rpb = cf_rows_per_block(tw);
     const int chunks = (th + rpb - 1) / rpb;
     if ((size_t)C * chunks > 0x7fffffffull) return CLHIP_EINVAL;
     const dim3 grid((unsigned)(C * chunks), (unsigned)B);

@@ -1,12 +1,43 @@
 // Rehearsal baselines (rehearsal/model/baseline_rehearsal_partial_mem.py:125-253): the step's batch assembly, which (with
 // the segmented loss of loss.hip) lets one engine pass over [current batch | exemplar chunks] replace the reference's one
 // forward / backward per exemplar chunk plus one for the current batch.
-#include "common.hpp"
+//   rehearsal_assemble             the store holds rows of the net's input shape
+//   rehearsal_assemble_crop_flip   the store holds FRAMES (the counterpart of the reference's memory of paths: :215-216 rebuilds
+//                                  the exemplar loader with the task's train transform at every step); the gathered exemplars
+//                                  are cropped and mirrored in the same launch
+#include "crop_flip.hpp"
 
 namespace {
 
 constexpr int ASM_BLOCK = 256;
 constexpr int ASM_VEC_PER_THREAD = 12;    // float4 per thread, all in flight at once: 48 KB per block = one 3x64x64 row
+constexpr size_t ASM_SEG = (size_t)ASM_BLOCK * ASM_VEC_PER_THREAD * 4;       // floats per block
+static_assert(ASM_BLOCK == CF_BLOCK, "the crop rows of rehearsal_assemble_cf_kernel run cf_copy_window");
+
+// Segment `seg` (ASM_SEG floats, the last one shorter) of a row of `elems` floats, src -> dst.
+template <bool VEC>
+__device__ __forceinline__ void copy_segment(const float* src, float* dst, size_t elems, unsigned seg) {
+    if (VEC) {
+        const size_t nvec = elems / 4;
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        float4* d4 = reinterpret_cast<float4*>(dst);
+        const size_t base = (size_t)seg * ASM_BLOCK * ASM_VEC_PER_THREAD + threadIdx.x;
+        float4 v[ASM_VEC_PER_THREAD];
+#pragma unroll
+        for (int k = 0; k < ASM_VEC_PER_THREAD; ++k) {          // all loads in flight before the first store
+            const size_t i = base + (size_t)k * ASM_BLOCK;
+            if (i < nvec) v[k] = s4[i];
+        }
+#pragma unroll
+        for (int k = 0; k < ASM_VEC_PER_THREAD; ++k) {
+            const size_t i = base + (size_t)k * ASM_BLOCK;
+            if (i < nvec) d4[i] = v[k];
+        }
+    } else {
+        const size_t end = min(elems, ((size_t)seg + 1) * ASM_SEG);
+        for (size_t i = (size_t)seg * ASM_SEG + threadIdx.x; i < end; i += ASM_BLOCK) dst[i] = src[i];
+    }
+}
 
 // One block row per destination row (blockIdx.y), blockIdx.x walks the row in 48 KB segments.
 //   rows [0, B)            x[r]                 -> x_mix[r],          y[r]        -> y_mix[r]
@@ -43,27 +74,85 @@ __global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_kernel(
         ysrc = store_y + g;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *ydst = *ysrc;
-    if (VEC) {
-        const size_t nvec = row_elems / 4;
-        const float4* s4 = reinterpret_cast<const float4*>(src);
-        float4* d4 = reinterpret_cast<float4*>(dst);
-        const size_t base = (size_t)blockIdx.x * ASM_BLOCK * ASM_VEC_PER_THREAD + threadIdx.x;
-        float4 v[ASM_VEC_PER_THREAD];
-#pragma unroll
-        for (int k = 0; k < ASM_VEC_PER_THREAD; ++k) {          // all loads in flight before the first store
-            const size_t i = base + (size_t)k * ASM_BLOCK;
-            if (i < nvec) v[k] = s4[i];
+    copy_segment<VEC>(src, dst, row_elems, blockIdx.x);
+}
+
+// The frame-mode assembly: the store rows are frames [C][Hs][Ws], x / x_mix rows are [C][th][tw].  A 1-D grid of three runs of
+// blocks, each row of a run taking the blocks its own role needs (the roles differ in size: a 3 x 256 x 256 frame is 16
+// segments, its 224 x 224 crop 39 windows):
+//   copy_rows x row_blocks     x[r]                       -> x_mix[r],            y[r]       -> y_mix[r]     48 KB segments
+//   ring x frame_blocks        src_frames[src_idx[i]]     -> store[row0 + i],     y[i]       -> store_y[..]  48 KB segments
+//   E x crop_blocks            window of store[gather[e]] -> x_mix[B + e],        store_y[..] -> y_mix[B + e]
+// with the window x_mix[B + e][c][y][x] = store[g][c][top + y][left + (flip ? tw - 1 - x : x)] copied as augment.hip copies it:
+// one block per (channel, chunk of rpb output lines), everything that selects the source block-uniform (scalar loads, the
+// divisions on the scalar unit), lanes along the output line.
+// Nothing outside a frame is addressed: a src_idx outside [0, src_rows) leaves its store row as it is and writes store label
+// -1; a gather row outside [0, store_rows), top outside [0, Hs - th], left outside [0, Ws - tw] or flip outside {0, 1} copies
+// nothing and writes label -1 (the host draws valid tables; this only keeps a bad one from faulting).
+struct assemble_cf_args {
+    const float* x; const int64_t* y; int B, copy_rows;                        // copy_rows = B, or 0 without x_mix
+    int C, Hs, Ws, th, tw;
+    const float* src_frames; long src_rows; const int64_t* src_idx;
+    float* store; int64_t* store_y; long store_rows, row0; int ring;
+    const int* gather; const int* params; int E;
+    float* x_mix; int64_t* y_mix;
+    unsigned row_blocks, frame_blocks, crop_blocks;                            // blocks per row of each run
+    int rpb, chunks;                                                           // crop_blocks = C * chunks, rpb lines each
+    int vec_row, vec_frame;                                                    // 16-byte copies of the two full-row roles
+};
+
+template <bool VEC_CROP>
+__global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const assemble_cf_args a) {
+    unsigned b = blockIdx.x;
+    const size_t row_elems = (size_t)a.C * a.th * a.tw, frame_elems = (size_t)a.C * a.Hs * a.Ws;
+    const unsigned n_row = (unsigned)a.copy_rows * a.row_blocks, n_ring = (unsigned)a.ring * a.frame_blocks;
+    if (b < n_row + n_ring) {
+        const float* src;
+        float* dst;
+        const int64_t* ysrc;
+        int64_t* ydst;
+        size_t elems;
+        unsigned seg;
+        bool vec;
+        if (b < n_row) {
+            const unsigned r = b / a.row_blocks;
+            seg = b - r * a.row_blocks; elems = row_elems; vec = a.vec_row;
+            src = a.x + r * row_elems; dst = a.x_mix + r * row_elems;
+            ysrc = a.y + r; ydst = a.y_mix + r;
+        } else {
+            b -= n_row;
+            const unsigned i = b / a.frame_blocks;
+            seg = b - i * a.frame_blocks; elems = frame_elems; vec = a.vec_frame;
+            const int64_t s = a.src_idx[i];
+            ysrc = a.y + i; ydst = a.store_y + a.row0 + i;
+            if (s < 0 || s >= a.src_rows) {
+                if (seg == 0 && threadIdx.x == 0) *ydst = -1;
+                return;
+            }
+            src = a.src_frames + (size_t)s * frame_elems; dst = a.store + (size_t)(a.row0 + i) * frame_elems;
         }
-#pragma unroll
-        for (int k = 0; k < ASM_VEC_PER_THREAD; ++k) {
-            const size_t i = base + (size_t)k * ASM_BLOCK;
-            if (i < nvec) d4[i] = v[k];
-        }
-    } else {
-        const size_t seg = (size_t)ASM_BLOCK * ASM_VEC_PER_THREAD * 4;
-        const size_t end = min(row_elems, ((size_t)blockIdx.x + 1) * seg);
-        for (size_t i = (size_t)blockIdx.x * seg + threadIdx.x; i < end; i += ASM_BLOCK) dst[i] = src[i];
+        if (seg == 0 && threadIdx.x == 0) *ydst = *ysrc;
+        if (vec) copy_segment<true>(src, dst, elems, seg);
+        else copy_segment<false>(src, dst, elems, seg);
+        return;
     }
+    b -= n_row + n_ring;
+    const unsigned e = b / a.crop_blocks;
+    const int k = (int)(b - e * a.crop_blocks);
+    const long g = a.gather[e];
+    const int top = a.params[3 * e], left = a.params[3 * e + 1], flip = a.params[3 * e + 2];
+    int64_t* ydst = a.y_mix + a.B + e;
+    if (g < 0 || g >= a.store_rows || top < 0 || top > a.Hs - a.th || left < 0 || left > a.Ws - a.tw || (flip != 0 && flip != 1)) {
+        if (k == 0 && threadIdx.x == 0) *ydst = -1;
+        return;
+    }
+    if (k == 0 && threadIdx.x == 0) *ydst = a.store_y[g];
+    const int c = k / a.chunks;
+    const int y0 = (k - c * a.chunks) * a.rpb;
+    const int nrows = min(a.rpb, a.th - y0);
+    const float* src = a.store + ((size_t)g * a.C + c) * a.Hs * a.Ws + (size_t)(top + y0) * a.Ws + left;
+    float* dst = a.x_mix + (((size_t)(a.B + e) * a.C + c) * a.th + y0) * a.tw;
+    cf_copy_window<VEC_CROP>(src, a.Ws, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip);   // total <= max(CF_SEG, tw) < 2^31
 }
 
 }  // namespace
@@ -84,14 +173,57 @@ int clhip_rehearsal_assemble(const float* x, const int64_t* labels_i64, int B, s
     if (rows == 0) return 0;
     if (rows > 65535) return CLHIP_EINVAL;
     const bool vec = row_elems % 4 == 0 && (!x || aligned16(x)) && (!x_mix || aligned16(x_mix)) && (!store_x || aligned16(store_x));
-    const size_t seg = (size_t)ASM_BLOCK * ASM_VEC_PER_THREAD * 4;
-    dim3 grid((unsigned)((row_elems + seg - 1) / seg), (unsigned)rows);
+    dim3 grid((unsigned)((row_elems + ASM_SEG - 1) / ASM_SEG), (unsigned)rows);
     if (vec)
         hipLaunchKernelGGL(rehearsal_assemble_kernel<true>, grid, dim3(ASM_BLOCK), 0, as_stream(stream), x, labels_i64, B, row_elems,
                            store_x, store_labels, store_rows, ring_row0, ring_rows, gather_rows, E, x_mix, labels_mix);
     else
         hipLaunchKernelGGL(rehearsal_assemble_kernel<false>, grid, dim3(ASM_BLOCK), 0, as_stream(stream), x, labels_i64, B, row_elems,
                            store_x, store_labels, store_rows, ring_row0, ring_rows, gather_rows, E, x_mix, labels_mix);
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+int clhip_rehearsal_assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                       const float* src_frames, long src_rows, const int64_t* src_idx, float* store_frames,
+                                       int64_t* store_labels, long store_rows, long ring_row0, int ring_rows,
+                                       const int* gather_rows, const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
+                                       void* stream) {
+    if (B < 0 || E < 0 || ring_rows < 0 || store_rows < 0 || src_rows < 0) return CLHIP_EINVAL;
+    if (C < 1 || th < 1 || tw < 1 || th > Hs || tw > Ws) return CLHIP_EINVAL;
+    if (ring_rows > B) return CLHIP_EINVAL;                                      // ring rows are a prefix of the batch
+    if (E > 0 && (!x_mix || !gather_rows || !gather_params)) return CLHIP_EINVAL;
+    const int copy_rows = x_mix ? B : 0;                                         // no x_mix (E == 0): the ring update alone
+    if (copy_rows > 0 && !x) return CLHIP_EINVAL;
+    if ((copy_rows > 0 || ring_rows > 0) && !labels_i64) return CLHIP_EINVAL;
+    if ((copy_rows > 0 || E > 0) && !labels_mix) return CLHIP_EINVAL;
+    if (ring_rows > 0 && (!src_frames || !src_idx)) return CLHIP_EINVAL;
+    if ((ring_rows > 0 || E > 0) && (!store_frames || !store_labels)) return CLHIP_EINVAL;
+    if (ring_rows > 0 && (ring_row0 < 0 || ring_row0 + ring_rows > store_rows)) return CLHIP_EINVAL;
+    const long rows = (long)copy_rows + ring_rows + E;
+    if (rows == 0) return 0;
+    if (rows > 65535) return CLHIP_EINVAL;
+    const size_t row_elems = (size_t)C * th * tw, frame_elems = (size_t)C * Hs * Ws;
+    assemble_cf_args a;
+    a.x = x; a.y = labels_i64; a.B = B; a.copy_rows = copy_rows;
+    a.C = C; a.Hs = Hs; a.Ws = Ws; a.th = th; a.tw = tw;
+    a.src_frames = src_frames; a.src_rows = src_rows; a.src_idx = src_idx;
+    a.store = store_frames; a.store_y = store_labels; a.store_rows = store_rows; a.row0 = ring_row0; a.ring = ring_rows;
+    a.gather = gather_rows; a.params = gather_params; a.E = E;
+    a.x_mix = x_mix; a.y_mix = labels_mix;
+    a.rpb = cf_rows_per_block(tw);
+    a.chunks = (th + a.rpb - 1) / a.rpb;
+    const size_t row_blocks = (row_elems + ASM_SEG - 1) / ASM_SEG, frame_blocks = (frame_elems + ASM_SEG - 1) / ASM_SEG;
+    const size_t crop_blocks = (size_t)C * a.chunks;
+    const size_t blocks = copy_rows * row_blocks + ring_rows * frame_blocks + E * crop_blocks;
+    if (row_blocks > 0xffffu || frame_blocks > 0xffffu || crop_blocks > 0xffffu || blocks > 0x7fffffffull) return CLHIP_EINVAL;
+    a.row_blocks = (unsigned)row_blocks; a.frame_blocks = (unsigned)frame_blocks; a.crop_blocks = (unsigned)crop_blocks;
+    a.vec_row = row_elems % 4 == 0 && aligned16(x) && aligned16(x_mix);
+    a.vec_frame = frame_elems % 4 == 0 && aligned16(src_frames) && aligned16(store_frames);
+    if (tw % 4 == 0 && aligned16(x_mix))
+        hipLaunchKernelGGL(rehearsal_assemble_cf_kernel<true>, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(rehearsal_assemble_cf_kernel<false>, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
     CLHIP_LAUNCH_CHECK();
     return 0;
 }

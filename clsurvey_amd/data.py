@@ -92,7 +92,7 @@ def merged_transform(dsets):
 class TensorTaskDataset(Dataset):
     """One split of one task. `classes` mirrors ImageFolder_Subset.classes (data/imgfolder.py).  `transform`: None or a
     RandomCropFlip.  It is applied by the loaders only (DeviceLoader, MultiTaskLoader): `dataset[i]` and `.x` stay the stored
-    frames, so code that reads them directly (the exemplar wrappers: GEM, R-PM / R-FM, iCaRL) sees what it is handed."""
+    frames, so code that reads them directly sees what it is handed."""
 
     transform = None          # class-level default: task files pickled before the attribute existed still load
 
@@ -171,11 +171,14 @@ class DeviceLoader:
     per position in serving order from a private CPU generator seeded with the base seed `order()` draws anyway (the
     _BaseDataLoaderIter draw), shuffle or not.  The global generator is consumed exactly as without a transform, so an augmented
     loader serves the same sample order as a plain one from the same RNG state.  The table is uploaded once per epoch and
-    sliced per batch: one clhip_gather_tasks_crop_flip launch per batch, no host read.  Differences from the reference: its
-    draws happen in DataLoader worker processes (see draw_crop_flip), and exemplar wrappers keep the one crop they are handed."""
+    sliced per batch: one clhip_gather_tasks_crop_flip launch per batch, no host read.  While iterating, `last_idx` (device
+    int64) and `last_idx_host` hold the sample numbers of the batch just served: with `frames` they are what an exemplar wrapper
+    in frame mode stores instead of the crop (methods/exemplar.py: the counterpart of the reference's `paths`).  Difference from
+    the reference: its draws happen in DataLoader worker processes (see draw_crop_flip)."""
 
     transform = None
     base_seed = None
+    last_idx = last_idx_host = None
 
     def __init__(self, dataset, batch_size, shuffle, device="cuda"):
         self.dataset = dataset
@@ -232,8 +235,10 @@ class DeviceLoader:
         if self._table is None:
             self._table = ops.task_table(*self._sources, self.device)
         params = self.epoch_params(perm).to(self.device)
-        idx = (torch.arange(self.n) if perm is None else perm).to(self.device)
+        idx_host = torch.arange(self.n) if perm is None else perm
+        idx = idx_host.to(self.device)
         for s in range(0, self.n, self.batch_size):
+            self.last_idx, self.last_idx_host = idx[s:s + self.batch_size], idx_host[s:s + self.batch_size]
             yield ops.gather_tasks_crop_flip(self._table, self.geometry, idx[s:s + self.batch_size], params[s:s + self.batch_size])
 
     def __iter__(self):

@@ -5,12 +5,21 @@ for a plan with BatchNorm or a step over the loss kernel's limits, segment by se
 
 A method derives from ExemplarNet and one of the two dropout policies and keeps what is its own: the store layout, the
 host draws, the memory management and the composition of its step.
+
+Frame mode (GEM, R-PM / R-FM): the reference's memories hold image PATHS, and every replay rebuilds the exemplar loader with
+the current task's train transform (gem.py:233-234, baseline_rehearsal_partial_mem.py:215-216, common.py:57-72), so an
+exemplar is cropped and mirrored afresh at every draw.  A wrapper built with a RandomCropFlip spec does the same: its store
+holds the loader's FRAMES (copied by sample number: BatchSource, the counterpart of the reference's `paths`), `store_ext`-style
+host tables hold each stored frame's valid (h, w), and the crop happens when the exemplars are replayed.
 """
+import collections
+
 import numpy as np
 import torch
 
 from .. import _lib, ops
 from .._lib import check
+from ..data import RandomCropFlip, draw_crop_flip
 from ..net import NetEngine
 
 FUSED_MAX_ROWS, FUSED_MAX_SEGS = ops.LOSS_MAX_ROWS, ops.LOSS_MAX_SEGS        # the fused loss's limits (include/clhip.h)
@@ -24,6 +33,21 @@ def compute_offsets(task_idx, cum_nc_per_task):
     """rehearsal/model/common.py:106-118."""
     o1 = 0 if task_idx == 0 else int(cum_nc_per_task[task_idx - 1])
     return o1, int(cum_nc_per_task[task_idx])
+
+
+# Where a batch of an augmented loader came from: the loader's frame tensor, the sample numbers it just gathered (device and
+# host) and the valid (h, w) of the loader's frames (host int64 [n][2], None: every frame is full).
+BatchSource = collections.namedtuple("BatchSource", ["frames", "idx", "idx_host", "extents"])
+
+
+def batch_source(loader):
+    """The BatchSource of the batch `loader` served last; None for a loader without a transform."""
+    spec = getattr(loader, "transform", None)
+    if spec is None:
+        return None
+    if len(loader.frames) != 1:
+        raise ValueError("exemplar frames are copied out of ONE frame tensor (a DeviceLoader over one task)")
+    return BatchSource(loader.frames[0], loader.last_idx, loader.last_idx_host, spec.extents)
 
 
 def compact_blocks(tensors, old_stride, new_stride, keep_per_block):
@@ -107,6 +131,65 @@ class ExemplarNet:
     _TRANSIENT = ("engine", "A", "stats", "opt", "x_mix", "y_mix", "_acc")
     _TRANSIENT_POLICY = ()          # the dropout policy's state
     _TRANSIENT_EXTRA = ()           # the subclass's own device state
+    _HOST_ROWS = ("_rows_ext",)     # rows of _rows_state() that stay on the host
+
+    # class-level defaults: a wrapper pickled before frame mode existed loads in crop mode
+    exemplar_transform = None       # RandomCropFlip(size, p) of the replayed exemplars, or None: the store holds crops
+    frame_shape = None              # (C, Hs, Ws) of the stored frames
+
+    def _init_frames(self, exemplar_transform, frame_shape):
+        """Frame mode on (a spec and the frame shape) or off (both None).  in_shape stays the crop shape."""
+        if exemplar_transform is None:
+            if frame_shape is not None and tuple(frame_shape) != tuple(self.in_shape):
+                raise ValueError("exemplar wrapper: a frame shape needs an exemplar_transform")
+            return
+        if not isinstance(exemplar_transform, RandomCropFlip) or frame_shape is None:
+            raise TypeError("exemplar wrapper: exemplar_transform is a RandomCropFlip and comes with the frame shape (C, Hs, Ws)")
+        C, Hs, Ws = (int(v) for v in frame_shape)
+        if (C,) + exemplar_transform.size != tuple(self.in_shape) or Hs < self.in_shape[1] or Ws < self.in_shape[2]:
+            raise ValueError("exemplar wrapper: frames %s, crop %s, net input %s" % (tuple(frame_shape), exemplar_transform.size,
+                                                                                 self.in_shape))
+        self.exemplar_transform = RandomCropFlip(exemplar_transform.size, exemplar_transform.p)     # (the extents are a task's)
+        self.frame_shape = (C, Hs, Ws)
+
+    @property
+    def store_shape(self):
+        """Row shape of the exemplar store."""
+        return self.in_shape if self.exemplar_transform is None else self.frame_shape
+
+    @property
+    def geometry(self):
+        return self.frame_shape + self.exemplar_transform.size
+
+    def _full_ext(self, rows):
+        """Host int64 [rows][2]: every frame full."""
+        return torch.tensor(self.frame_shape[1:], dtype=torch.int64).repeat(rows, 1)
+
+    def _check_source(self, source):
+        """A frame-mode wrapper takes batches with their BatchSource, a crop-mode one without."""
+        if self.exemplar_transform is None:
+            if source is not None:
+                raise ValueError("exemplar wrapper in crop mode handed a batch with its frames (build it with exemplar_transform)")
+            return
+        if source is None:
+            raise ValueError("exemplar wrapper in frame mode handed a plain batch: it stores frames by sample number "
+                             "(pass batch_source(loader))")
+        if tuple(source.frames.shape[1:]) != self.frame_shape:
+            raise ValueError("exemplar wrapper: frames %s, store %s" % (tuple(source.frames.shape[1:]), self.frame_shape))
+
+    def _source_ext(self, source, n):
+        """Host int64 [n][2]: the valid (h, w) of the first n samples of the batch."""
+        if source.extents is None:
+            return self._full_ext(n)
+        return source.extents.index_select(0, source.idx_host[:n])
+
+    def draw_exemplar_params(self, ext, seed):
+        """Host int32 [n][3] of (top, left, flip) for exemplars whose frames have the valid sizes ext [n][2], in that order, from
+        a private CPU generator: the global one is not touched (DeviceLoader's rule for its epoch table)."""
+        g = torch.Generator()
+        g.manual_seed(seed)
+        spec = RandomCropFlip(self.exemplar_transform.size, self.exemplar_transform.p, ext)
+        return draw_crop_flip(ext.shape[0], spec, self.frame_shape[1:], g)
 
     def _bind(self, mix=True):
         """Engine and work buffers; mix: the [current batch | exemplar chunks] rows of a step."""
@@ -138,7 +221,7 @@ class ExemplarNet:
         self.__dict__.update(state)
         self.device = torch.device(self.device)
         self.net = self.net.to(self.device)
-        self._load_rows({k: v.to(self.device) for k, v in rows.items()})
+        self._load_rows({k: v if k in self._HOST_ROWS else v.to(self.device) for k, v in rows.items()})
         self._bind()
         self.opt = None
 
@@ -163,15 +246,21 @@ class ExemplarNet:
         self.old_task = t
 
     # ------------------------------------------------------------------ the step over [current batch | exemplar chunks]
-    def _upload(self, gather, rows):
-        """Gather rows (int32) and rows of int32 columns (clhip_loss_segment tables: ops.loss_segment_rows) in ONE pinned
-        host buffer, one non-blocking copy.  Returns the two device parts, the second one flat."""
-        pinned = torch.empty(len(gather) + rows.size, dtype=torch.int32, pin_memory=True)
+    def _upload(self, gather, rows, params=None):
+        """Gather rows (int32), rows of int32 columns (clhip_loss_segment tables: ops.loss_segment_rows) and, in frame mode, the
+        exemplars' (top, left, flip) rows (int32 [len(gather)][3]) in ONE pinned host buffer, one non-blocking copy.  Returns
+        the device parts, the second one flat; the third one only when params is given."""
+        n, m = len(gather), rows.size
+        pinned = torch.empty(n + m + (0 if params is None else 3 * n), dtype=torch.int32, pin_memory=True)
         host = pinned.numpy()
-        host[:len(gather)] = gather
-        host[len(gather):] = rows.reshape(-1)
+        host[:n] = gather
+        host[n:n + m] = rows.reshape(-1)
+        if params is not None:
+            host[n + m:] = params.numpy().reshape(-1)
         dev = pinned.to(self.device, non_blocking=True)     # the caching host allocator keeps `pinned` until the copy ran
-        return dev[:len(gather)], dev[len(gather):]
+        if params is None:
+            return dev[:n], dev[n:]
+        return dev[:n], dev[n:n + m], dev[n + m:].view(n, 3)
 
     def _fused(self, N, n_segs):
         """One fused pass, or segment by segment: a plan with BatchNorm normalises every chunk with its own statistics, and

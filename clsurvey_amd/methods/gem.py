@@ -6,6 +6,10 @@ training batch (gem.py:233-235); here memory[t] is a device tensor and a past-ta
 ceil(n_memories / batch) engine calls.  Gradients of a task are one contiguous row of G (the
 ParamArena gradient is flat), the QP inputs come from ONE Gram-matrix pass and the tiny QP (quadprog's Goldfarb-Idnani)
 runs on the device in float64 (clhip_gem_qp) — no host round trip per batch.
+
+Frame mode (exemplar.py): memory[t] holds the loader's frames, fill_buffer copies them by sample number (the ring-only form of
+clhip_rehearsal_assemble_crop_flip), and a past-task pass serves memory[t] through the augmented DeviceLoader, a fresh crop
+and flip per exemplar per pass as gem.py:233-234 rebuilds its ImagePathlist with the train transform.
 """
 import copy
 import ctypes as C
@@ -13,11 +17,11 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, ops
 from .._lib import check
-from ..data import DeviceLoader, TensorTaskDataset
+from ..data import DeviceLoader, RandomCropFlip, TensorTaskDataset
 from ..optim import SGD
-from .exemplar import ExemplarNet, SharedRowDropout, _stream, compute_offsets  # noqa: F401  (compute_offsets: imported from here)
+from .exemplar import ExemplarNet, SharedRowDropout, _stream, batch_source, compute_offsets  # noqa: F401  (compute_offsets: imported from here)
 
 
 def extend_head(model, n_outputs):
@@ -39,14 +43,17 @@ class GemNet(SharedRowDropout, ExemplarNet):
     _TRANSIENT_EXTRA = ("G", "_gram_ws", "_gram", "_v", "_info", "_qp_bad", "host_qp")
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, memory_strength=1.0,
-                 batch_size=200, in_shape=(3, 64, 64), device="cuda"):
+                 batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None):
         self.net = model.to(device)
         self.device = torch.device(device)
         self.n_outputs, self.n_tasks, self.n_memories = n_outputs, n_tasks, n_memories
         self.batch_size = batch_size
         self.in_shape = tuple(in_shape)
-        self.memory_x = torch.zeros((n_tasks, n_memories) + self.in_shape, dtype=torch.float32, device=self.device)
+        self._init_frames(exemplar_transform, frame_shape)
+        self.memory_x = torch.zeros((n_tasks, n_memories) + self.store_shape, dtype=torch.float32, device=self.device)
         self.memory_labels = torch.zeros((n_tasks, n_memories), dtype=torch.int64, device=self.device)
+        if self.exemplar_transform is not None:                     # host: valid (h, w) of every stored frame
+            self.memory_ext = self._full_ext(n_tasks * n_memories).view(n_tasks, n_memories, 2)
         self.cum_nc_per_task = [sum(nc_per_task[:i + 1]) for i in range(len(nc_per_task))]
         self.observed_tasks, self.old_task, self.mem_cnt = [], -1, 0
         self._bind()
@@ -72,13 +79,21 @@ class GemNet(SharedRowDropout, ExemplarNet):
         self.margin = memory_strength
 
     # ------------------------------------------------------------------ memory
-    def fill_buffer(self, t, x, y):
-        """gem.py:322-345 (ring buffer; exemplar tensors instead of paths)."""
+    def fill_buffer(self, t, x, y, source=None):
+        """gem.py:322-345 (ring buffer; exemplar tensors instead of paths).  Frame mode: the frames of the batch's first eff
+        samples (source: its BatchSource), one launch."""
+        self._check_source(source)
         bsz = y.shape[0]
         endcnt = min(self.mem_cnt + bsz, self.n_memories)
         eff = endcnt - self.mem_cnt
-        self.memory_x[t, self.mem_cnt:endcnt] = x[:eff]
-        self.memory_labels[t, self.mem_cnt:endcnt] = y[:eff]
+        if self.exemplar_transform is not None:
+            ops.rehearsal_assemble_crop_flip(self.geometry, None, y, bsz, source.frames, source.idx,
+                                             self.memory_x.view((-1,) + self.frame_shape), self.memory_labels.view(-1),
+                                             t * self.n_memories + self.mem_cnt, eff, None, None, None, None)
+            self.memory_ext[t, self.mem_cnt:endcnt] = self._source_ext(source, eff)
+        else:
+            self.memory_x[t, self.mem_cnt:endcnt] = x[:eff]
+            self.memory_labels[t, self.mem_cnt:endcnt] = y[:eff]
         self.mem_cnt += eff
         if self.mem_cnt == self.n_memories:
             self.mem_cnt = 0
@@ -90,9 +105,17 @@ class GemNet(SharedRowDropout, ExemplarNet):
         for x, y in loader:
             if t != self.old_task:
                 self.init_new_task(t)
-            if self.fill_buffer(t, x, y):
+            if self.fill_buffer(t, x, y, batch_source(loader) if self.exemplar_transform is not None else None):
                 return True
         return False
+
+    def _memory_loader(self, past):
+        """The shuffled loader of one past task's memory pass; frame mode: augmented with the stored frames' own extents."""
+        mem = TensorTaskDataset.__new__(TensorTaskDataset)
+        mem.x, mem.y, mem.classes = self.memory_x[past], self.memory_labels[past], []
+        if self.exemplar_transform is not None:
+            mem.transform = RandomCropFlip(self.exemplar_transform.size, self.exemplar_transform.p, self.memory_ext[past])
+        return DeviceLoader(mem, self.batch_size, True, self.device)
 
     # ------------------------------------------------------------------ kernels
     def _axpy(self, row, assign):
@@ -138,20 +161,18 @@ class GemNet(SharedRowDropout, ExemplarNet):
                                            self.A.grad.data_ptr(), self.A.numel, _stream()), "clhip_gem_project")
 
     # ------------------------------------------------------------------ gem.py:206-287
-    def observe(self, x, t, y):
+    def observe(self, x, t, y, source=None):
         batch_stats = {"projected_grads": [0]}
         if t != self.old_task:
             self.init_new_task(t)
-        self.fill_buffer(t, x, y)
+        self.fill_buffer(t, x, y, source)
         self.reset_dropout_config()                                   # gem.py:214-215: net.train(); fresh masks per observe
         self._dropout(True)
         if len(self.observed_tasks) > 1:
             for past in self.observed_tasks[:-1]:
                 sl = compute_offsets(past, self.cum_nc_per_task)
-                mem = TensorTaskDataset.__new__(TensorTaskDataset)
-                mem.x, mem.y, mem.classes = self.memory_x[past], self.memory_labels[past], []
                 first = True
-                for xb, yb in DeviceLoader(mem, self.batch_size, True, self.device):
+                for xb, yb in self._memory_loader(past):
                     self.engine.loss_step(xb.contiguous(), yb.contiguous(), "ce_mean", True, class_slice=sl)
                     self._axpy(self.G[past], assign=first)          # grads accumulate over batches (:237-256)
                     first = False
@@ -175,8 +196,9 @@ class GemNet(SharedRowDropout, ExemplarNet):
         self.opt.step()
         return loss, self.stats[1], batch_stats
 
-    def observe_FT(self, x, t, y):
+    def observe_FT(self, x, t, y, source=None):
         """gem.py:289-309: plain SGD step on the task's output slice (phase-1 grid; no memory)."""
+        self._check_source(source)
         sl = compute_offsets(t, self.cum_nc_per_task)
         self.stats.zero_()
         self._dropout(True)       # no reset here: the masks drawn after init_setup stay for the whole run, as in the reference

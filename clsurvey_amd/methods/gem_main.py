@@ -18,6 +18,7 @@ import torch
 from ..data import load_task_datasets
 
 from ..data import DeviceLoader
+from .exemplar import batch_source
 from . import gem as G
 from . import rehearsal as R
 from .train_common import set_lr
@@ -60,12 +61,16 @@ def train_model(model, args, dset_sizes, resume="", save_models_mode=False, savi
             running_corrects = torch.zeros((), dtype=torch.float64, device=model.device)
             projected = []
             val_stats.zero_()
-            for inputs, labels in args.dset_loaders[phase]:
+            loader = args.dset_loaders[phase]
+            frame_mode = getattr(model, "exemplar_transform", None) is not None
+            for inputs, labels in loader:
                 if phase == "train":
+                    # frame mode: the batch goes with its frames and sample numbers (the reference's `paths`)
+                    src = {"source": batch_source(loader)} if frame_mode else {}
                     if args.finetune:
-                        loss, correct = model.observe_FT(inputs, args.task_idx, labels)
+                        loss, correct = model.observe_FT(inputs, args.task_idx, labels, **src)
                     else:
-                        loss, correct, batch_stats = model.observe(inputs, args.task_idx, labels)
+                        loss, correct, batch_stats = model.observe(inputs, args.task_idx, labels, **src)
                         projected.extend(batch_stats["projected_grads"])
                     running_loss = running_loss + loss.double().sum()
                     running_corrects = running_corrects + correct
@@ -162,6 +167,9 @@ def main(overwrite_args, nc_per_task, device="cuda"):
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}
     in_shape = tuple(args.dset_loaders["train"].x.shape[1:])
+    # a train split with a transform: the wrapper stores frames and re-augments them at every replay (exemplar.py)
+    spec = args.dset_loaders["train"].transform
+    frames = dict(exemplar_transform=spec, frame_shape=tuple(dsets["train"].x.shape[1:])) if spec is not None else {}
     if baseline:
         step_rows = exemplar_split(args, dset_sizes)
 
@@ -170,7 +178,7 @@ def main(overwrite_args, nc_per_task, device="cuda"):
             assert args.task_idx == 0
             raw = R.replace_head(torch.load(args.prev_model_path, weights_only=False), args.n_outputs)    # :36-41
             model = R.RehearsalNet(raw, args.n_outputs, args.n_tasks, args.nc_per_task, args.n_memories, args.lr,
-                                   args.weight_decay, args.full_mem_mode, step_rows, in_shape, device)
+                                   args.weight_decay, args.full_mem_mode, step_rows, in_shape, device, **frames)
         else:
             model = torch.load(args.prev_model_path, weights_only=False)
             if model.batch_size < step_rows:
@@ -181,7 +189,7 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         raw = torch.load(args.prev_model_path, weights_only=False)
         raw = G.extend_head(raw, args.n_outputs)                   # gem.py:96-113
         model = G.GemNet(raw, args.n_outputs, args.n_tasks, args.nc_per_task, args.n_memories, args.lr,
-                         args.weight_decay, args.memory_strength, args.batch_size, in_shape, device)
+                         args.weight_decay, args.memory_strength, args.batch_size, in_shape, device, **frames)
     else:
         model = torch.load(args.prev_model_path, weights_only=False)
         if model.batch_size < args.batch_size:

@@ -13,6 +13,10 @@ with the sample plan (which exemplars, in which chunk order) drawn on the host e
 copied to the device in one non-blocking copy.  A plan with BatchNorm normalises every chunk with its own batch
 statistics, so it takes the segmented path instead: one loss_step per chunk in the reference's order, weighted
 accumulation with clhip_axpy.
+
+Frame mode (exemplar.py): the store holds the loader's frames, the ring update copies them by sample number, and the step's
+exemplars get one fresh (top, left, flip) each, drawn on the host after the plan and applied by the assembly launch
+(clhip_rehearsal_assemble_crop_flip in place of clhip_rehearsal_assemble; everything after it is the same).
 """
 import random
 
@@ -41,11 +45,12 @@ class _Order(DeviceLoader):
         self.n, self.shuffle = int(n), True
 
 
-def sample_plan(t, n_append, observed_tasks, n_memories, chunk_size, filled=None):
+def sample_plan(t, n_append, observed_tasks, n_memories, chunk_size, filled=None, seeds=None):
     """The reference's exemplar draws for one observe_FT step at task index t (:191-234), on Python `random` and the
     global torch CPU generator.  Returns (counts, [(task, slots, chunks)]) with chunks = lists of slots in the order the
     exemplar DataLoader of that task yields them.  `filled[task]` (optional) = slots of the task ever written: a slot at
-    or above it is a None path in the reference."""
+    or above it is a None path in the reference.  `seeds` (optional list) collects the worker base seed every exemplar
+    DataLoader draws (and the reference hands to its workers)."""
     if not (t > 0 and n_append > 0):
         return [], []
     n_fixed = int(np.floor(n_append / t))
@@ -71,7 +76,10 @@ def sample_plan(t, n_append, observed_tasks, n_memories, chunk_size, filled=None
                              "load a None path)" % (max(slots), past, filled[past]))
         if chunk_size <= 0:
             raise ValueError("rehearsal: exemplar chunk size %d (batch fully taken by exemplars)" % chunk_size)
-        perm = _Order(cnt).order().tolist()
+        loader = _Order(cnt)
+        perm = loader.order().tolist()
+        if seeds is not None:
+            seeds.append(loader.base_seed)
         ordered = [slots[i] for i in perm]
         out.append((past, slots, [ordered[s:s + chunk_size] for s in range(0, cnt, chunk_size)]))
     return counts, out
@@ -81,10 +89,11 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
     """baseline_rehearsal_{partial,full}_mem.Net.  The pickle carries the net, the counters and the stored rows of the
     observed tasks only.  Dropout: GEM's shared mask rows (:97-111), reset at every step."""
 
-    _TRANSIENT_EXTRA = ("store_x", "store_y")
+    _TRANSIENT_EXTRA = ("store_x", "store_y", "store_ext", "last_gather", "last_exemplar_params")
+    last_gather = last_exemplar_params = None                        # host: the last step's store rows and their draws
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, full_mem_mode=False,
-                 batch_size=200, in_shape=(3, 64, 64), device="cuda"):
+                 batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None):
         self.net = model.to(device)
         self.device = torch.device(device)
         self.n_outputs, self.n_tasks = n_outputs, n_tasks
@@ -94,6 +103,7 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
         self.n_memories = self.n_total_memories if self.full_mem_mode else n_memories
         self.batch_size = batch_size
         self.in_shape = tuple(in_shape)
+        self._init_frames(exemplar_transform, frame_shape)
         self.cum_nc_per_task = [sum(nc_per_task[:i + 1]) for i in range(len(nc_per_task))]
         self.observed_tasks, self.old_task, self.mem_cnt = [], -1, 0
         self.filled = [0] * n_tasks                                 # slots of each task written at least once
@@ -120,15 +130,22 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
 
     def _rows_state(self):
         rows = (max(self.observed_tasks) + 1) * self.n_memories if self.observed_tasks else 0
-        return {"_rows_x": self.store_x[:rows].clone(), "_rows_y": self.store_y[:rows].clone()}
+        state = {"_rows_x": self.store_x[:rows].clone(), "_rows_y": self.store_y[:rows].clone()}
+        if self.exemplar_transform is not None:
+            state["_rows_ext"] = self.store_ext[:rows].clone()
+        return state
 
     def _load_rows(self, rows):
         n = self.n_total_memories
-        self.store_x = torch.zeros((n,) + self.in_shape, dtype=torch.float32, device=self.device)
+        self.store_x = torch.zeros((n,) + self.store_shape, dtype=torch.float32, device=self.device)
         self.store_y = torch.zeros((n,), dtype=torch.int64, device=self.device)
+        if self.exemplar_transform is not None:
+            self.store_ext = self._full_ext(n)                       # host [rows][2]: valid (h, w) of every stored frame
         if rows:
             self.store_x[:rows["_rows_x"].shape[0]].copy_(rows["_rows_x"])
             self.store_y[:rows["_rows_y"].shape[0]].copy_(rows["_rows_y"])
+            if self.exemplar_transform is not None:
+                self.store_ext[:rows["_rows_ext"].shape[0]].copy_(rows["_rows_ext"])
 
     def _row(self, task, slot):
         return task * self.n_memories + slot
@@ -147,12 +164,13 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
             return
         n_new = int(self.n_total_memories / len(self.observed_tasks))
         self.filled = [min(f, n_new) for f in self.filled]
-        compact_blocks((self.store_x, self.store_y), self.n_memories, n_new, self.filled)
+        stores = (self.store_x, self.store_y) + (() if self.exemplar_transform is None else (self.store_ext,))
+        compact_blocks(stores, self.n_memories, n_new, self.filled)
         self.n_memories = n_new
 
-    def ring_update(self, t, B):
+    def ring_update(self, t, B, source=None):
         """:170-186: the first eff rows of a B-row batch go to slots [mem_cnt, mem_cnt + eff) of task t; the counter wraps
-        at n_memories.  Returns (first store row, eff)."""
+        at n_memories.  Frame mode: their extents go to store_ext.  Returns (first store row, eff)."""
         if (t + 1) * self.n_memories > self.store_x.shape[0]:
             raise ValueError("rehearsal: task %d does not fit the exemplar store" % t)
         endcnt = min(self.mem_cnt + B, self.n_memories)
@@ -160,21 +178,35 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
         row0 = self._row(t, self.mem_cnt)
         self.filled[t] = max(self.filled[t], endcnt)
         self.mem_cnt = 0 if endcnt == self.n_memories else endcnt
+        if self.exemplar_transform is not None:
+            self.store_ext[row0:row0 + eff] = self._source_ext(source, eff)
         return row0, eff
 
-    def plan(self, t):
-        return sample_plan(t, self.n_append, self.observed_tasks, self.n_memories, self.chunk_size, self.filled)
+    def plan(self, t, seeds=None):
+        return sample_plan(t, self.n_append, self.observed_tasks, self.n_memories, self.chunk_size, self.filled, seeds)
+
+    def exemplar_params(self, gather, seeds):
+        """Frame mode: host int32 [len(gather)][3], one (top, left, flip) per gathered store row in gather order, over the
+        rows' own extents; the generator is seeded with the base seed the plan's last exemplar loader drew anyway (`seeds`
+        of plan()), so the global generator and Python `random` are consumed exactly as in crop mode.  No exemplars: no draws."""
+        if not gather:
+            return torch.zeros((0, 3), dtype=torch.int32)
+        return self.draw_exemplar_params(self.store_ext[torch.tensor(gather, dtype=torch.int64)], seeds[-1])
 
     # ------------------------------------------------------------------ the step (:125-253)
-    def observe_FT(self, x, t, y):
-        """One rehearsal step: returns device (loss, hits on the current batch)."""
+    def observe_FT(self, x, t, y, source=None):
+        """One rehearsal step: returns device (loss, hits on the current batch).  source: the batch's BatchSource in frame
+        mode (exemplar.batch_source(loader)), None in crop mode."""
+        self._check_source(source)
+        frames = self.exemplar_transform is not None
         self.net.train(True)
         self.reset_dropout_config()
         if t != self.old_task:
             self.switch_task(t)
         B = int(y.shape[0])
-        ring_row0, eff = self.ring_update(t, B)
-        _, plan = self.plan(t)
+        ring_row0, eff = self.ring_update(t, B, source)
+        seeds = []
+        _, plan = self.plan(t, seeds)
         chunks = [(past, ch) for past, _, chs in plan for ch in chs]
         segs = [(0, B) + self._slice(t) + (1.0, 0)]                 # every segment is of kind 0: cross-entropy
         gather = []
@@ -184,12 +216,20 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
         E, N = len(gather), B + len(gather)
         if N > self.batch_size:
             raise RuntimeError("rehearsal: step of %d rows > engine batch %d" % (N, self.batch_size))
-        gather_dev, segs_dev = self._upload(gather, ops.loss_segment_rows(segs))
-        row_elems = int(np.prod(self.in_shape))
-        check(_lib.lib().clhip_rehearsal_assemble(
-            x.data_ptr(), y.data_ptr(), B, row_elems, self.store_x.data_ptr(), self.store_y.data_ptr(), self.store_x.shape[0],
-            ring_row0, eff, gather_dev.data_ptr() if E else None, E, self.x_mix.data_ptr(), self.y_mix.data_ptr(), _stream()),
-            "clhip_rehearsal_assemble")
+        self.last_gather = list(gather)
+        if frames:
+            self.last_exemplar_params = self.exemplar_params(gather, seeds)
+            gather_dev, segs_dev, params_dev = self._upload(gather, ops.loss_segment_rows(segs), self.last_exemplar_params)
+            ops.rehearsal_assemble_crop_flip(self.geometry, x, y, B, source.frames, source.idx, self.store_x, self.store_y,
+                                             ring_row0, eff, gather_dev if E else None, params_dev if E else None, self.x_mix,
+                                             self.y_mix)
+        else:
+            gather_dev, segs_dev = self._upload(gather, ops.loss_segment_rows(segs))
+            row_elems = int(np.prod(self.in_shape))
+            check(_lib.lib().clhip_rehearsal_assemble(
+                x.data_ptr(), y.data_ptr(), B, row_elems, self.store_x.data_ptr(), self.store_y.data_ptr(), self.store_x.shape[0],
+                ring_row0, eff, gather_dev.data_ptr() if E else None, E, self.x_mix.data_ptr(), self.y_mix.data_ptr(), _stream()),
+                "clhip_rehearsal_assemble")
         self._dropout(True)
         self.stats.zero_()
         xm, ym = self.x_mix[:N], self.y_mix[:N]

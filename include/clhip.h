@@ -481,6 +481,23 @@ int clhip_gem_project_dev(const float* G, size_t ld, const int* row_idx_host, co
  *                         store[gather_rows[e]] -> x_mix[B + e], e < E                the exemplar chunks (:214-234)
  *                       gather_rows (device int32[E]) hold store row indices of PAST tasks (never the ring rows).
  *                       store rows >= store_rows are not read (label -1).  B + ring_rows + E <= 65535.
+ *   rehearsal_assemble_crop_flip  the same launch for a store of FRAMES [C][Hs][Ws] (the reference's memories hold paths and
+ *                       every replay rebuilds the exemplar loader with the task's train transform, :215-216, gem.py:233-234, so
+ *                       an exemplar gets a fresh RandomCrop + RandomHorizontalFlip at every draw); x and x_mix rows are
+ *                       [C][th][tw]:
+ *                         x[0:B)                          -> x_mix[0:B)                 (the loader already cropped them)
+ *                         src_frames[src_idx[i]] (whole)  -> store rows [ring_row0, +ring_rows), labels_i64[i] -> store_labels
+ *                         x_mix[B + e][c][y][x] = store[gather_rows[e]][c][top_e + y][left_e + (flip_e ? tw - 1 - x : x)]
+ *                       src_frames: the loader's frame tensor (src_rows frames), src_idx device int64[ring_rows] the sample
+ *                       numbers of the batch's first rows (the `paths` argument of the reference's observe); gather_params
+ *                       device int32[E][3] of (top, left, flip) as in clhip_gather_tasks_crop_flip below.  A src_idx outside
+ *                       [0, src_rows) leaves its store row untouched and writes store label -1; a gather row outside
+ *                       [0, store_rows), top outside [0, Hs - th], left outside [0, Ws - tw] or flip outside {0, 1} copies
+ *                       nothing and writes label -1; no address outside a frame is formed.  x_mix == NULL (E == 0 only): the
+ *                       ring update alone, rows [0, B) are not copied (GEM's fill_buffer).  CLHIP_EINVAL before any launch:
+ *                       the checks of clhip_rehearsal_assemble and of clhip_gather_tasks_crop_flip's geometry.  16-byte
+ *                       copies of full rows / frames under the rule above; float4 stores of the cropped rows when
+ *                       tw % 4 == 0 and x_mix is 16-byte aligned, loads at dword alignment.
  *   loss_segments       segs (device, n_segs <= CLHIP_LOSS_MAX_SEGS) cover rows of logits[N][ld], N <= CLHIP_LOSS_MAX_ROWS, each
  *                       with a class slice [col_off, col_off + ncols), a scale and a kind:
  *                         kind 0  scale * mean_i CE_i over the slice against labels (relative to the slice)
@@ -504,6 +521,11 @@ typedef struct clhip_loss_segment { int row_begin; int row_end; int col_off; int
 int clhip_rehearsal_assemble(const float* x, const int64_t* labels_i64, int B, size_t row_elems, float* store_x,
                              int64_t* store_labels, long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
                              int E, float* x_mix, int64_t* labels_mix, void* stream);
+int clhip_rehearsal_assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                       const float* src_frames, long src_rows, const int64_t* src_idx, float* store_frames,
+                                       int64_t* store_labels, long store_rows, long ring_row0, int ring_rows,
+                                       const int* gather_rows, const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
+                                       void* stream);
 int clhip_loss_segments(const float* logits, const int64_t* labels_i64, const float* targets, int ld_t, int N, int ld,
                         const clhip_loss_segment* segs, int n_segs, float T, float* dlogits, float* loss_out, double* stats,
                         void* stream);
