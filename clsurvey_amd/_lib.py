@@ -136,6 +136,8 @@ SIGNATURES = {
     "clhip_net_probe_read": (_i, [_p, C.POINTER(_f), C.POINTER(_i)]),
     "clhip_net_layer_input": (_i, [_p, _i, _p, _p]),
     "clhip_net_layer_pool_idx": (_i, [_p, _i, _p, _p]),
+    "clhip_net_prepared_weights": (_i, [_p, _p, _p]),
+    "clhip_net_edge_grid_count": (_i, [_p]),
     "clhip_net_layer_paths": (_i, [_p, _i]),
     "clhip_net_probe_kind": (_i, [_p, _i, _i]),
     "clhip_net_set_input_grad": (_i, [_p, _i, _p]),

@@ -179,6 +179,10 @@ int clhip_internal_convkk(int mode, const float* in, const float* w, const float
 struct clhip_wino_wt { const float* w; float* U; int Ko, Ci, mode, pad; };
 int clhip_internal_wino_weights(const clhip_wino_wt* jobs, int n, hipStream_t s);
 int clhip_internal_weight_images(const clhip_wino_wt* wino_jobs, int n_wino, const clhip_wino_wt* bs_jobs, int n_bs, hipStream_t s);   // both kinds, one launch
+// conv3x3.hip: the first layer's fused conv + ReLU + pool launch with those images built by blocks of the same grid; CLHIP_ENOTSUP: two launches
+int clhip_internal_c3w64_pool_weight_images(const float* x, const float* w, const float* b, float* y_pool, uint8_t* idx_u8, int N, int C,
+                                            int K, int H, int W, const clhip_wino_wt* wino_jobs, int n_wino, const clhip_wino_wt* bs_jobs,
+                                            int n_bs, int wt_first, hipStream_t s);
 int clhip_internal_wino_conv_u(int mode, const float* in, const float* U, const float* bias, const float* mask_src, float* out,
                                uint8_t* pool_idx, int unpool, int N, int Cin, int Cout, int H, int W, int relu, hipStream_t s);
 bool clhip_internal_wino_ok(int Cin, int Cout, int H, int W);

@@ -18,6 +18,7 @@
 // LDS per buffer: weights [CK*9][65] + activations [CK][PLANE]; two buffers, register-staged
 // prefetch of chunk t+1 while chunk t feeds the matrix pipe (one barrier per chunk).
 #include "common.hpp"
+#include "weight_images.hpp"
 
 namespace {
 
@@ -961,19 +962,23 @@ __device__ __forceinline__ floatx16 c3w64_fake_mfma(float a, float b, floatx16 c
 #else
 #define C3W64_MFMA(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, x, y, z)
 #endif
+// The block body over an LDS base and a block index (bx of gx blocks along the units, by = channel tile), so that the SAME code is both
+// the launch of its own (conv3x3_c3w64_relu_pool_kernel) and the first-layer half of a merged grid (c3w64_relu_pool_wt_kernel below).
+// halo_s: 8 * 2 * W6_HALO floats, 16-byte aligned; aux_s: KT floats (bias) or W6_TWP + 5 (CLHIP_C3W64_BIAS_IN_K: ones).
+constexpr int W6_AUX = CLHIP_C3W64_BIAS_IN_K ? W6_TWP + 5 : KT;
 template <bool FULL>       // FULL: every block owns 64 real output channels (no per-store channel predicate)
-__global__ __launch_bounds__(512) void conv3x3_c3w64_relu_pool_kernel(
+__device__ __forceinline__ void c3w64_relu_pool_body(
+    float* __restrict__ halo_s, float* __restrict__ aux_s, const int bx, const int by, const int gx,
     const float* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ bias,
     float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N, int Cout, int H, int W,
     int tiles_w, int row_pairs, int ntiles) {
-    __shared__ __attribute__((aligned(16))) float halo_s[8 * 2 * W6_HALO];
 #if CLHIP_C3W64_BIAS_IN_K
-    __shared__ float ones_s[W6_TWP + 5];
+    float* const ones_s = aux_s;
 #else
-    __shared__ float bias_s[KT];
+    float* const bias_s = aux_s;
 #endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kk = lane >> 5;
-    const int ko0 = blockIdx.y * KT;
+    const int ko0 = by * KT;
 #if CLHIP_C3W64_BIAS_IN_K
     if (tid < W6_TWP + 5) ones_s[tid] = 1.f;
 #else
@@ -1010,7 +1015,7 @@ __global__ __launch_bounds__(512) void conv3x3_c3w64_relu_pool_kernel(
     };
 
     // units of this wave
-    const int simd = blockIdx.x * 4 + (wave & 3), nsimd = gridDim.x * 4;
+    const int simd = bx * 4 + (wave & 3), nsimd = gx * 4;
     const int units = 2 * ntiles;
     const int per = units / nsimd, rem = units - per * nsimd;
     const int s_start = simd * per + min(simd, rem), s_cnt = per + (simd < rem ? 1 : 0);
@@ -1164,13 +1169,80 @@ __global__ __launch_bounds__(512) void conv3x3_c3w64_relu_pool_kernel(
     }
 }
 
+template <bool FULL>
+__global__ __launch_bounds__(512) void conv3x3_c3w64_relu_pool_kernel(
+    const float* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ bias,
+    float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N, int Cout, int H, int W,
+    int tiles_w, int row_pairs, int ntiles) {
+    __shared__ __attribute__((aligned(16))) float halo_s[8 * 2 * W6_HALO];
+    __shared__ float aux_s[W6_AUX];
+    c3w64_relu_pool_body<FULL>(halo_s, aux_s, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, x, wt, bias, out, pool_idx, N, Cout, H, W,
+                               tiles_w, row_pairs, ntiles);
+}
+
+// The first layer's forward AND the prepared-weights launch of the pass (weight_images.hpp) as ONE grid.  The weight images — Winograd
+// U and bf16-split, forward and backward sets — are first read by layer 2, not by this layer; their launch of its own is a few hundred
+// 256-thread blocks of one load -> a few adds -> a few stores each (latency-bound, ~8 us on an otherwise empty chip) in front of a
+// kernel that is bound by issue on the f32 matrix pipe.  Here a contiguous range of nwb blocks at one end of a 1-D grid runs the
+// weight jobs and the other gx * kts blocks run the body above with (bx, by) = (b % gx, b / gx): grid size, block size and the
+// unit-to-SIMD dealing of the first-layer half are those of the launch of its own => same bits from both halves.
+//   * 512-thread blocks carry TWO 256-thread weight blocks, threads 0..255 block 2 wb and threads 256..511 block 2 wb + 1 (the body has
+//     no LDS and no barrier, so halves of a block do not meet): every wave of the block has work, half as many blocks wait for a CU, and
+//     the per-job code is the unchanged 256-thread body.  (One job on half a block would leave 4 of 8 waves idle for the same slots.)
+//   * The two halves do NOT share a CU: this kernel needs ~170 VGPRs (the body), 2 waves per SIMD fill the register file, and a block is
+//     8 waves.  What the merged grid gains is the launch boundary and the uneven end of the first-layer half: at N = 200 the blocks
+//     of the lower half of the grid own 13 units per SIMD and those of the upper half 12, so half of the CUs are free for the last
+//     ~1/13 of the kernel — long enough for the weight blocks whichever end they sit at (wt_first: dispatched first, the first-layer
+//     blocks behind them start a few us late; otherwise dispatched last, into the CUs the short blocks leave).  Both orders were
+//     measured against the two launches (profiles/edge_grids_orders.json): the executor puts the weight blocks last
+//     (CLHIP_EDGE_GRIDS=2: first).
+template <bool FULL>
+__global__ __launch_bounds__(512) void c3w64_relu_pool_wt_kernel(
+    const float* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ bias,
+    float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N, int Cout, int H, int W,
+    int tiles_w, int row_pairs, int ntiles, int gx, int nfl, int nwb, int wt_first, WtJobs J) {
+    __shared__ __attribute__((aligned(16))) float halo_s[8 * 2 * W6_HALO];
+    __shared__ float aux_s[W6_AUX];
+    const int b = (int)blockIdx.x;
+    const int fb = wt_first ? b - nwb : b;              // first-layer block, or out of [0, nfl): a weight block
+    if ((unsigned)fb >= (unsigned)nfl) {
+        const int vb = 2 * (wt_first ? b : b - nfl) + ((int)threadIdx.x >> 8);
+        if (vb < J.first[J.n]) weight_image_block(J, vb, (int)threadIdx.x & 255);
+        return;
+    }
+    c3w64_relu_pool_body<FULL>(halo_s, aux_s, fb % gx, fb / gx, gx, x, wt, bias, out, pool_idx, N, Cout, H, W, tiles_w, row_pairs, ntiles);
+}
+
+// grid of the first-layer launch: one 8-wave block per CU along the units x channel tiles
+static inline long long c3w64_gx(long long ntiles) {
+    long long gx = 256;
+    if (gx * 8 > 2 * ntiles) gx = (2 * ntiles + 7) / 8;
+    return gx;
+}
+
+int launch_c3w64_pool_wt(const float* x, const float* wt, const float* bias, float* out, uint8_t* idx, int N, int Cout, int H, int W,
+                         const WtJobs& J, int wt_first, hipStream_t s) {
+    const int tiles_w = W / 64, row_pairs = H / 2;
+    const long long ntiles = (long long)tiles_w * row_pairs * N;
+    const int kts = (Cout + KT - 1) / KT;
+    const long long gx = c3w64_gx(ntiles);
+    const int nfl = (int)(gx * kts), nwb = (J.first[J.n] + 1) / 2;
+    if (Cout % KT == 0)
+        hipLaunchKernelGGL(c3w64_relu_pool_wt_kernel<true>, dim3((unsigned)(nfl + nwb)), dim3(512), 0, s,
+                           x, wt, bias, out, idx, N, Cout, H, W, tiles_w, row_pairs, (int)ntiles, (int)gx, nfl, nwb, wt_first, J);
+    else
+        hipLaunchKernelGGL(c3w64_relu_pool_wt_kernel<false>, dim3((unsigned)(nfl + nwb)), dim3(512), 0, s,
+                           x, wt, bias, out, idx, N, Cout, H, W, tiles_w, row_pairs, (int)ntiles, (int)gx, nfl, nwb, wt_first, J);
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_c3w64_pool(const float* x, const float* wt, const float* bias, float* out, uint8_t* idx,
                       int N, int Cout, int H, int W, hipStream_t s) {
     const int tiles_w = W / 64, row_pairs = H / 2;
     const long long ntiles = (long long)tiles_w * row_pairs * N;
     const int kts = (Cout + KT - 1) / KT;
-    long long gx = 256;                             // one 8-wave block per CU
-    if (gx * 8 > 2 * ntiles) gx = (2 * ntiles + 7) / 8;
+    const long long gx = c3w64_gx(ntiles);          // one 8-wave block per CU
     if (Cout % KT == 0)
         hipLaunchKernelGGL(conv3x3_c3w64_relu_pool_kernel<true>, dim3((unsigned)gx, (unsigned)kts), dim3(512), 0, s,
                            x, wt, bias, out, idx, N, Cout, H, W, tiles_w, row_pairs, (int)ntiles);
@@ -1194,6 +1266,12 @@ int launch_c3_pool(const float* x, const float* wt, const float* bias, float* ou
                        x, wt, bias, out, idx, N, Cout, H, W, tiles_w, tiles_h, (int)ntiles);
     CLHIP_LAUNCH_CHECK();
     return 0;
+}
+
+// shapes of conv3x3_c3w64_relu_pool_kernel (32-bit byte offsets into x and the pooled output)
+bool c3w64_shape(int N, int C, int K, int H, int W) {
+    return CLHIP_C3W64 && C == 3 && W % 64 == 0 && H % 2 == 0 && (size_t)N * 3 * H * W < ((size_t)1 << 29) &&
+           (size_t)N * K * (H / 2) * (W / 2) < ((size_t)1 << 29);
 }
 
 // 16-byte staging needs aligned rows and whole tiles along w.
@@ -1227,15 +1305,32 @@ int clhip_conv3x3_relu_pool_fwd(const float* x, const float* w, const float* b, 
     if (!x || !w || !y_pool || !idx_u8 || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1))
         return CLHIP_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (CLHIP_C3W64 && C == 3 && W % 64 == 0 && H % 2 == 0 && (size_t)N * 3 * H * W < ((size_t)1 << 29) &&
-        (size_t)N * K * (H / 2) * (W / 2) < ((size_t)1 << 29))
-        return launch_c3w64_pool(x, w, b, y_pool, idx_u8, N, K, H, W, s);
+    if (c3w64_shape(N, C, K, H, W)) return launch_c3w64_pool(x, w, b, y_pool, idx_u8, N, K, H, W, s);
     if (C == 3 && W % C3_TW == 0) return launch_c3_pool(x, w, b, y_pool, idx_u8, N, K, H, W, s);
 
     if (C <= 4) return launch_conv<4, 0, false>(x, w, b, nullptr, y_pool, N, C, K, H, W, K, C, 1, s, idx_u8);
     if (vec_ok(x, w, C, H, W, C)) return launch_conv<8, 0, true>(x, w, b, nullptr, y_pool, N, C, K, H, W, K, C, 1, s, idx_u8);
     return launch_conv<8, 0, false>(x, w, b, nullptr, y_pool, N, C, K, H, W, K, C, 1, s, idx_u8);
 }
+
+}  // extern "C"
+
+// clhip_conv3x3_relu_pool_fwd of a first layer on conv3x3_c3w64_relu_pool_kernel with the weight images of the pass (Winograd jobs wj,
+// bf16-split jobs bj: the table of clhip_internal_weight_images) built by blocks of the SAME grid.  wt_first: the weight blocks sit at
+// the front of the grid (else at its end).  CLHIP_ENOTSUP — nothing launched, the caller takes the two launches — when the first layer
+// runs on another kernel or the jobs do not fit one table.
+int clhip_internal_c3w64_pool_weight_images(const float* x, const float* w, const float* b, float* y_pool, uint8_t* idx_u8, int N, int C,
+                                            int K, int H, int W, const clhip_wino_wt* wj, int nw, const clhip_wino_wt* bj, int nb,
+                                            int wt_first, hipStream_t s) {
+    if (!x || !w || !y_pool || !idx_u8 || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return CLHIP_EINVAL;
+    if (!c3w64_shape(N, C, K, H, W) || nw < 0 || nb < 0 || nw + nb <= 0 || nw + nb > WT_JOBS) return CLHIP_ENOTSUP;
+    WtJobs J;
+    const int blocks = weight_jobs_table(wj, nw, bj, nb, J);
+    if (blocks < 0) return blocks;
+    return launch_c3w64_pool_wt(x, w, b, y_pool, idx_u8, N, K, H, W, J, wt_first, s);
+}
+
+extern "C" {
 
 int clhip_conv3x3_bwd_data(const float* dy, const float* w, const float* relu_src, float* dx,
                            int N, int C, int K, int H, int W, void* stream) {

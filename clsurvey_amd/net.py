@@ -276,6 +276,19 @@ class NetEngine:
         check(_lib.lib().clhip_net_layer_pool_idx(self._h, int(layer), C.byref(off), C.byref(elems)), "clhip_net_layer_pool_idx")
         return self.ws[off.value:off.value + n * elems.value].view(n, elems.value)
 
+    def prepared_weights(self):
+        """uint8 view (no copy, possibly empty) of the workspace region that holds the transformed weights of the last pass."""
+        off, nbytes = C.c_size_t(), C.c_size_t()
+        check(_lib.lib().clhip_net_prepared_weights(self._h, C.byref(off), C.byref(nbytes)), "clhip_net_prepared_weights")
+        return self.ws[off.value:off.value + nbytes.value]
+
+    def edge_grid_count(self):
+        """Forward passes so far whose weight images were built inside the first layer's forward launch (CLHIP_EDGE_GRIDS)."""
+        n = _lib.lib().clhip_net_edge_grid_count(self._h)
+        if n < 0:
+            raise RuntimeError("clhip_net_edge_grid_count")
+        return n
+
     def layer_paths(self, layer):
         """{'fwd', 'bwd_data', 'bwd_weight'} -> True where the plan runs the layer's kernel through a prepared-weights path
         (Winograd, csrc/wino.hip) instead of the direct f32 kernels; 'bs_fwd' / 'bs_bwd_data' -> True where that launch is the

@@ -408,6 +408,14 @@ int clhip_net_probe_read(void* handle, float* avg_us, int* count);
  * (clhip_net_layer_input) this is every non-linear decision the backward pass will use — what a parity harness
  * needs to judge gradients independently of ReLU / arg-max near-ties.  EINVAL for layers without a pool.   */
 int clhip_net_layer_pool_idx(void* handle, int layer, size_t* ws_byte_off, size_t* elems_per_sample);
+/* Where the prepared weights of a pass live (Winograd U images and bf16-split images of every layer that takes such a path, written
+ * at the start of each forward / stand-alone backward): byte offset into ws and size; *bytes = 0 for a plan without such layers.
+ * A parity harness compares the region between two ways of launching its jobs (CLHIP_EDGE_GRIDS). */
+int clhip_net_prepared_weights(void* handle, size_t* ws_byte_off, size_t* bytes);
+/* How many forward passes of this plan built those weights INSIDE the first layer's forward launch (one merged grid,
+ * CLHIP_EDGE_GRIDS != 0) instead of by a launch of their own; < 0 on error.  While it counts, a forward probe on layer 0
+ * (clhip_net_probe_kind 0) times the merged launch, weight blocks included; with the separate launches they lie outside the pair. */
+int clhip_net_edge_grid_count(void* handle);
 /* Which kernels the plan chose for a layer (measurement harnesses time the same ones): bit 0 forward, bit 1 backward-data, bit 2
  * weight gradient through a prepared-weights path instead of the direct f32 MFMA kernels — Winograd F(2x2,3x3) (csrc/wino.hip)
  * unless bit 3 (forward) / bit 4 (backward-data) says the launch is the bf16-split kernel (csrc/bsconv.hip); bit 5: the weight
