@@ -283,6 +283,8 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lwf_loss_kernel(const float* __res
                 for (int c = 0; c < C; ++c) dz[o + c] = 0.f;
             }
         }
+        // columns past the last head (ld > sum of the heads) carry no loss: zero, as the slice and segment kernels do
+        for (int c = hd.off[hd.n - 1] + hd.size[hd.n - 1]; c < ld; ++c) dz[c] = 0.f;
     }
     s_task[row] = task; s_dist[row] = dist; s_corr[row] = (unsigned char)ok;
     __syncthreads();

@@ -197,7 +197,7 @@ int clhip_mse_zero_sum(const float* logits, size_t n, float* dlogits, float* los
 /* LwF objective over stacked heads — LwF/main_LWF.py:47-76 (distillation_loss) and :184-202 (train_model_lwf):
  * logits [N][ld] = n_heads heads side by side (head_sizes, host array); last head = new task, CrossEntropy(mean);
  * every earlier head is distilled (temperature T) towards teacher [N][ld_teacher] (same column layout).
- * dlogits = d(task + reg_lambda * sum dist)/dlogits; loss_out2[0] = task loss, [1] = reg_lambda * sum of the
+ * dlogits [N][ld] = d(task + reg_lambda * sum dist)/dlogits (columns past the last head = 0); loss_out2[0] = task loss, [1] = reg_lambda * sum of the
  * distillation terms; stats (optional, f64[2]) += (task loss, #correct on the new head). distill = 0: validation
  * (task loss / accuracy only, zero gradient on the old heads). N <= 1024.                                      */
 int clhip_lwf_loss(const float* logits, const int64_t* labels_i64, const float* teacher, const int* head_sizes, int n_heads,

@@ -1,0 +1,96 @@
+"""Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py) — test infrastructure.
+
+The fp32-chain rule is the one of assert_fp32_parity in test_gpu_parity.py with the bounds these two files use: the device
+result's distance from an fp64 evaluation of the same formula on the same float32 inputs, relative to the tensor's largest
+entry, must not exceed max(base, 4 x the distance of torch's own float32 CPU evaluation).  The factor 4: device expf / logf /
+powf / coshf are allowed a few ulp more than the host's, and the row sums run in another order.  Every figure is printed
+before it is asserted (`MEASURED|<test id>|<what>|<device>|<float32 CPU>`), so one run with -s yields the headroom tables
+kept in the docstrings of the two test files."""
+import torch
+
+LOSS_BASE = 1e-5      # what test_softmax_ce asserts
+HAT_BASE = 1e-6       # what test_elementwise_regularizers_match_oracle asserts for its SGD steps
+CPU_FACTOR = 4.0
+
+
+def fp32_chain_check(case, what, got, ref32, ref64, base):
+    got = torch.as_tensor(got).detach().double().cpu().reshape(-1)
+    ref32 = torch.as_tensor(ref32).detach().double().reshape(-1)
+    ref64 = torch.as_tensor(ref64).detach().double().reshape(-1)
+    assert got.shape == ref64.shape == ref32.shape, (what, got.shape, ref32.shape, ref64.shape)
+    assert bool(torch.isfinite(ref64).all()), what + ": the fp64 reference is not finite"
+    scale = max(float(ref64.abs().max()), 1e-30)
+    d = (got - ref64).abs()
+    e_dev = float(d.max()) / scale if bool(torch.isfinite(got).all()) else float("inf")
+    e_cpu = float((ref32 - ref64).abs().max()) / scale
+    print("MEASURED|%s|%s|%.3e|%.3e" % (case, what, e_dev, e_cpu))
+    assert e_dev <= max(base, CPU_FACTOR * e_cpu), \
+        "%s: %.3e of its scale from the fp64 value (float32 CPU: %.3e, base %.0e)" % (what, e_dev, e_cpu, base)
+    return e_dev, e_cpu
+
+
+def ulp_distance(a, b):
+    """Largest distance in float32 units in the last place between two float32 tensors (0 <=> bitwise equal up to the sign
+    of zero); NaN anywhere => a huge number."""
+    a, b = a.detach().cpu().contiguous().reshape(-1), b.detach().cpu().contiguous().reshape(-1)
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape
+    if a.numel() == 0:
+        return 0
+    if bool(torch.isnan(a).any()) or bool(torch.isnan(b).any()):
+        return 1 << 40
+
+    def key(x):                                       # monotone map of the float32 line onto the integers
+        i = x.view(torch.int32).to(torch.int64)
+        return torch.where(i < 0, -(i & 0x7fffffff), i)
+    return int((key(a) - key(b)).abs().max())
+
+
+def bitwise_equal(a, b):
+    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
+    return a.shape == b.shape and a.dtype == b.dtype and bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
+
+
+class Arena:
+    """Tensors packed into one flat float32 buffer, each at a 16-byte boundary or exactly one float past one, with sentinel
+    gaps between them: one upload, one download, and a write outside any tensor shows in the gaps."""
+    GAP = 7.25
+
+    def __init__(self):
+        self.items = []            # (offset, host tensor)
+        self.size = 4
+
+    def add(self, t, misaligned=False):
+        t = t.detach().contiguous().reshape(-1).float()
+        off = (self.size + 3) // 4 * 4 + 4 + (1 if misaligned else 0)
+        self.items.append((off, t))
+        self.size = off + t.numel()
+        return len(self.items) - 1
+
+    def host(self):
+        flat = torch.full((self.size + 8,), self.GAP, dtype=torch.float32)
+        for off, t in self.items:
+            flat[off:off + t.numel()] = t
+        return flat
+
+    def upload(self, device):
+        self.dev = self.host().to(device)
+        assert self.dev.data_ptr() % 16 == 0
+        return self
+
+    def ptr(self, k):
+        off, t = self.items[k]
+        return self.dev.data_ptr() + 4 * off
+
+    def download(self):
+        self.back = self.dev.cpu()
+        return self
+
+    def get(self, k):
+        off, t = self.items[k]
+        return self.back[off:off + t.numel()]
+
+    def gaps_untouched(self):
+        keep = torch.ones(self.back.numel(), dtype=torch.bool)
+        for off, t in self.items:
+            keep[off:off + t.numel()] = False
+        return bool((self.back[keep] == self.GAP).all())
