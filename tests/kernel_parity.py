@@ -1,4 +1,5 @@
-"""Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py) — test infrastructure.
+"""Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py,
+test_gpu_gemm_kernels.py) — test infrastructure.
 
 The fp32-chain rule is the one of assert_fp32_parity in test_gpu_parity.py with the bounds these two files use: the device
 result's distance from an fp64 evaluation of the same formula on the same float32 inputs, relative to the tensor's largest
@@ -50,6 +51,16 @@ def bitwise_equal(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
 
 
+def bit_pattern(n, bits):
+    """n float32 that all hold the 32-bit pattern `bits` (a NaN with a chosen payload survives every copy bit for bit)."""
+    assert 0 <= bits < 1 << 31
+    return torch.full((n,), bits, dtype=torch.int32).view(torch.float32)
+
+
+def all_bits(t, bits):
+    return bool((t.detach().cpu().contiguous().view(torch.int32) == bits).all())
+
+
 class Arena:
     """Tensors packed into one flat float32 buffer, each at a 16-byte boundary or exactly one float past one, with sentinel
     gaps between them: one upload, one download, and a write outside any tensor shows in the gaps."""
@@ -59,7 +70,10 @@ class Arena:
         self.items = []            # (offset, host tensor)
         self.size = 4
 
-    def add(self, t, misaligned=False):
+    def add(self, t, misaligned=False, fill=None):
+        """t: a tensor, or with `fill` a number of floats that all start as that 32-bit pattern (bit_pattern)."""
+        if fill is not None:
+            t = bit_pattern(int(t), fill)
         t = t.detach().contiguous().reshape(-1).float()
         off = (self.size + 3) // 4 * 4 + 4 + (1 if misaligned else 0)
         self.items.append((off, t))
