@@ -12,8 +12,11 @@ the reference run under the same seed (utilities/utils.py:52-58).
 
 A split may carry a `RandomCropFlip` spec (the `train` split of a RecogSeq task, the `rnd_transform` file of iNaturalist):
 its stored frames stay static in HBM and the loaders crop and mirror them inside the gather that assembles each batch
-(clhip_gather_tasks_crop_flip), a fresh draw per sample per epoch.
+(clhip_gather_tasks_crop_flip), a fresh draw per sample per epoch.  A `RandomResizedCropFlip` spec (the `train` split of the
+cropped Tiny-ImageNet variant) is served the same way by the gather that resamples (clhip_gather_tasks_resized_crop_flip).
 """
+import math
+
 import torch
 from torch.utils.data import Dataset
 
@@ -35,6 +38,34 @@ class RandomCropFlip(object):
 
     def __repr__(self):
         return "RandomCropFlip(size=%s, p=%s%s)" % (self.size, self.p, "" if self.extents is None else ", extents=[%d][2]" % len(self.extents))
+
+
+RESIZE_MAX_RATIO = 8          # CLHIP_RESIZE_MAX_RATIO (include/clhip.h): the largest extent / size the resampling gather takes
+
+
+class RandomResizedCropFlip(object):
+    """RandomResizedCrop(size, scale, ratio) + RandomHorizontalFlip(p) of stored frames (data/tinyimgnet_dataprep.py:105-122,
+    the cropped Tiny-ImageNet variant; the standard ImageNet training augmentation) as a picklable spec like RandomCropFlip —
+    a class of its own, not a subclass: code that asks isinstance(t, RandomCropFlip) never takes one for the other.
+    size = (th, tw) of the output, scale the range of the window's share of the image area, ratio the range of its aspect
+    w / h, extents as in RandomCropFlip."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p=0.5, extents=None):
+        th, tw = (int(v) for v in size)
+        scale, ratio = tuple(float(v) for v in scale), tuple(float(v) for v in ratio)
+        if th < 1 or tw < 1 or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("RandomResizedCropFlip: size >= 1 and 0 <= p <= 1, got %s, %s" % (size, p))
+        if len(scale) != 2 or len(ratio) != 2 or not 0.0 < scale[0] <= scale[1] or not 0.0 < ratio[0] <= ratio[1]:
+            raise ValueError("RandomResizedCropFlip: 0 < scale[0] <= scale[1] and 0 < ratio[0] <= ratio[1], got %s, %s" % (scale, ratio))
+        self.size = (th, tw)
+        self.scale = scale
+        self.ratio = ratio
+        self.p = float(p)
+        self.extents = None if extents is None else torch.as_tensor(extents, dtype=torch.int64).cpu().reshape(-1, 2)
+
+    def __repr__(self):
+        return "RandomResizedCropFlip(size=%s, scale=%s, ratio=%s, p=%s%s)" % (
+            self.size, self.scale, self.ratio, self.p, "" if self.extents is None else ", extents=[%d][2]" % len(self.extents))
 
 
 def draw_crop_flip(n, spec, frame_hw, generator, order=None):
@@ -69,29 +100,102 @@ def draw_crop_flip(n, spec, frame_hw, generator, order=None):
     return torch.stack([top, left, flip], 1).to(torch.int32).contiguous()
 
 
+RESIZED_TRIES = 10            # RandomResizedCrop.get_params: tries before the central fallback window
+
+
+def draw_resized_crop_flip(n, spec, frame_hw, generator, order=None):
+    """int32 [n][5] of (top, left, h, w, flip), one row per position of an epoch: RandomResizedCrop.get_params on the extent
+    (H, W) of the sample served there (frame_hw, or extents[order[k]] as in draw_crop_flip).  Up to 10 tries of
+    area = H W U(scale), aspect = exp(U(log ratio[0], log ratio[1])), w = round(sqrt(area aspect)), h = round(sqrt(area /
+    aspect)) (Python's round: half to even), the first with 0 < w <= W and 0 < h <= H wins and gets top uniform on [0, H - h],
+    left uniform on [0, W - w].  Otherwise the central window clamped to the ratio range: w = W, h = round(W / ratio[0]) when
+    W / H < ratio[0]; h = H, w = round(H ratio[1]) when W / H > ratio[1]; else the whole extent; top = (H - h) // 2,
+    left = (W - w) // 2 (a side that rounds to 0 or past the extent is clamped into [1, extent]).  flip = 1 with probability
+    spec.p.  ALL uniforms of the epoch come from one torch.rand call of 2 x 10 + 3 columns per row (areas, aspects, top, left,
+    flip), whether a row uses them or not: the table is a function of the generator's seed and of `order` alone.
+    Raises if an extent exceeds the frame or RESIZE_MAX_RATIO times the size (the window could be one the gather rejects).
+
+    torchvision draws these numbers one by one from the global generator inside the DataLoader workers (see draw_crop_flip):
+    same distribution, a deterministic function of the seed here."""
+    th, tw = spec.size
+    Hs, Ws = (int(v) for v in frame_hw)
+    n = int(n)
+    if spec.extents is None:
+        H = torch.full((n,), Hs, dtype=torch.int64)
+        W = torch.full((n,), Ws, dtype=torch.int64)
+    else:
+        ext = spec.extents if order is None else spec.extents.index_select(0, torch.as_tensor(order, dtype=torch.int64))
+        if ext.shape[0] != n:
+            raise ValueError("draw_resized_crop_flip: %d extents for %d positions" % (ext.shape[0], n))
+        H, W = ext[:, 0], ext[:, 1]
+    if n and (int(H.min()) < 1 or int(W.min()) < 1):
+        raise ValueError("draw_resized_crop_flip: an empty extent")
+    if n and (int(H.max()) > Hs or int(W.max()) > Ws):
+        raise ValueError("draw_resized_crop_flip: an extent exceeds the stored frame %d x %d" % (Hs, Ws))
+    if n and (int(H.max()) > RESIZE_MAX_RATIO * th or int(W.max()) > RESIZE_MAX_RATIO * tw):
+        raise ValueError("draw_resized_crop_flip: an extent of %d x %d is more than %d times the output %d x %d"
+                         % (int(H.max()), int(W.max()), RESIZE_MAX_RATIO, th, tw))
+    K = RESIZED_TRIES
+    u = torch.rand((n, 2 * K + 3), generator=generator, dtype=torch.float64)
+    Hf, Wf = H.double()[:, None], W.double()[:, None]
+    area = Hf * Wf * (spec.scale[0] + u[:, :K] * (spec.scale[1] - spec.scale[0]))
+    l0, l1 = math.log(spec.ratio[0]), math.log(spec.ratio[1])
+    aspect = torch.exp(l0 + u[:, K:2 * K] * (l1 - l0))
+    w = torch.round(torch.sqrt(area * aspect))                    # (torch.round is half to even, as Python's)
+    h = torch.round(torch.sqrt(area / aspect))
+    ok = (w > 0) & (w <= Wf) & (h > 0) & (h <= Hf)
+    first = ok.int().argmax(1, keepdim=True) if n else torch.zeros((0, 1), dtype=torch.int64)   # (the first maximum)
+    found = ok.any(1)
+    w, h = w.gather(1, first)[:, 0].long(), h.gather(1, first)[:, 0].long()
+    top = torch.minimum((u[:, 2 * K] * (H - h + 1).double()).floor().long(), H - h)
+    left = torch.minimum((u[:, 2 * K + 1] * (W - w + 1).double()).floor().long(), W - w)
+    # the fallback of the rows no try served
+    in_ratio = W.double() / H.double()
+    fw = torch.where(in_ratio > spec.ratio[1], torch.round(H.double() * spec.ratio[1]).long(), W)
+    fh = torch.where(in_ratio < spec.ratio[0], torch.round(W.double() / spec.ratio[0]).long(), H)
+    fw, fh = torch.minimum(fw.clamp(min=1), W), torch.minimum(fh.clamp(min=1), H)
+    w, h = torch.where(found, w, fw), torch.where(found, h, fh)
+    top, left = torch.where(found, top, (H - fh) // 2), torch.where(found, left, (W - fw) // 2)
+    flip = (u[:, 2 * K + 2] < spec.p).long()
+    return torch.stack([top, left, h, w, flip], 1).to(torch.int32).contiguous()
+
+
+def _spec_key(t):
+    """What two specs must share to be served as one (the extents are per task)."""
+    return (type(t), t.size, t.p, getattr(t, "scale", None), getattr(t, "ratio", None))
+
+
+def _respec(t, extents=None):
+    """`t` with other extents."""
+    if isinstance(t, RandomResizedCropFlip):
+        return RandomResizedCropFlip(t.size, t.scale, t.ratio, t.p, extents)
+    return RandomCropFlip(t.size, t.p, extents)
+
+
 def _transform_of(dataset):
-    """The RandomCropFlip a dataset carries, else None (any other `transform` attribute is the dataset's own business)."""
+    """The RandomCropFlip or RandomResizedCropFlip a dataset carries, else None (any other `transform` attribute is the
+    dataset's own business)."""
     t = getattr(dataset, "transform", None)
-    return t if isinstance(t, RandomCropFlip) else None
+    return t if isinstance(t, (RandomCropFlip, RandomResizedCropFlip)) else None
 
 
 def merged_transform(dsets):
-    """One spec for several tasks served as one dataset: all carry equal size and p (extents concatenated in task order, a task
-    without them counts as full frames), or none carries a transform."""
+    """One spec for several tasks served as one dataset: all carry a spec of one class with equal parameters (extents
+    concatenated in task order, a task without them counts as full frames), or none carries a transform."""
     ts = [_transform_of(d) for d in dsets]
     if all(t is None for t in ts):
         return None
-    if any(t is None for t in ts) or any((t.size, t.p) != (ts[0].size, ts[0].p) for t in ts):
+    if any(t is None for t in ts) or any(_spec_key(t) != _spec_key(ts[0]) for t in ts):
         raise ValueError("tasks served as one dataset carry equal RandomCropFlip size and p, or none: %s" % ts)
     if all(t.extents is None for t in ts):
-        return RandomCropFlip(ts[0].size, ts[0].p)
+        return _respec(ts[0])
     ext = [t.extents if t.extents is not None else torch.tensor(tuple(d.x.shape[-2:])).repeat(len(d), 1) for t, d in zip(ts, dsets)]
-    return RandomCropFlip(ts[0].size, ts[0].p, torch.cat(ext))
+    return _respec(ts[0], torch.cat(ext))
 
 
 class TensorTaskDataset(Dataset):
-    """One split of one task. `classes` mirrors ImageFolder_Subset.classes (data/imgfolder.py).  `transform`: None or a
-    RandomCropFlip.  It is applied by the loaders only (DeviceLoader, MultiTaskLoader): `dataset[i]` and `.x` stay the stored
+    """One split of one task. `classes` mirrors ImageFolder_Subset.classes (data/imgfolder.py).  `transform`: None, a
+    RandomCropFlip or a RandomResizedCropFlip.  It is applied by the loaders only (DeviceLoader, MultiTaskLoader): `dataset[i]` and `.x` stay the stored
     frames, so code that reads them directly sees what it is handed."""
 
     transform = None          # class-level default: task files pickled before the attribute existed still load
@@ -102,7 +206,7 @@ class TensorTaskDataset(Dataset):
         self.y = y.contiguous().long()
         self.classes = list(classes)
         if transform is not None:
-            if not isinstance(transform, RandomCropFlip):
+            if not isinstance(transform, (RandomCropFlip, RandomResizedCropFlip)):
                 raise TypeError("TensorTaskDataset: transform is None or a RandomCropFlip")
             if transform.extents is not None and len(transform.extents) != len(self):
                 raise ValueError("TensorTaskDataset: %d extents for %d frames" % (len(transform.extents), len(self)))
@@ -174,9 +278,12 @@ class DeviceLoader:
     sliced per batch: one clhip_gather_tasks_crop_flip launch per batch, no host read.  While iterating, `last_idx` (device
     int64) and `last_idx_host` hold the sample numbers of the batch just served: with `frames` they are what an exemplar wrapper
     in frame mode stores instead of the crop (methods/exemplar.py: the counterpart of the reference's `paths`).  Difference from
-    the reference: its draws happen in DataLoader worker processes (see draw_crop_flip)."""
+    the reference: its draws happen in DataLoader worker processes (see draw_crop_flip).
+    A RandomResizedCropFlip is served by the same steps: the table holds (top, left, h, w, flip) rows from
+    draw_resized_crop_flip and the launch is clhip_gather_tasks_resized_crop_flip."""
 
     transform = None
+    _resized = False
     base_seed = None
     last_idx = last_idx_host = None
 
@@ -196,14 +303,15 @@ class DeviceLoader:
     def _augment(self, transform, xs, ys, cum_rows, label_shifts):
         """Serve `transform` of the frames xs (one tensor per task)."""
         if xs[0].dim() != 4 or any(tuple(v.shape[1:]) != tuple(xs[0].shape[1:]) for v in xs):
-            raise ValueError("RandomCropFlip needs frames [n, C, Hs, Ws] of one shape")
+            raise ValueError("%s needs frames [n, C, Hs, Ws] of one shape" % type(transform).__name__)
         C, Hs, Ws = (int(v) for v in xs[0].shape[1:])
         th, tw = transform.size
-        if th > Hs or tw > Ws:
-            raise ValueError("RandomCropFlip: crop %d x %d of frames %d x %d" % (th, tw, Hs, Ws))
+        if (th > Hs or tw > Ws) and not isinstance(transform, RandomResizedCropFlip):      # (a resized window may be enlarged)
+            raise ValueError("%s: crop %d x %d of frames %d x %d" % (type(transform).__name__, th, tw, Hs, Ws))
         if transform.extents is not None and len(transform.extents) != self.n:
-            raise ValueError("RandomCropFlip: %d extents for %d frames" % (len(transform.extents), self.n))
+            raise ValueError("%s: %d extents for %d frames" % (type(transform).__name__, len(transform.extents), self.n))
         self.transform = transform
+        self._resized = isinstance(transform, RandomResizedCropFlip)
         self.frames = xs
         self.geometry = (C, Hs, Ws, th, tw)
         self.x = xs[0].new_empty((0, C, th, tw))    # (row shape only: what engine_for reads; no memory)
@@ -225,10 +333,11 @@ class DeviceLoader:
         return torch.randperm(self.n, generator=g)
 
     def epoch_params(self, perm):
-        """Host int32 [n][3] table of the epoch whose order() returned `perm` (None: dataset order)."""
+        """Host int32 table of the epoch whose order() returned `perm` (None: dataset order): [n][3] rows of draw_crop_flip, or
+        [n][5] rows of draw_resized_crop_flip."""
         g = torch.Generator()
         g.manual_seed(self.base_seed)
-        return draw_crop_flip(self.n, self.transform, self.geometry[1:3], g, order=perm)
+        return (draw_resized_crop_flip if self._resized else draw_crop_flip)(self.n, self.transform, self.geometry[1:3], g, order=perm)
 
     def _augmented(self, perm):
         from . import ops
@@ -237,9 +346,10 @@ class DeviceLoader:
         params = self.epoch_params(perm).to(self.device)
         idx_host = torch.arange(self.n) if perm is None else perm
         idx = idx_host.to(self.device)
+        gather = ops.gather_tasks_resized_crop_flip if self._resized else ops.gather_tasks_crop_flip
         for s in range(0, self.n, self.batch_size):
             self.last_idx, self.last_idx_host = idx[s:s + self.batch_size], idx_host[s:s + self.batch_size]
-            yield ops.gather_tasks_crop_flip(self._table, self.geometry, idx[s:s + self.batch_size], params[s:s + self.batch_size])
+            yield gather(self._table, self.geometry, idx[s:s + self.batch_size], params[s:s + self.batch_size])
 
     def __iter__(self):
         perm = self.order()
@@ -294,8 +404,8 @@ class TaskList(Dataset):
 class MultiTaskLoader(DeviceLoader):
     """DeviceLoader over a TaskList: same length, order and consumption of the global RNG, but a batch is gathered straight
     out of the per-task tensors (clhip_gather_tasks) — the merged copy `ConcatTasks` makes (a second copy in HBM of every
-    task the cache already holds) is never built.  Tasks that carry a RandomCropFlip (all of equal size and p, or none) are
-    served augmented as DeviceLoader describes, the crop and flip done in the same gather."""
+    task the cache already holds) is never built.  Tasks that carry a RandomCropFlip or a RandomResizedCropFlip (all of one class and
+    equal parameters, or none) are served augmented as DeviceLoader describes, the crop and flip done in the same gather."""
 
     def __init__(self, dataset, batch_size, shuffle, device="cuda"):
         from . import ops

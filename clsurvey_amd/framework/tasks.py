@@ -13,17 +13,22 @@ from collections import OrderedDict
 
 import torch
 
-from ..data import RandomCropFlip, TensorTaskDataset, synthetic_task
+from ..data import RandomCropFlip, RandomResizedCropFlip, TensorTaskDataset, synthetic_task
 
 
 class SyntheticTaskSequence(object):
     def __init__(self, root, task_count=10, classes_per_task=20, sizes=(8000, 2000, 1000), hw=64, seed=7, noise=1.0,
-                 name="synthetic_tiny_imagenet", kind="protos", blobs=None, rnd_margin=0, rnd_always=False):
+                 name="synthetic_tiny_imagenet", kind="protos", blobs=None, rnd_margin=0, rnd_always=False, rnd_resized=0):
         """rnd_margin = m > 0: images are generated at (hw + m)^2; task_N.pth.tar holds their centre hw^2 crops (the Resize(256) /
         CenterCrop(224) of get_transforms(), data/inaturalist_dataprep.py:256-277) and task_N_rndtrans.pth.tar (named after
         data/dataset.py:108) the same images with the full frames + RandomCropFlip((hw, hw)) as `train` split.  rnd_always: the
         RecogSeq rule, get_task_dataset_path ignores its rnd_transform argument (data/dataset.py:458-466).  rnd_margin = 0:
-        every byte written and every path returned is what it was before the option existed."""
+        every byte written and every path returned is what it was before the option existed.
+        rnd_resized = m > 0 (instead of rnd_margin): the cropped Tiny-ImageNet variant (data/tinyimgnet_dataprep.py:105-122,
+        crop=True).  The same two files of the same images; the `train` split of task_N_rndtrans.pth.tar holds the full
+        (hw + m)^2 frames with RandomResizedCropFlip((hw, hw)) (RandomResizedCrop(56) of 64^2 images), every other split the
+        centre hw^2 crops (Resize(64) of a 64-pixel image is the identity, then CenterCrop(56)).  0: as if the option did
+        not exist."""
         self.name = name
         self.argname = name
         self.test_results_dir = name
@@ -42,8 +47,11 @@ class SyntheticTaskSequence(object):
         self.n_classes = classes_per_task
         self.rnd_margin = int(rnd_margin)
         self.rnd_always = bool(rnd_always)
-        if self.rnd_margin < 0:
-            raise ValueError("SyntheticTaskSequence: rnd_margin >= 0")
+        self.rnd_resized = int(rnd_resized)
+        if self.rnd_margin < 0 or self.rnd_resized < 0:
+            raise ValueError("SyntheticTaskSequence: rnd_margin >= 0 and rnd_resized >= 0")
+        if self.rnd_margin and self.rnd_resized:
+            raise ValueError("SyntheticTaskSequence: rnd_margin or rnd_resized, not both")
 
     def get_taskname(self, task_index):
         return str(task_index)
@@ -55,14 +63,16 @@ class SyntheticTaskSequence(object):
                "blobs": None if self.blobs is None else {k: float(v) for k, v in sorted(dict(self.blobs).items())}}
         if self.rnd_margin:
             out["rnd_margin"] = self.rnd_margin
-            if rnd_transform:
-                out["rnd_transform"] = True
+        if self.rnd_resized:
+            out["rnd_resized"] = self.rnd_resized
+        if (self.rnd_margin or self.rnd_resized) and rnd_transform:
+            out["rnd_transform"] = True
         return out
 
     def _make(self, task_name, rnd_transform):
         """The {'train', 'val', 'test'} dict of one file."""
         want = self.spec(task_name)
-        m = self.rnd_margin
+        m = self.rnd_margin or self.rnd_resized
         d = synthetic_task(self.sizes[0], self.sizes[1], self.sizes[2], self.n_classes, self.hw + m,
                            seed=want["seed"], noise=self.noise, kind=self.kind, blobs=self.blobs)
         if not m:
@@ -71,7 +81,7 @@ class SyntheticTaskSequence(object):
         out = {s: TensorTaskDataset(v.x[:, :, o:o + self.hw, o:o + self.hw], v.y, v.classes) for s, v in d.items()}
         if rnd_transform:
             out["train"] = TensorTaskDataset(d["train"].x, d["train"].y, d["train"].classes,
-                                             transform=RandomCropFlip((self.hw, self.hw)))
+                                             transform=(RandomResizedCropFlip if self.rnd_resized else RandomCropFlip)((self.hw, self.hw)))
         return out
 
     def get_task_dataset_path(self, task_name=None, rnd_transform=False):
@@ -79,10 +89,10 @@ class SyntheticTaskSequence(object):
         file of ANOTHER spec (other kind / blobs / noise / sizes / seed under the same results root) is an error, not a hit:
         the results tree beside it holds success tokens and models of that other data.
         task_name=None asks for a pre-merged file of ALL tasks (Joint.grid_datafetch, method.py:1204): there is none.
-        With a margin, rnd_transform (or rnd_always) selects task_N_rndtrans.pth.tar, which has its own sidecar."""
+        With a margin (rnd_margin or rnd_resized), rnd_transform (or rnd_always) selects task_N_rndtrans.pth.tar, which has its own sidecar."""
         if task_name is None:
             return None
-        rnd = bool(self.rnd_margin) and (bool(rnd_transform) or self.rnd_always)
+        rnd = bool(self.rnd_margin or self.rnd_resized) and (bool(rnd_transform) or self.rnd_always)
         stem = "task_%s%s" % (task_name, "_rndtrans" if rnd else "")
         path = os.path.join(self.root, self.name, stem + ".pth.tar")
         side = os.path.join(self.root, self.name, stem + ".spec.json")

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 from ..data import load_task_datasets
 
-from ..data import DeviceLoader
+from ..data import DeviceLoader, RandomResizedCropFlip
 from .exemplar import batch_source
 from . import gem as G
 from . import rehearsal as R
@@ -164,6 +164,10 @@ def main(overwrite_args, nc_per_task, device="cuda"):
 
     dsets = load_task_datasets(args.dataset_path)
     args.task_imgfolders = dsets
+    if isinstance(getattr(dsets["train"], "transform", None), RandomResizedCropFlip):
+        # the exemplar wrappers replay stored frames through clhip_rehearsal_assemble_crop_flip, which does not resample
+        raise NotImplementedError("rehearsal method %r: exemplars are replayed with RandomCropFlip only, the train split carries %r"
+                                  % (args.method, dsets["train"].transform))
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}
     in_shape = tuple(args.dset_loaders["train"].x.shape[1:])

@@ -816,6 +816,33 @@ def gather_tasks_crop_flip(table, geometry, idx, params, x_out=None, labels_out=
     return x_out, labels_out
 
 
+RESIZE_MAX_RATIO = 8          # CLHIP_RESIZE_MAX_RATIO (include/clhip.h): the largest shrink ratio of a resized window
+
+
+def gather_tasks_resized_crop_flip(table, geometry, idx, params, x_out=None, labels_out=None):
+    """clhip_gather_tasks_resized_crop_flip: geometry = (C, Hs, Ws, th, tw) of the stored frames and of the output, idx device
+    int64[B] GLOBAL sample numbers, params device int32[B, 5] of (top, left, h, w, flip) per batch position, both checked by the
+    caller.  Returns (x_out [B, C, th, tw], labels_out [B])."""
+    _chk(table, idx, params, x_out, labels_out)
+    C, Hs, Ws, th, tw = (int(v) for v in geometry)
+    assert idx.dtype == torch.int64 and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 4
+    B = idx.shape[0]
+    assert params.dtype == torch.int32 and tuple(params.shape) == (B, 5) and params.is_contiguous()
+    if x_out is None:
+        x_out = torch.empty((B, C, th, tw), dtype=torch.float32, device=idx.device)
+    if labels_out is None:
+        labels_out = torch.empty((B,), dtype=torch.int64, device=idx.device)
+    row_elems = C * th * tw
+    assert x_out.numel() >= B * row_elems and labels_out.numel() >= B
+    xf, step = x_out.view(-1), 65535                     # one launch takes at most 65535 rows (grid y): larger batches in pieces
+    for s in range(0, max(B, 1), step):
+        n = min(step, B - s)
+        check(_lib.lib().clhip_gather_tasks_resized_crop_flip(_ptr(table), table.shape[0], C, Hs, Ws, th, tw, _ptr(idx[s:s + n]),
+                                                              _ptr(params[s:s + n]), n, _ptr(xf[s * row_elems:]),
+                                                              _ptr(labels_out[s:]), _stream()), "clhip_gather_tasks_resized_crop_flip")
+    return x_out, labels_out
+
+
 def rehearsal_assemble_crop_flip(geometry, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows, gather, params,
                                  x_mix, y_mix):
     """clhip_rehearsal_assemble_crop_flip: geometry = (C, Hs, Ws, th, tw); store [rows, C, Hs, Ws] frames, x / x_mix rows

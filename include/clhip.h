@@ -584,6 +584,46 @@ int clhip_slice_argmax_count(const float* logits, int N, int ld, const int* cols
 int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const int64_t* idx,
                                  const int* params, int B, float* x_out, int64_t* labels_out, void* stream);
 
+/* data/tinyimgnet_dataprep.py:105-122 (the `train` split of the cropped Tiny-ImageNet variant: RandomResizedCrop(56) ->
+ * RandomHorizontalFlip -> ToTensor -> Normalize on 64 x 64 images; also the standard ImageNet training augmentation).
+ *
+ *   gather_tasks_resized_crop_flip   clhip_gather_tasks_crop_flip with a window that is RESIZED: params is device int32[B][5] of
+ *                            (top, left, h, w, flip), the h x w window of the stored frame [C][Hs][Ws] whose top-left corner is
+ *                            (top, left); x_out is [B][C][th][tw] and
+ *                              x_out[b][c][y][x] = sum_j sum_i Wy[y][j] Wx[x'][i] frame(idx[b])[c][top + j][left + i]
+ *                              x' = flip ? tw - 1 - x : x                 (torchvision's crop, resize, then hflip)
+ *                            W is the antialiased bilinear filter of torchvision's tensor resized_crop(antialias=True), ATen's
+ *                            _upsample_bilinear2d_aa with align_corners = False.  Per axis, n_in the window's and n_out the
+ *                            output's extent:
+ *                              scale = n_in / n_out     sup = max(scale, 1)     c = scale (i_out + 0.5)
+ *                              lo = max(0, int(c - sup + 0.5))     hi = min(n_in, int(c + sup + 0.5))
+ *                              w_j = max(0, 1 - |(j - c + 0.5) / sup|) for j in [lo, hi), normalised to sum 1
+ *                            at most ceil(2 sup) + 1 taps.  The weights are computed on the device in fp32 from the integers.
+ *                            Summation order (fixed: two runs are bitwise equal): the horizontal pass first, one fp32 value per
+ *                            (source line, output column), then the vertical pass; each accumulates by fp32 fused multiply-add
+ *                            over its taps in ascending source index, starting from -0.0f, and skips a tap whose weight is
+ *                            exactly 0.  A window with h == th and w == tw has one tap of weight exactly 1 per axis: the result
+ *                            is then bitwise that of clhip_gather_tasks_crop_flip for (top, left, flip).
+ *                            Difference from the reference: PIL resizes the uint8 image and rounds to uint8 before Normalize;
+ *                            here the stored normalised floats are resampled, so a value can differ by up to half a grey level
+ *                            divided by the channel's std (0.5 / 255 / std).
+ *                            A row copies nothing and writes label -1 when its sample number is outside [0, cum_rows[T-1]),
+ *                            h < 1, w < 1, top < 0, left < 0, top + h > Hs, left + w > Ws, flip is outside {0, 1}, or
+ *                            h > CLHIP_RESIZE_MAX_RATIO th or w > CLHIP_RESIZE_MAX_RATIO tw; no address outside the source
+ *                            frame is formed.  CLHIP_EINVAL before any launch: the checks of clhip_gather_tasks_crop_flip
+ *                            except th > Hs and tw > Ws (a window may be enlarged: 5 x 7 -> 8 x 8), and Hs < 1 or Ws < 1.
+ *                            CLHIP_ENOTSUP: the source band of ONE output line at the largest window the frame allows, with
+ *                            s = min(Hs / th, CLHIP_RESIZE_MAX_RATIO) about 2 max(s, 1) + 3 lines of
+ *                            min(Ws, CLHIP_RESIZE_MAX_RATIO tw) + tw floats, and the tap tables do not fit 64 KB of LDS (the plan is
+ *                            made for the frame, not for the windows of one batch): 512 -> 64 is served, 1000 -> 125 is not.
+ *                            B == 0 returns 0.  float4 stores when tw % 4 == 0 and x_out is 16-byte aligned; dword loads.
+ * CLHIP_RESIZE_MAX_RATIO: the largest supported shrink ratio max(h / th, w / tw) of a window (17 taps per axis; 64 -> 8 and
+ * 256 -> 56 with room).  It bounds the LDS a block needs for its source band and its tap tables. */
+#define CLHIP_RESIZE_MAX_RATIO 8
+int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,
+                                         const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out,
+                                         void* stream);
+
 /* ------------------------------------------------------------------ iCaRL
  * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471) and the nearest-mean-of-exemplars classifier of
  * Net.forward (:142-186); the loss of update_representation (:482-598) over one mixed batch is clhip_loss_segments above.
