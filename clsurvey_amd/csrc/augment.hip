@@ -8,10 +8,17 @@
 //   gather_tasks_resized_crop_flip   one (top, left, h, w, flip) per batch position: the h x w window of the frame resized to
 //                            th x tw by the antialiased bilinear filter of ATen's _upsample_bilinear2d_aa (align_corners =
 //                            False), then mirrored.  Separable: lines first, then columns, fp32, taps in ascending source order.
+// Both also serve BYTE frames (the ..._u8 entries; TS = clhip_task_src_u8): a stored byte v of channel c means lut[c][v], the
+// ToTensor -> Normalize of the reference's Compose as a table the host computed.  The block's channel of the table is staged in
+// LDS and every source element is decoded where it is loaded; everything after the load is the fp32 code, so the result is
+// bitwise the fp32 entry's on the decoded frames.
 #include "crop_flip.hpp"
 #include <math.h>
+#include <type_traits>
 
 namespace {
+
+template <typename TS> constexpr bool ts_u8 = std::is_same<TS, clhip_task_src_u8>::value;
 
 // blockIdx.y = batch position.  blockIdx.x = (channel, chunk of `rpb` output lines): the block's destination is one contiguous
 // run of nrows * tw floats, its source a nrows x tw window of one channel plane, copied by cf_copy_window (crop_flip.hpp).
@@ -20,9 +27,10 @@ namespace {
 // A sample number outside [0, total), top outside [0, Hs - th], left outside [0, Ws - tw] or flip outside {0, 1} copies nothing
 // and writes label -1: no address outside the source frame is ever formed (the host draws valid tables; this only keeps a bad
 // one from faulting).
-template <bool VEC>
-__global__ __launch_bounds__(CF_BLOCK) void gather_crop_flip_kernel(const clhip_task_src* __restrict__ tasks, int T, int C, int Hs,
+template <bool VEC, typename TS>
+__global__ __launch_bounds__(CF_BLOCK) void gather_crop_flip_kernel(const TS* __restrict__ tasks, int T, int C, int Hs,
                                                                      int Ws, int th, int tw, int rpb, int chunks,
+                                                                     const float* __restrict__ lut,
                                                                      const int64_t* __restrict__ idx, const int* __restrict__ params,
                                                                      float* __restrict__ x_out, int64_t* __restrict__ labels_out) {
     const int r = blockIdx.y;
@@ -40,11 +48,20 @@ __global__ __launch_bounds__(CF_BLOCK) void gather_crop_flip_kernel(const clhip_
     const int c = (int)blockIdx.x / chunks;
     const int y0 = ((int)blockIdx.x - c * chunks) * rpb;
     const int nrows = min(rpb, th - y0);
-    // (a pointer read out of the table is generic to the compiler; it is device memory, so say so: global_load, not flat_load)
-    typedef const float __attribute__((address_space(1))) gfloat;
-    gfloat* src = (gfloat*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws + (size_t)(top + y0) * Ws + left);
     float* dst = x_out + (((size_t)r * C + c) * th + y0) * tw;
-    cf_copy_window<VEC>(src, Ws, dst, (unsigned)nrows * (unsigned)tw, tw, flip);      // total <= max(CF_SEG, tw) < 2^31
+    // (a pointer read out of the table is generic to the compiler; it is device memory, so say so: global_load, not flat_load)
+    if constexpr (ts_u8<TS>) {
+        __shared__ float lut_s[256];                                        // the table of channel c (CF_BLOCK == 256: one entry each)
+        lut_s[threadIdx.x] = lut[c * 256 + (int)threadIdx.x];
+        __syncthreads();
+        typedef const uint8_t __attribute__((address_space(1))) gbyte;
+        gbyte* src = (gbyte*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws + (size_t)(top + y0) * Ws + left);
+        cf_copy_window<VEC>(src, Ws, dst, (unsigned)nrows * (unsigned)tw, tw, flip, cf_load_u8{lut_s});
+    } else {
+        typedef const float __attribute__((address_space(1))) gfloat;
+        gfloat* src = (gfloat*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws + (size_t)(top + y0) * Ws + left);
+        cf_copy_window<VEC>(src, Ws, dst, (unsigned)nrows * (unsigned)tw, tw, flip);  // total <= max(CF_SEG, tw) < 2^31
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- resized crop
@@ -58,7 +75,8 @@ struct rz_plan { int rpb, chunks, nb, wmax, ktx, kty; size_t lds; };
 
 static inline int rz_align4(int v) { return (v + 3) & ~3; }
 
-static bool rz_make_plan(int Hs, int Ws, int th, int tw, rz_plan* p) {
+// `extra`: LDS bytes the block takes besides (the byte entry's table).
+static bool rz_make_plan(int Hs, int Ws, int th, int tw, size_t extra, rz_plan* p) {
     const double R = CLHIP_RESIZE_MAX_RATIO;
     const double sy = fmin((double)Hs / th, R), sx = fmin((double)Ws / tw, R);
     p->kty = (int)ceil(2.0 * fmax(sy, 1.0)) + 1;
@@ -68,7 +86,7 @@ static bool rz_make_plan(int Hs, int Ws, int th, int tw, rz_plan* p) {
         const double span = ceil(sy * (rpb - 1) + 2.0 * fmax(sy, 1.0)) + 3.0;
         const int nb = (int)fmin((double)Hs, span);
         const size_t floats = (size_t)rz_align4(nb * p->wmax) + (size_t)nb * tw + (size_t)p->ktx * tw + (size_t)p->kty * rpb;
-        const size_t bytes = 4 * (floats + (size_t)tw + 2 * (size_t)rpb);
+        const size_t bytes = 4 * (floats + (size_t)tw + 2 * (size_t)rpb) + extra;
         if (bytes <= (size_t)RZ_LDS_AIM || (rpb == 1 && bytes <= (size_t)RZ_LDS_MAX)) {
             p->rpb = rpb;
             p->chunks = (th + rpb - 1) / rpb;
@@ -103,7 +121,8 @@ __device__ __forceinline__ void rz_taps(int o, int n_in, int n_out, int KT, floa
 //   0. the taps of its output lines and of all tw output columns (of column tw - 1 - x under a flip: everything after this is
 //      flip-agnostic), computed on the device into LDS: wx[k][x], wy[k][line] (lanes along x / along the line: no bank conflicts)
 //   1. the source band (the lines its output lines tap, all w columns of the window) global -> LDS, lanes along the source line,
-//      dword loads (a line starts anywhere)
+//      dword loads (a line starts anywhere); byte frames: byte loads, decoded here through the channel's table (staged in LDS
+//      in step 0), so raw[] holds what it holds for the decoded frames
 //   2. the horizontal pass LDS -> LDS, once per source line of the band: tmp[j][x] = sum_k wx[k][x] raw[j][xlo[x] + k]
 //   3. the vertical pass: out[y][x] = sum_k wy[k][y] tmp[ylo[y] - jlo + k][x], lanes along the output line, float4 when VEC
 // SUMMATION ORDER (fixed; two runs are bitwise equal): both passes accumulate in fp32 by fmaf over the taps in ascending source
@@ -111,10 +130,11 @@ __device__ __forceinline__ void rz_taps(int o, int n_in, int n_out, int KT, floa
 // skipped, so nothing outside the support of the filter takes part (no 0 * inf).  A window of the output's size has one tap of
 // weight exactly 1 per axis: the result is then the source value, bitwise.
 // Rows the header lists as bad copy nothing and write label -1; no address outside the source frame is formed.
-template <bool VEC>
-__global__ __launch_bounds__(CF_BLOCK) void gather_resized_kernel(const clhip_task_src* __restrict__ tasks, int T, int C, int Hs, int Ws,
+template <bool VEC, typename TS>
+__global__ __launch_bounds__(CF_BLOCK) void gather_resized_kernel(const TS* __restrict__ tasks, int T, int C, int Hs, int Ws,
                                                                    int th, int tw, int rpb, int chunks, int nb, int wmax, int ktx_max,
-                                                                   int kty_max, const int64_t* __restrict__ idx,
+                                                                   int kty_max, const float* __restrict__ lut,
+                                                                   const int64_t* __restrict__ idx,
                                                                    const int* __restrict__ params, float* __restrict__ x_out,
                                                                    int64_t* __restrict__ labels_out) {
     extern __shared__ __attribute__((aligned(16))) float rz_lds[];
@@ -143,6 +163,8 @@ __global__ __launch_bounds__(CF_BLOCK) void gather_resized_kernel(const clhip_ta
     int* xlo = reinterpret_cast<int*>(wy + kty_max * rpb);
     int* ylo = xlo + tw;
     int* yhi = ylo + rpb;
+    float* lut_s = reinterpret_cast<float*>(yhi + rpb);   // [256], byte frames only (the plan's `extra`)
+    if constexpr (ts_u8<TS>) lut_s[tid] = lut[c * 256 + tid];              // (CF_BLOCK == 256: one entry each)
     // taps this window needs (block-uniform; <= the plan's, which is made for the largest window)
     const int ktx = min(ktx_max, (int)ceilf(2.0f * fmaxf((float)w / (float)tw, 1.0f)) + 1);
     const int kty = min(kty_max, (int)ceilf(2.0f * fmaxf((float)h / (float)th, 1.0f)) + 1);
@@ -163,14 +185,15 @@ __global__ __launch_bounds__(CF_BLOCK) void gather_resized_kernel(const clhip_ta
     const int band = min(yhi[nrows - 1] - jlo, nb);
 
     // (a pointer read out of the table is generic to the compiler; it is device memory, so say so: global_load, not flat_load)
-    typedef const float __attribute__((address_space(1))) gfloat;
-    gfloat* src = (gfloat*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws + (size_t)(top + jlo) * Ws + left);
+    typedef typename std::conditional<ts_u8<TS>, const uint8_t, const float>::type __attribute__((address_space(1))) gelem;
+    gelem* src = (gelem*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws + (size_t)(top + jlo) * Ws + left);
     {
         const int q = CF_BLOCK / w, rem = CF_BLOCK % w, total = band * w;  // a thread divides once, then steps (crop_flip.hpp)
         int j = tid / w, i = tid - j * w;
 #pragma unroll 4
         for (int e = tid; e < total; e += CF_BLOCK) {
-            raw[e] = src[(size_t)j * Ws + i];
+            if constexpr (ts_u8<TS>) raw[e] = lut_s[src[(size_t)j * Ws + i]];
+            else raw[e] = src[(size_t)j * Ws + i];
             i += rem;
             j += q;
             if (i >= w) { i -= w; ++j; }
@@ -232,11 +255,12 @@ __global__ __launch_bounds__(CF_BLOCK) void gather_resized_kernel(const clhip_ta
 
 }  // namespace
 
-extern "C" {
-
-int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const int64_t* idx,
-                                 const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
+// One body per pair of entries: TS selects the frames' element type, lut is NULL for floats.
+template <typename TS>
+static int gather_crop_flip(const TS* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const float* lut, const int64_t* idx,
+                            const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
     if (!tasks_dev || T < 1 || T > CLHIP_MAX_TASKS || C < 1 || th < 1 || tw < 1 || th > Hs || tw > Ws || B < 0) return CLHIP_EINVAL;
+    if (ts_u8<TS> && !lut) return CLHIP_EINVAL;
     if (B == 0) return 0;
     if (!idx || !params || !x_out || !labels_out || B > 65535) return CLHIP_EINVAL;
     const int rpb = cf_rows_per_block(tw);
@@ -244,33 +268,58 @@ int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, 
     if ((size_t)C * chunks > 0x7fffffffull) return CLHIP_EINVAL;
     const dim3 grid((unsigned)(C * chunks), (unsigned)B);
     if (tw % 4 == 0 && aligned16(x_out))
-        hipLaunchKernelGGL(gather_crop_flip_kernel<true>, grid, dim3(CF_BLOCK), 0, as_stream(stream), tasks_dev, T, C, Hs, Ws, th, tw,
-                           rpb, chunks, idx, params, x_out, labels_out);
+        hipLaunchKernelGGL((gather_crop_flip_kernel<true, TS>), grid, dim3(CF_BLOCK), 0, as_stream(stream), tasks_dev, T, C, Hs, Ws,
+                           th, tw, rpb, chunks, lut, idx, params, x_out, labels_out);
     else
-        hipLaunchKernelGGL(gather_crop_flip_kernel<false>, grid, dim3(CF_BLOCK), 0, as_stream(stream), tasks_dev, T, C, Hs, Ws, th, tw,
-                           rpb, chunks, idx, params, x_out, labels_out);
+        hipLaunchKernelGGL((gather_crop_flip_kernel<false, TS>), grid, dim3(CF_BLOCK), 0, as_stream(stream), tasks_dev, T, C, Hs, Ws,
+                           th, tw, rpb, chunks, lut, idx, params, x_out, labels_out);
     CLHIP_LAUNCH_CHECK();
     return 0;
 }
 
-int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,
-                                         const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
+template <typename TS>
+static int gather_resized(const TS* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const float* lut, const int64_t* idx,
+                          const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
     // (an output larger than the frame is an enlargement here, not an error)
     if (!tasks_dev || T < 1 || T > CLHIP_MAX_TASKS || C < 1 || Hs < 1 || Ws < 1 || th < 1 || tw < 1 || B < 0) return CLHIP_EINVAL;
+    if (ts_u8<TS> && !lut) return CLHIP_EINVAL;
     if (B == 0) return 0;
     if (!idx || !params || !x_out || !labels_out || B > 65535) return CLHIP_EINVAL;
     rz_plan p;
-    if (!rz_make_plan(Hs, Ws, th, tw, &p)) return CLHIP_ENOTSUP;              // one output line's band does not fit the LDS
+    if (!rz_make_plan(Hs, Ws, th, tw, ts_u8<TS> ? 256 * sizeof(float) : 0, &p)) return CLHIP_ENOTSUP;   // one output line's band does not fit the LDS
     if ((size_t)C * p.chunks > 0x7fffffffull) return CLHIP_EINVAL;
     const dim3 grid((unsigned)(C * p.chunks), (unsigned)B);
     if (tw % 4 == 0 && aligned16(x_out))
-        hipLaunchKernelGGL(gather_resized_kernel<true>, grid, dim3(CF_BLOCK), p.lds, as_stream(stream), tasks_dev, T, C, Hs, Ws, th, tw,
-                           p.rpb, p.chunks, p.nb, p.wmax, p.ktx, p.kty, idx, params, x_out, labels_out);
+        hipLaunchKernelGGL((gather_resized_kernel<true, TS>), grid, dim3(CF_BLOCK), p.lds, as_stream(stream), tasks_dev, T, C, Hs, Ws,
+                           th, tw, p.rpb, p.chunks, p.nb, p.wmax, p.ktx, p.kty, lut, idx, params, x_out, labels_out);
     else
-        hipLaunchKernelGGL(gather_resized_kernel<false>, grid, dim3(CF_BLOCK), p.lds, as_stream(stream), tasks_dev, T, C, Hs, Ws, th, tw,
-                           p.rpb, p.chunks, p.nb, p.wmax, p.ktx, p.kty, idx, params, x_out, labels_out);
+        hipLaunchKernelGGL((gather_resized_kernel<false, TS>), grid, dim3(CF_BLOCK), p.lds, as_stream(stream), tasks_dev, T, C, Hs, Ws,
+                           th, tw, p.rpb, p.chunks, p.nb, p.wmax, p.ktx, p.kty, lut, idx, params, x_out, labels_out);
     CLHIP_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" {
+
+int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const int64_t* idx,
+                                 const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
+    return gather_crop_flip(tasks_dev, T, C, Hs, Ws, th, tw, nullptr, idx, params, B, x_out, labels_out, stream);
+}
+
+int clhip_gather_tasks_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const float* lut,
+                                    const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
+    return gather_crop_flip(tasks_dev, T, C, Hs, Ws, th, tw, lut, idx, params, B, x_out, labels_out, stream);
+}
+
+int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,
+                                         const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
+    return gather_resized(tasks_dev, T, C, Hs, Ws, th, tw, nullptr, idx, params, B, x_out, labels_out, stream);
+}
+
+int clhip_gather_tasks_resized_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,
+                                            const float* lut, const int64_t* idx, const int* params, int B, float* x_out,
+                                            int64_t* labels_out, void* stream) {
+    return gather_resized(tasks_dev, T, C, Hs, Ws, th, tw, lut, idx, params, B, x_out, labels_out, stream);
 }
 
 }  // extern "C"

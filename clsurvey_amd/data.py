@@ -14,6 +14,10 @@ A split may carry a `RandomCropFlip` spec (the `train` split of a RecogSeq task,
 its stored frames stay static in HBM and the loaders crop and mirror them inside the gather that assembles each batch
 (clhip_gather_tasks_crop_flip), a fresh draw per sample per epoch.  A `RandomResizedCropFlip` spec (the `train` split of the
 cropped Tiny-ImageNet variant) is served the same way by the gather that resamples (clhip_gather_tasks_resized_crop_flip).
+
+A split may also hold its frames as the decoded uint8 images (`ByteTaskDataset`): ToTensor -> Normalize, the last step of every
+Compose of the reference, then happens inside the same gathers through a 256-entry table per channel (the ..._u8 entries of
+include/clhip.h), and the batches are bitwise those of the fp32 split `.decoded()` returns.
 """
 import math
 
@@ -179,9 +183,32 @@ def _transform_of(dataset):
     return t if isinstance(t, (RandomCropFlip, RandomResizedCropFlip)) else None
 
 
+def norm_lut(mean, std):
+    """CPU fp32 [C][256], the meaning of a byte per channel: ToTensor (uint8 -> float, / 255) then Normalize (- mean, / std),
+    op for op as torchvision does them, of all 256 byte values."""
+    return (torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)[None, :] - mean[:, None]) / std[:, None]
+
+
+def merged_norm(dsets):
+    """(mean, std) of several tasks served as one dataset when they hold byte frames, None when they hold floats.  All are
+    ByteTaskDatasets with equal mean and std, or none is: anything else is a ValueError (one table decodes a batch)."""
+    dsets = list(dsets)
+    byte = [isinstance(d, ByteTaskDataset) for d in dsets]
+    if not any(byte):
+        return None
+    if not all(byte):
+        raise ValueError("tasks served as one dataset all hold byte frames or all hold floats: %s" % [type(d).__name__ for d in dsets])
+    mean, std = dsets[0].mean, dsets[0].std
+    if any(not (torch.equal(d.mean, mean) and torch.equal(d.std, std)) for d in dsets):
+        raise ValueError("byte tasks served as one dataset share mean and std: %s" % [(d.mean.tolist(), d.std.tolist()) for d in dsets])
+    return mean, std
+
+
 def merged_transform(dsets):
     """One spec for several tasks served as one dataset: all carry a spec of one class with equal parameters (extents
-    concatenated in task order, a task without them counts as full frames), or none carries a transform."""
+    concatenated in task order, a task without them counts as full frames), or none carries a transform.  The tasks also
+    agree on how their frames are stored (merged_norm)."""
+    merged_norm(dsets)
     ts = [_transform_of(d) for d in dsets]
     if all(t is None for t in ts):
         return None
@@ -205,6 +232,9 @@ class TensorTaskDataset(Dataset):
         self.x = x.contiguous().float()
         self.y = y.contiguous().long()
         self.classes = list(classes)
+        self._set_transform(transform)
+
+    def _set_transform(self, transform):
         if transform is not None:
             if not isinstance(transform, (RandomCropFlip, RandomResizedCropFlip)):
                 raise TypeError("TensorTaskDataset: transform is None or a RandomCropFlip")
@@ -217,6 +247,45 @@ class TensorTaskDataset(Dataset):
 
     def __getitem__(self, i):
         return self.x[i], self.y[i]
+
+
+class ByteTaskDataset(TensorTaskDataset):
+    """A split whose frames stay the decoded uint8 images [n][C][H][W], with the per-channel `mean` and `std` of the
+    reference's Normalize.  It MEANS the fp32 split of lut()[c][x]: the loaders decode inside their gathers (a quarter of the
+    bytes in HBM, in the task cache and on the source side of every gather) and serve, bitwise, what they serve for
+    `decoded()`.  `.x` and `dataset[i]` stay bytes: code that reads frames directly goes through `decoded()`."""
+
+    def __init__(self, x_u8, y, classes, mean, std, transform=None):
+        if not torch.is_tensor(x_u8) or x_u8.dtype != torch.uint8:
+            raise TypeError("ByteTaskDataset: frames are a uint8 tensor, got %s" % (getattr(x_u8, "dtype", type(x_u8)),))
+        if x_u8.dim() != 4:
+            raise ValueError("ByteTaskDataset: frames [n, C, H, W], got %s" % (tuple(x_u8.shape),))
+        assert x_u8.shape[0] == y.shape[0]
+        mean = torch.as_tensor(mean, dtype=torch.float32).detach().cpu().reshape(-1).clone()
+        std = torch.as_tensor(std, dtype=torch.float32).detach().cpu().reshape(-1).clone()
+        C = int(x_u8.shape[1])
+        if mean.numel() != C or std.numel() != C:
+            raise ValueError("ByteTaskDataset: %d channels, %d means, %d stds" % (C, mean.numel(), std.numel()))
+        if not bool(torch.isfinite(mean).all()) or not bool(torch.isfinite(std).all()) or not bool((std > 0).all()):
+            raise ValueError("ByteTaskDataset: mean finite, std finite and > 0, got %s, %s" % (mean.tolist(), std.tolist()))
+        self.x = x_u8.contiguous()
+        self.y = y.contiguous().long()
+        self.classes = list(classes)
+        self.mean, self.std = mean, std
+        self._set_transform(transform)
+
+    def lut(self):
+        """CPU fp32 [C][256]: the table the loaders decode through (norm_lut)."""
+        return norm_lut(self.mean, self.std)
+
+    def decoded(self):
+        """The equivalent TensorTaskDataset (same labels, classes and transform), frames looked up in lut()."""
+        lut = self.lut().to(self.x.device)
+        x = torch.empty(self.x.shape, dtype=torch.float32, device=self.x.device)
+        for c in range(self.x.shape[1]):
+            plane = self.x[:, c]
+            x[:, c] = lut[c].index_select(0, plane.reshape(-1).int()).view(plane.shape)
+        return TensorTaskDataset(x, self.y, self.classes, transform=self.transform)
 
 
 _TASK_CACHE = {}          # (path, mtime_ns, size, device) -> {'train' / 'val' / 'test': TensorTaskDataset in HBM}
@@ -242,16 +311,24 @@ def load_task_datasets(dataset_path, device="cuda"):
     out, nbytes = {}, 0
     for split, dset in dsets.items():
         x, y = _extract(dset)
-        out[split] = TensorTaskDataset(x.to(device), y.to(device), getattr(dset, "classes", []), transform=_transform_of(dset))
-        nbytes += x.numel() * 4 + y.numel() * 8
+        if isinstance(dset, ByteTaskDataset):
+            out[split] = ByteTaskDataset(x.to(device), y.to(device), dset.classes, dset.mean, dset.std, transform=_transform_of(dset))
+        else:
+            out[split] = TensorTaskDataset(x.to(device), y.to(device), getattr(dset, "classes", []), transform=_transform_of(dset))
+        nbytes += _split_bytes(out[split])
     limit = float(os.environ.get("CLHIP_DATA_CACHE_GB", "64")) * 2 ** 30
     while _TASK_CACHE and _TASK_CACHE_BYTES[0] + nbytes > limit:
         old = next(iter(_TASK_CACHE))
-        _TASK_CACHE_BYTES[0] -= sum(d.x.numel() * 4 + d.y.numel() * 8 for d in _TASK_CACHE.pop(old).values())
+        _TASK_CACHE_BYTES[0] -= sum(_split_bytes(d) for d in _TASK_CACHE.pop(old).values())
     if nbytes <= limit:
         _TASK_CACHE[key] = out
         _TASK_CACHE_BYTES[0] += nbytes
     return out
+
+
+def _split_bytes(d):
+    """What a cached split holds in HBM (fp32 frames: 4 bytes an element, byte frames: 1)."""
+    return d.x.numel() * d.x.element_size() + d.y.numel() * 8
 
 
 def _extract(dataset):
@@ -280,10 +357,17 @@ class DeviceLoader:
     in frame mode stores instead of the crop (methods/exemplar.py: the counterpart of the reference's `paths`).  Difference from
     the reference: its draws happen in DataLoader worker processes (see draw_crop_flip).
     A RandomResizedCropFlip is served by the same steps: the table holds (top, left, h, w, flip) rows from
-    draw_resized_crop_flip and the launch is clhip_gather_tasks_resized_crop_flip."""
+    draw_resized_crop_flip and the launch is clhip_gather_tasks_resized_crop_flip.
+    A ByteTaskDataset is ALWAYS served through a gather, with or without a transform (the ..._u8 entry of the gather the fp32
+    split would take; clhip_gather_tasks_u8 with idx = arange when there is neither a transform nor a shuffle): `.x`, `.frames`,
+    `last_idx` and `last_idx_host` behave as in augmented mode, `.transform` stays what the dataset carries.  The table of the
+    byte values is uploaded once per loader.  Batches, labels and the consumption of the generators are those of the loader
+    over `dataset.decoded()`."""
 
     transform = None
     _resized = False
+    _norm = None              # (mean, std) of byte frames
+    _lut = None
     base_seed = None
     last_idx = last_idx_host = None
 
@@ -297,8 +381,21 @@ class DeviceLoader:
         self.y = y.to(self.device)
         self.n = self.x.shape[0]
         transform = _transform_of(dataset)
+        self._norm = merged_norm([dataset])
         if transform is not None:
             self._augment(transform, [self.x], [self.y], [self.n], [0])
+        elif self._norm is not None:
+            self._serve_bytes([self.x], [self.y], [self.n], [0])
+
+    def _serve_bytes(self, xs, ys, cum_rows, label_shifts):
+        """Serve the byte frames xs (one tensor per task) without a transform: decoded by the plain gather."""
+        if any(tuple(v.shape[1:]) != tuple(xs[0].shape[1:]) for v in xs):
+            raise ValueError("byte tasks of one sequence share the frame shape")
+        self.frames = xs
+        self.row_shape = tuple(int(v) for v in xs[0].shape[1:])
+        self.x = torch.empty((0,) + self.row_shape, dtype=torch.float32, device=xs[0].device)
+        self._sources = (xs, ys, list(cum_rows), list(label_shifts))
+        self._table = None
 
     def _augment(self, transform, xs, ys, cum_rows, label_shifts):
         """Serve `transform` of the frames xs (one tensor per task)."""
@@ -314,7 +411,7 @@ class DeviceLoader:
         self._resized = isinstance(transform, RandomResizedCropFlip)
         self.frames = xs
         self.geometry = (C, Hs, Ws, th, tw)
-        self.x = xs[0].new_empty((0, C, th, tw))    # (row shape only: what engine_for reads; no memory)
+        self.x = torch.empty((0, C, th, tw), dtype=torch.float32, device=xs[0].device)    # (row shape only: what engine_for reads; no memory)
         self._sources = (xs, ys, list(cum_rows), list(label_shifts))
         self._table = None                          # device table, built at the first epoch (order() alone needs no device)
 
@@ -343,17 +440,26 @@ class DeviceLoader:
         from . import ops
         if self._table is None:
             self._table = ops.task_table(*self._sources, self.device)
-        params = self.epoch_params(perm).to(self.device)
+            if self._norm is not None:
+                self._lut = norm_lut(*self._norm).to(self.device)
+        params = self.epoch_params(perm).to(self.device) if self.transform is not None else None
         idx_host = torch.arange(self.n) if perm is None else perm
         idx = idx_host.to(self.device)
-        gather = ops.gather_tasks_resized_crop_flip if self._resized else ops.gather_tasks_crop_flip
+        if self._norm is None:
+            gather, lut = (ops.gather_tasks_resized_crop_flip if self._resized else ops.gather_tasks_crop_flip), ()
+        else:
+            gather, lut = (ops.gather_tasks_resized_crop_flip_u8 if self._resized else ops.gather_tasks_crop_flip_u8), (self._lut,)
         for s in range(0, self.n, self.batch_size):
             self.last_idx, self.last_idx_host = idx[s:s + self.batch_size], idx_host[s:s + self.batch_size]
-            yield gather(self._table, self.geometry, idx[s:s + self.batch_size], params[s:s + self.batch_size])
+            if params is None:                      # byte frames without a transform: whole rows
+                x, y = ops.gather_tasks_u8(self._table, self.row_shape[0], math.prod(self.row_shape[1:]), self._lut, self.last_idx)
+                yield x.view((x.shape[0],) + self.row_shape), y
+            else:
+                yield gather(self._table, self.geometry, *lut, self.last_idx, params[s:s + self.batch_size])
 
     def __iter__(self):
         perm = self.order()
-        if self.transform is not None:
+        if self.transform is not None or self._norm is not None:
             yield from self._augmented(perm)
             return
         if perm is not None:
@@ -376,6 +482,7 @@ class TaskList(Dataset):
         import itertools
         self.datasets = list(dsets)
         assert self.datasets, "TaskList needs at least one task"
+        merged_norm(self.datasets)                    # all byte frames with one mean / std, or all floats
         classes_len = [len(d.classes) for d in self.datasets] if classes_len is None else list(classes_len)
         self.cumulative_sizes = list(itertools.accumulate(len(d) for d in self.datasets))
         self.cumulative_classes_len = list(itertools.accumulate(classes_len))
@@ -405,7 +512,8 @@ class MultiTaskLoader(DeviceLoader):
     """DeviceLoader over a TaskList: same length, order and consumption of the global RNG, but a batch is gathered straight
     out of the per-task tensors (clhip_gather_tasks) — the merged copy `ConcatTasks` makes (a second copy in HBM of every
     task the cache already holds) is never built.  Tasks that carry a RandomCropFlip or a RandomResizedCropFlip (all of one class and
-    equal parameters, or none) are served augmented as DeviceLoader describes, the crop and flip done in the same gather."""
+    equal parameters, or none) are served augmented as DeviceLoader describes, the crop and flip done in the same gather.
+    Tasks that hold byte frames (all of them, with equal mean and std) are decoded in the same gather; no merged copy either."""
 
     def __init__(self, dataset, batch_size, shuffle, device="cuda"):
         from . import ops
@@ -421,15 +529,19 @@ class MultiTaskLoader(DeviceLoader):
         self.row_elems = int(xs[0][0].numel())
         self.x = xs[0][:0]                      # (row shape only: what engine_for reads; no memory)
         transform = merged_transform(dataset.datasets)
+        self._norm = merged_norm(dataset.datasets)
         if transform is not None:
             self._augment(transform, xs, ys, dataset.cumulative_sizes, dataset.label_shifts)
+            return
+        if self._norm is not None:
+            self._serve_bytes(xs, ys, dataset.cumulative_sizes, dataset.label_shifts)
             return
         self.table = ops.task_table(xs, ys, dataset.cumulative_sizes, dataset.label_shifts, self.device)
 
     def __iter__(self):
         from . import ops
         perm = self.order()
-        if self.transform is not None:
+        if self.transform is not None or self._norm is not None:
             if perm is not None and self.n:
                 self.dataset.locate(perm[[int(perm.argmin()), int(perm.argmax())]])               # host check, before any launch
             yield from self._augmented(perm)

@@ -87,6 +87,10 @@ def build_parser():
                    help="with --synthetic: images are generated M pixels larger than hw and every training pass (importance "
                         "passes over reg_sets included) sees a fresh random hw x hw crop + horizontal flip of them, the RecogSeq "
                         "rule (data/recogseq_dataprep.py:53-60); evaluation reads the centre crops.  0: no augmentation")
+    p.add_argument("--u8_frames", action="store_true",
+                   help="with --synthetic: the task files hold the images as uint8 frames with their mean / std (data.ByteTaskDataset) "
+                        "and the loaders normalise them inside their batch gathers: a quarter of the bytes in HBM, bitwise the "
+                        "batches of the float files of the same quantised images.  Combines with --rnd_margin / --rnd_resized")
     p.add_argument("--rnd_resized", type=int, default=0,
                    help="with --synthetic, instead of --rnd_margin: images are generated M pixels larger than hw and every training "
                         "pass sees a fresh RandomResizedCrop to hw x hw (scale 0.08 - 1, ratio 3/4 - 4/3, antialiased bilinear) + "
@@ -760,6 +764,8 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         raise SystemExit("--rnd_margin belongs to --synthetic: a dataset object says itself which of its files are augmented")
     if args.rnd_resized and (dataset is not None or not args.synthetic):
         raise SystemExit("--rnd_resized belongs to --synthetic: a dataset object says itself which of its files are augmented")
+    if args.u8_frames and (dataset is not None or not args.synthetic):
+        raise SystemExit("--u8_frames belongs to --synthetic: a dataset object says itself how its files store their frames")
     if args.rnd_resized and args.rnd_margin:
         raise SystemExit("--rnd_margin and --rnd_resized exclude each other: a train split carries one transform")
     if args.rnd_resized < 0:
@@ -773,7 +779,8 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         dataset = SyntheticTaskSequence(os.path.join(args.results_root, "data"), task_count=n_tasks, classes_per_task=n_cls,
                                         sizes=(n_tr, n_va, n_te), hw=hw, noise=float(fields[6]) if len(fields) > 6 else 1.0,
                                         kind=kind, blobs=blobs, seed=int(fields[12]) if len(fields) > 12 else 7,
-                                        rnd_margin=args.rnd_margin, rnd_always=True, rnd_resized=args.rnd_resized)
+                                        rnd_margin=args.rnd_margin, rnd_always=True, rnd_resized=args.rnd_resized,
+                                        u8_frames=args.u8_frames)
     set_random(7)                                                 # utils.init -> set_random()
     if method is None:
         method = methods.parse(args.method_name)

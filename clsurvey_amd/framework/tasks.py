@@ -13,12 +13,13 @@ from collections import OrderedDict
 
 import torch
 
-from ..data import RandomCropFlip, RandomResizedCropFlip, TensorTaskDataset, synthetic_task
+from ..data import ByteTaskDataset, RandomCropFlip, RandomResizedCropFlip, TensorTaskDataset, synthetic_task
 
 
 class SyntheticTaskSequence(object):
     def __init__(self, root, task_count=10, classes_per_task=20, sizes=(8000, 2000, 1000), hw=64, seed=7, noise=1.0,
-                 name="synthetic_tiny_imagenet", kind="protos", blobs=None, rnd_margin=0, rnd_always=False, rnd_resized=0):
+                 name="synthetic_tiny_imagenet", kind="protos", blobs=None, rnd_margin=0, rnd_always=False, rnd_resized=0,
+                 u8_frames=False):
         """rnd_margin = m > 0: images are generated at (hw + m)^2; task_N.pth.tar holds their centre hw^2 crops (the Resize(256) /
         CenterCrop(224) of get_transforms(), data/inaturalist_dataprep.py:256-277) and task_N_rndtrans.pth.tar (named after
         data/dataset.py:108) the same images with the full frames + RandomCropFlip((hw, hw)) as `train` split.  rnd_always: the
@@ -28,7 +29,10 @@ class SyntheticTaskSequence(object):
         crop=True).  The same two files of the same images; the `train` split of task_N_rndtrans.pth.tar holds the full
         (hw + m)^2 frames with RandomResizedCropFlip((hw, hw)) (RandomResizedCrop(56) of 64^2 images), every other split the
         centre hw^2 crops (Resize(64) of a 64-pixel image is the identity, then CenterCrop(56)).  0: as if the option did
-        not exist."""
+        not exist.
+        u8_frames: the same generated images, quantised as clamp(round(x * 48 + 128), 0, 255), are stored as ByteTaskDatasets
+        with mean = 128 / 255 and std = 48 / 255 on every channel (what a pipeline that keeps the decoded images hands over), in
+        both files of a task and with either margin option.  False: as if the option did not exist."""
         self.name = name
         self.argname = name
         self.test_results_dir = name
@@ -48,6 +52,7 @@ class SyntheticTaskSequence(object):
         self.rnd_margin = int(rnd_margin)
         self.rnd_always = bool(rnd_always)
         self.rnd_resized = int(rnd_resized)
+        self.u8_frames = bool(u8_frames)
         if self.rnd_margin < 0 or self.rnd_resized < 0:
             raise ValueError("SyntheticTaskSequence: rnd_margin >= 0 and rnd_resized >= 0")
         if self.rnd_margin and self.rnd_resized:
@@ -67,7 +72,17 @@ class SyntheticTaskSequence(object):
             out["rnd_resized"] = self.rnd_resized
         if (self.rnd_margin or self.rnd_resized) and rnd_transform:
             out["rnd_transform"] = True
+        if self.u8_frames:
+            out["u8_frames"] = True
         return out
+
+    def _split(self, x, y, classes, transform=None):
+        """One split of a file: floats, or with u8_frames the quantised bytes."""
+        if not self.u8_frames:
+            return TensorTaskDataset(x, y, classes, transform=transform)
+        C = x.shape[1]
+        return ByteTaskDataset((x * 48 + 128).round().clamp(0, 255).to(torch.uint8), y, classes, [128.0 / 255] * C, [48.0 / 255] * C,
+                               transform=transform)
 
     def _make(self, task_name, rnd_transform):
         """The {'train', 'val', 'test'} dict of one file."""
@@ -76,12 +91,12 @@ class SyntheticTaskSequence(object):
         d = synthetic_task(self.sizes[0], self.sizes[1], self.sizes[2], self.n_classes, self.hw + m,
                            seed=want["seed"], noise=self.noise, kind=self.kind, blobs=self.blobs)
         if not m:
-            return d
+            return {s: self._split(v.x, v.y, v.classes) for s, v in d.items()} if self.u8_frames else d
         o = int(round(m / 2.0))                    # torchvision's center_crop offset
-        out = {s: TensorTaskDataset(v.x[:, :, o:o + self.hw, o:o + self.hw], v.y, v.classes) for s, v in d.items()}
+        out = {s: self._split(v.x[:, :, o:o + self.hw, o:o + self.hw], v.y, v.classes) for s, v in d.items()}
         if rnd_transform:
-            out["train"] = TensorTaskDataset(d["train"].x, d["train"].y, d["train"].classes,
-                                             transform=(RandomResizedCropFlip if self.rnd_resized else RandomCropFlip)((self.hw, self.hw)))
+            out["train"] = self._split(d["train"].x, d["train"].y, d["train"].classes,
+                                       transform=(RandomResizedCropFlip if self.rnd_resized else RandomCropFlip)((self.hw, self.hw)))
         return out
 
     def get_task_dataset_path(self, task_name=None, rnd_transform=False):

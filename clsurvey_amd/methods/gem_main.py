@@ -17,7 +17,7 @@ import numpy as np
 import torch
 from ..data import load_task_datasets
 
-from ..data import DeviceLoader, RandomResizedCropFlip
+from ..data import ByteTaskDataset, DeviceLoader, RandomResizedCropFlip
 from .exemplar import batch_source
 from . import gem as G
 from . import rehearsal as R
@@ -168,6 +168,10 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         # the exemplar wrappers replay stored frames through clhip_rehearsal_assemble_crop_flip, which does not resample
         raise NotImplementedError("rehearsal method %r: exemplars are replayed with RandomCropFlip only, the train split carries %r"
                                   % (args.method, dsets["train"].transform))
+    if isinstance(dsets["train"], ByteTaskDataset) and getattr(dsets["train"], "transform", None) is not None:
+        # frame mode copies fp32 frames into an fp32 store; without a transform the store holds the fp32 crops the loader served
+        raise NotImplementedError("rehearsal method %r: the exemplar store holds fp32 frames, the augmented train split holds byte "
+                                  "frames (a byte exemplar store does not exist yet)" % (args.method,))
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}
     in_shape = tuple(args.dset_loaders["train"].x.shape[1:])

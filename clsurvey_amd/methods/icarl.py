@@ -23,6 +23,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
+from ..data import ByteTaskDataset
 from ..optim import SGD
 from .exemplar import ExemplarNet, PerRowDropout, _stream, compact_blocks, compute_offsets
 from .gem import extend_head
@@ -243,6 +244,8 @@ class IcarlNet(PerRowDropout, ExemplarNet):
         if getattr(train, "transform", None) is not None:
             raise NotImplementedError("icarl: herding ranks the stored images of the task; an augmented split (%r) stores frames "
                                       "larger than the net's input" % (train.transform,))
+        if isinstance(train, ByteTaskDataset):
+            train = train.decoded()                                             # a byte split: herding reads the frames it means
         x, y = train.x, train.y
         order = torch.sort(y, stable=True)[1]                                   # classes back to back, dataset order inside
         sizes = torch.bincount(y, minlength=o2 - o1).cpu().tolist()

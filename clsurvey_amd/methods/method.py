@@ -27,7 +27,7 @@ from enum import Enum, auto
 
 import torch
 
-from ..data import DeviceLoader, MultiTaskLoader, TaskList, TensorTaskDataset, load_task_datasets, merged_transform
+from ..data import ByteTaskDataset, DeviceLoader, MultiTaskLoader, TaskList, TensorTaskDataset, load_task_datasets, merged_norm, merged_transform
 from . import ebll as _ebll
 from . import ewc as _ewc
 from . import finetune as _ft
@@ -229,7 +229,16 @@ EVALUATE = {"swap_head": _eval_swap_head, "as_is": _eval_as_is, "wrapper_after_f
 # ------------------------------------------------------------------------------------------------ shared phase 1 (SGD)
 class ConcatTasks(TensorTaskDataset):
     """Several tasks as one dataset, labels of task j shifted by the class counts of the tasks before it
-    (data/imgfolder.py ConcatDatasetDynamicLabels)."""
+    (data/imgfolder.py ConcatDatasetDynamicLabels).  Over tasks that hold byte frames (all of them, with equal mean and std:
+    data.merged_norm) the result is the ByteTaskDataset of the concatenated bytes, not an instance of this class."""
+
+    def __new__(cls, dsets, classes_len):
+        norm = merged_norm(dsets)
+        if norm is None:
+            return super().__new__(cls)
+        shift = [0] + list(itertools.accumulate(classes_len))[:-1]
+        return ByteTaskDataset(torch.cat([d.x for d in dsets]), torch.cat([d.y + s for d, s in zip(dsets, shift)]),
+                               [c for d in dsets for c in d.classes], norm[0], norm[1], transform=merged_transform(dsets))
 
     def __init__(self, dsets, classes_len):
         shift = [0] + list(itertools.accumulate(classes_len))[:-1]

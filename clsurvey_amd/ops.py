@@ -764,11 +764,13 @@ def cross_entropy(logits, labels, reduction="mean"):
 
 # ------------------------------------------------------------------ Joint baseline
 def task_table(xs, ys, cum_rows, label_shifts, device):
-    """Device table of clhip_task_src rows (x pointer, label pointer, cumulative row count, label shift) as int64[T, 4]."""
+    """Device table of clhip_task_src rows (x pointer, label pointer, cumulative row count, label shift) as int64[T, 4].
+    xs all float32, or all uint8 (clhip_task_src_u8 rows, the same layout: for the ..._u8 gathers)."""
     _chk(*xs, *ys)
     T = len(xs)
     assert 1 <= T <= 64 and len(ys) == len(cum_rows) == len(label_shifts) == T, "clhip_gather_tasks takes 1..64 tasks"
-    assert all(x.dtype == torch.float32 for x in xs) and all(y.dtype == torch.int64 for y in ys)
+    assert xs[0].dtype in (torch.float32, torch.uint8) and all(x.dtype == xs[0].dtype for x in xs), "tasks of one table: all float32 or all uint8"
+    assert all(y.dtype == torch.int64 for y in ys)
     rows = [[x.data_ptr(), y.data_ptr(), int(c), int(s)] for x, y, c, s in zip(xs, ys, cum_rows, label_shifts)]
     return torch.tensor(rows, dtype=torch.int64).to(device)
 
@@ -841,6 +843,65 @@ def gather_tasks_resized_crop_flip(table, geometry, idx, params, x_out=None, lab
                                                               _ptr(params[s:s + n]), n, _ptr(xf[s * row_elems:]),
                                                               _ptr(labels_out[s:]), _stream()), "clhip_gather_tasks_resized_crop_flip")
     return x_out, labels_out
+
+
+def _chk_lut(lut, C):
+    assert lut.dtype == torch.float32 and tuple(lut.shape) == (C, 256) and lut.is_contiguous(), "lut: float32 [C, 256]"
+
+
+def gather_tasks_u8(table, C, plane_elems, lut, idx, x_out=None, labels_out=None):
+    """clhip_gather_tasks_u8: gather_tasks out of a table of uint8 rows [C][plane_elems] (task_table over uint8 tensors), every
+    byte decoded through lut (device float32 [C, 256]).  Returns (x_out [B, C * plane_elems], labels_out [B])."""
+    _chk(table, lut, idx, x_out, labels_out)
+    C, plane_elems = int(C), int(plane_elems)
+    assert idx.dtype == torch.int64 and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 4
+    _chk_lut(lut, C)
+    B = idx.shape[0]
+    row_elems = C * plane_elems
+    if x_out is None:
+        x_out = torch.empty((B, row_elems), dtype=torch.float32, device=idx.device)
+    if labels_out is None:
+        labels_out = torch.empty((B,), dtype=torch.int64, device=idx.device)
+    assert x_out.dtype == torch.float32 and x_out.numel() >= B * row_elems and labels_out.numel() >= B
+    xf, step = x_out.view(-1), 65535                     # one launch takes at most 65535 rows (grid y): larger batches in pieces
+    for s in range(0, B, step):
+        n = min(step, B - s)
+        check(_lib.lib().clhip_gather_tasks_u8(_ptr(table), table.shape[0], C, plane_elems, _ptr(lut), _ptr(idx[s:s + n]), n,
+                                               _ptr(xf[s * row_elems:]), _ptr(labels_out[s:]), _stream()), "clhip_gather_tasks_u8")
+    return x_out, labels_out
+
+
+def _gather_window_u8(entry, ncols, table, geometry, lut, idx, params, x_out, labels_out):
+    _chk(table, lut, idx, params, x_out, labels_out)
+    C, Hs, Ws, th, tw = (int(v) for v in geometry)
+    assert idx.dtype == torch.int64 and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 4
+    _chk_lut(lut, C)
+    B = idx.shape[0]
+    assert params.dtype == torch.int32 and tuple(params.shape) == (B, ncols) and params.is_contiguous()
+    if x_out is None:
+        x_out = torch.empty((B, C, th, tw), dtype=torch.float32, device=idx.device)
+    if labels_out is None:
+        labels_out = torch.empty((B,), dtype=torch.int64, device=idx.device)
+    row_elems = C * th * tw
+    assert x_out.dtype == torch.float32 and x_out.numel() >= B * row_elems and labels_out.numel() >= B
+    xf, step = x_out.view(-1), 65535                     # one launch takes at most 65535 rows (grid y): larger batches in pieces
+    for s in range(0, max(B, 1), step):
+        n = min(step, B - s)
+        check(getattr(_lib.lib(), entry)(_ptr(table), table.shape[0], C, Hs, Ws, th, tw, _ptr(lut), _ptr(idx[s:s + n]),
+                                         _ptr(params[s:s + n]), n, _ptr(xf[s * row_elems:]), _ptr(labels_out[s:]), _stream()), entry)
+    return x_out, labels_out
+
+
+def gather_tasks_crop_flip_u8(table, geometry, lut, idx, params, x_out=None, labels_out=None):
+    """clhip_gather_tasks_crop_flip_u8: gather_tasks_crop_flip out of uint8 frames, decoded through lut (device float32
+    [C, 256]): bitwise gather_tasks_crop_flip of the decoded frames."""
+    return _gather_window_u8("clhip_gather_tasks_crop_flip_u8", 3, table, geometry, lut, idx, params, x_out, labels_out)
+
+
+def gather_tasks_resized_crop_flip_u8(table, geometry, lut, idx, params, x_out=None, labels_out=None):
+    """clhip_gather_tasks_resized_crop_flip_u8: gather_tasks_resized_crop_flip out of uint8 frames, decoded through lut (device
+    float32 [C, 256]) before the filter: bitwise gather_tasks_resized_crop_flip of the decoded frames."""
+    return _gather_window_u8("clhip_gather_tasks_resized_crop_flip_u8", 5, table, geometry, lut, idx, params, x_out, labels_out)
 
 
 def rehearsal_assemble_crop_flip(geometry, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows, gather, params,

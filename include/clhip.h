@@ -624,6 +624,49 @@ int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T,
                                          const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out,
                                          void* stream);
 
+/* ------------------------------------------------------------------ byte frames
+ * ToTensor -> Normalize, the last step of every Compose of the reference (data/recogseq_dataprep.py:53-60,
+ * data/inaturalist_dataprep.py:232-277, data/tinyimgnet_dataprep.py:105-122), done inside the gathers: the task tensors hold the
+ * decoded images as uint8 [n][C][H][W], a quarter of the bytes in HBM and on every gather's source side.
+ *
+ * MEANING.  A byte dataset is its frames plus per-channel mean and std (fp32 [C], std > 0).  It means the fp32 dataset of
+ * lut[c][x], lut a [C][256] fp32 table the HOST computes once with torch on the CPU, op for op as ToTensor then Normalize do:
+ *     lut[c][v] = (float(v) / 255 - mean[c]) / std[c]          (fp32: convert, div, sub, div)
+ * The device never does this arithmetic: it looks the byte up.  So each entry below yields, BITWISE, what its fp32 sibling
+ * yields on the decoded frames for the same idx / params; crop, flip and the antialiased resize act on the decoded values
+ * exactly as the fp32 kernels do (the stated difference to PIL's uint8 rounding in the resized case is unchanged).
+ *
+ * The task table keeps its layout (clhip_task_src_u8 differs from clhip_task_src only in the type x points to); every entry
+ * takes the DEVICE table `lut` (fp32 [C][256]) after the geometry.
+ *
+ *   gather_tasks_u8     clhip_gather_tasks for byte rows [C][plane_elems] (row_elems = C plane_elems):
+ *                         x_out[b][e] = lut[(e / plane_elems) % C][row(idx[b])[e]]
+ *                       bad rows and labels as clhip_gather_tasks.  CLHIP_EINVAL before any launch: its checks, lut == NULL,
+ *                       C < 1, plane_elems < 1.  B == 0 returns 0.  float4 stores when row_elems % 4 == 0 and the destination
+ *                       row is 16-byte aligned, plain stores otherwise.  Source: a row of odd size starts at any byte, so the
+ *                       baseline is byte loads; the 4 bytes of a float4 are one dword load only when the source row's address
+ *                       was TESTED to be a multiple of 4.  The table is read through the cache (a 16 KB output segment may
+ *                       cross any number of channel planes).
+ *   gather_tasks_crop_flip_u8   clhip_gather_tasks_crop_flip for byte frames, same geometry and (top, left, flip) table:
+ *                         x_out[b][c][y][x] = lut[c][frame(idx[b])[c][top_b + y][left_b + (flip_b ? tw - 1 - x : x)]]
+ *                       Same bad rows (nothing copied, label -1, no address outside the frame formed), same CLHIP_EINVAL
+ *                       checks plus lut == NULL.  float4 stores when tw % 4 == 0 and x_out is 16-byte aligned; byte loads,
+ *                       one dword load per 4 columns only behind a test of that address.  The block's channel of the table
+ *                       is staged in LDS (1 KB).
+ *   gather_tasks_resized_crop_flip_u8   clhip_gather_tasks_resized_crop_flip for byte frames, same geometry, (top, left, h, w,
+ *                       flip) table, plan, taps, summation order and stores: the bytes are decoded through the block's channel
+ *                       of the table (staged in LDS; the plan counts its 1 KB) while the source band is staged, everything
+ *                       after is the fp32 entry's code.  Same bad rows, CLHIP_EINVAL checks plus lut == NULL, CLHIP_ENOTSUP
+ *                       as there (with the table's 1 KB counted).  Byte loads. */
+typedef struct clhip_task_src_u8 { const uint8_t* x; const int64_t* labels; int64_t cum_rows; int64_t label_shift; } clhip_task_src_u8;
+int clhip_gather_tasks_u8(const clhip_task_src_u8* tasks_dev, int T, int C, size_t plane_elems, const float* lut,
+                          const int64_t* idx, int B, float* x_out, int64_t* labels_out, void* stream);
+int clhip_gather_tasks_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const float* lut,
+                                    const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out, void* stream);
+int clhip_gather_tasks_resized_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,
+                                            const float* lut, const int64_t* idx, const int* params, int B, float* x_out,
+                                            int64_t* labels_out, void* stream);
+
 /* ------------------------------------------------------------------ iCaRL
  * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471) and the nearest-mean-of-exemplars classifier of
  * Net.forward (:142-186); the loss of update_representation (:482-598) over one mixed batch is clhip_loss_segments above.
