@@ -28,11 +28,13 @@ int ew_launch(size_t n, bool vec_ok, F f, hipStream_t s) {
 struct RegSgd {
     float* theta; const float* grad; const float* omega; const float* init; float* buf;
     float two_lambda, lr, momentum, wd; int first;
+    // The multiply-adds are fused by hand, in the form hipcc's contraction gave the float4 path: left to the compiler the
+    // scalar path came out unfused, and a tensor's result depended on the alignment of its pointers.
     __device__ __forceinline__ float one(float th, float g, float om, float iv, float& b) const {
-        float d = g + (th - iv) * (two_lambda * om);   // train_EWC.py:62-65
-        d = d + wd * th;                               // :70-71
-        b = first ? d : (b * momentum + d);            // :72-78
-        return th - lr * b;                            // :83
+        float d = __fmaf_rn(two_lambda * om, th - iv, g);   // train_EWC.py:62-65
+        d = __fmaf_rn(wd, th, d);                           // :70-71
+        b = first ? d : __fmaf_rn(b, momentum, d);          // :72-78
+        return __fmaf_rn(-lr, b, th);                       // :83
     }
     __device__ __forceinline__ void scalar(size_t i) const {
         float b = first ? 0.f : buf[i];
@@ -80,12 +82,13 @@ struct MasAcc {
 struct SiStep {
     float* theta; const float* grad; const float* omega; const float* init; float* w; float* buf;
     float two_lambda, lr, momentum, wd; int first;
+    // multiply-adds fused by hand as in RegSgd::one: the same value on the scalar and the float4 path
     __device__ __forceinline__ float one(float th, float g, float om, float iv, float& b, float& wv) const {
-        float d = g + (th - iv) * (two_lambda * om);   // train_SI.py:69-73
-        d = d + wd * th;                               // :82-83
-        b = first ? d : (b * momentum + d);            // :85-96
-        float tn = th - lr * b;                        // :98
-        wv = wv + ((tn - th) * g) * -1.f;              // :99-120 (unregularised g, actual step)
+        float d = __fmaf_rn(two_lambda * om, th - iv, g);   // train_SI.py:69-73
+        d = __fmaf_rn(wd, th, d);                           // :82-83
+        b = first ? d : __fmaf_rn(b, momentum, d);          // :85-96
+        float tn = __fmaf_rn(-lr, b, th);                   // :98
+        wv = __fmaf_rn(-g, tn - th, wv);                    // :99-120 (unregularised g, actual step)
         return tn;
     }
     __device__ __forceinline__ void scalar(size_t i) const {
@@ -142,14 +145,16 @@ struct ImmPtrs { const float* theta[IMM_MAX]; const float* prec[IMM_MAX]; };
 struct ImmMerge {
     ImmPtrs p; const float* sum_prec; float* out; int n_models; int mean_mode;
     __device__ __forceinline__ void scalar(size_t i) const {
+        // Plain operators under contract(off): separate, correctly rounded div / mul / add like the reference's three torch
+        // ops.  (HIP's __fmul_rn / __fadd_rn are plain operators compiled with contraction on: the pair became one fma.)
+#pragma clang fp contract(off)
         float acc = 0.f;
         if (mean_mode) {
-            for (int m = 0; m < n_models; ++m) acc = __fadd_rn(acc, p.theta[m][i]);
-            acc = __fdiv_rn(acc, (float)n_models);
+            for (int m = 0; m < n_models; ++m) acc = acc + p.theta[m][i];
+            acc = acc / (float)n_models;
         } else {
             const float sp = sum_prec[i];
-            // separate, correctly rounded div / mul / add like the reference's three torch ops (no fma contraction)
-            for (int m = 0; m < n_models; ++m) acc = __fadd_rn(acc, __fmul_rn(__fdiv_rn(p.prec[m][i], sp), p.theta[m][i]));
+            for (int m = 0; m < n_models; ++m) acc = acc + (p.prec[m][i] / sp) * p.theta[m][i];
         }
         out[i] = acc;
     }

@@ -6,6 +6,8 @@ namespace {
 
 constexpr int PB = 256;
 
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
 // One thread per output element; consecutive threads -> consecutive ow => coalesced
 // float2 reads of both input rows.
 __global__ __launch_bounds__(PB) void maxpool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -156,6 +158,7 @@ extern "C" {
 
 int clhip_maxpool2_fwd(const float* x, float* y, uint8_t* idx_u8, int NC, int H, int W, void* stream) {
     if (!x || !y || !idx_u8 || NC <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return CLHIP_EINVAL;
+    if (!aligned8(x)) return CLHIP_EINVAL;          // the kernel reads x as float2
     size_t total = (size_t)NC * (H / 2) * (W / 2);
     hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(ew_grid(total, PB)), dim3(PB), 0, as_stream(stream), x, y, idx_u8, total, H, W);
     CLHIP_LAUNCH_CHECK();
@@ -164,6 +167,7 @@ int clhip_maxpool2_fwd(const float* x, float* y, uint8_t* idx_u8, int NC, int H,
 
 int clhip_maxpool2_bwd(const float* dy, const uint8_t* idx_u8, float* dx, int NC, int H, int W, void* stream) {
     if (!dy || !dx || !idx_u8 || NC <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return CLHIP_EINVAL;
+    if (!aligned8(dx)) return CLHIP_EINVAL;         // the kernel writes dx as float2
     size_t total = (size_t)NC * (H / 2) * (W / 2);
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total, PB)), dim3(PB), 0, as_stream(stream), dy, idx_u8, dx, total, H, W);
     CLHIP_LAUNCH_CHECK();

@@ -98,7 +98,8 @@ int clhip_conv3x3_bwd_weight_unpool(const float* x, const float* dy_pool, const 
 /* ------------------------------------------------------------------ max-pool 2x2 stride 2
  * nn.MaxPool2d(2, 2) — models/VGGSlim.py:32. idx_u8 holds the argmax (0..3, row-major in the
  * window, first maximum wins as in ATen).  H, W are the INPUT sizes (even).  The backward kernel
- * also takes the fused kernels' code 4 ("no positive maximum": the window gets no gradient).        */
+ * also takes the fused kernels' code 4 ("no positive maximum": the window gets no gradient).
+ * x (forward) and dx (backward) are accessed as float2: CLHIP_EINVAL unless they are 8-byte aligned. */
 int clhip_maxpool2_fwd(const float* x, float* y, uint8_t* idx_u8, int NC, int H, int W, void* stream);
 int clhip_maxpool2_bwd(const float* dy, const uint8_t* idx_u8, float* dx, int NC, int H, int W,
                        void* stream);

@@ -1,5 +1,6 @@
 """Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py,
-test_gpu_gemm_kernels.py) — test infrastructure.
+test_gpu_gemm_kernels.py, test_gpu_pool_kernels.py, test_gpu_bn_kernels.py, test_gpu_packnet_kernels.py,
+test_gpu_elementwise_kernels.py) — test infrastructure.
 
 The fp32-chain rule is the one of assert_fp32_parity in test_gpu_parity.py with the bounds these two files use: the device
 result's distance from an fp64 evaluation of the same formula on the same float32 inputs, relative to the tensor's largest
@@ -14,13 +15,15 @@ HAT_BASE = 1e-6       # what test_elementwise_regularizers_match_oracle asserts 
 CPU_FACTOR = 4.0
 
 
-def fp32_chain_check(case, what, got, ref32, ref64, base):
+def fp32_chain_check(case, what, got, ref32, ref64, base, scale=None):
+    """scale: what the distances are measured against; default the fp64 reference's largest entry.  A caller passes the
+    size of the terms when the result is a difference of much larger ones (BatchNorm's dz)."""
     got = torch.as_tensor(got).detach().double().cpu().reshape(-1)
     ref32 = torch.as_tensor(ref32).detach().double().reshape(-1)
     ref64 = torch.as_tensor(ref64).detach().double().reshape(-1)
     assert got.shape == ref64.shape == ref32.shape, (what, got.shape, ref32.shape, ref64.shape)
     assert bool(torch.isfinite(ref64).all()), what + ": the fp64 reference is not finite"
-    scale = max(float(ref64.abs().max()), 1e-30)
+    scale = max(float(ref64.abs().max()) if scale is None else float(scale), 1e-30)
     d = (got - ref64).abs()
     e_dev = float(d.max()) / scale if bool(torch.isfinite(got).all()) else float("inf")
     e_cpu = float((ref32 - ref64).abs().max()) / scale
@@ -71,11 +74,12 @@ class Arena:
         self.size = 4
 
     def add(self, t, misaligned=False, fill=None):
-        """t: a tensor, or with `fill` a number of floats that all start as that 32-bit pattern (bit_pattern)."""
+        """t: a tensor, or with `fill` a number of floats that all start as that 32-bit pattern (bit_pattern).
+        misaligned: True or 1 = one float past a 16-byte boundary; 2 = two floats past one (8-byte aligned, not 16)."""
         if fill is not None:
             t = bit_pattern(int(t), fill)
         t = t.detach().contiguous().reshape(-1).float()
-        off = (self.size + 3) // 4 * 4 + 4 + (1 if misaligned else 0)
+        off = (self.size + 3) // 4 * 4 + 4 + int(misaligned)
         self.items.append((off, t))
         self.size = off + t.numel()
         return len(self.items) - 1
@@ -94,6 +98,56 @@ class Arena:
     def ptr(self, k):
         off, t = self.items[k]
         return self.dev.data_ptr() + 4 * off
+
+    def download(self):
+        self.back = self.dev.cpu()
+        return self
+
+    def get(self, k):
+        off, t = self.items[k]
+        return self.back[off:off + t.numel()]
+
+    def gaps_untouched(self):
+        keep = torch.ones(self.back.numel(), dtype=torch.bool)
+        for off, t in self.items:
+            keep[off:off + t.numel()] = False
+        return bool((self.back[keep] == self.GAP).all())
+
+
+class ByteArena:
+    """Arena's counterpart for uint8 tensors (PackNet's task masks, the pools' arg-max codes): one flat byte buffer, every
+    tensor at an odd byte offset (or, odd=False, on a 16-byte boundary), sentinel bytes in the gaps between them."""
+    GAP = 0xA5
+
+    def __init__(self):
+        self.items = []            # (offset, host tensor)
+        self.size = 16
+
+    def add(self, t, odd=True, fill=None):
+        """t: a uint8 tensor, or with `fill` a number of bytes that all start as that value."""
+        if fill is not None:
+            t = torch.full((int(t),), int(fill), dtype=torch.uint8)
+        t = t.detach().contiguous().reshape(-1)
+        assert t.dtype == torch.uint8
+        off = (self.size + 15) // 16 * 16 + 16 + (5 if odd else 0)
+        self.items.append((off, t))
+        self.size = off + t.numel()
+        return len(self.items) - 1
+
+    def host(self):
+        flat = torch.full((self.size + 32,), self.GAP, dtype=torch.uint8)
+        for off, t in self.items:
+            flat[off:off + t.numel()] = t
+        return flat
+
+    def upload(self, device):
+        self.dev = self.host().to(device)
+        assert self.dev.data_ptr() % 16 == 0
+        return self
+
+    def ptr(self, k):
+        off, t = self.items[k]
+        return self.dev.data_ptr() + off
 
     def download(self):
         self.back = self.dev.cpu()
