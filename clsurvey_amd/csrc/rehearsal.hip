@@ -5,20 +5,29 @@
 //   rehearsal_assemble_crop_flip   the store holds FRAMES (the counterpart of the reference's memory of paths: :215-216 rebuilds
 //                                  the exemplar loader with the task's train transform at every step); the gathered exemplars
 //                                  are cropped and mirrored in the same launch
+//   rehearsal_assemble_crop_flip_u8  the same with BYTE frames in the store (clhip.h, byte frames): the ring rows are raw byte
+//                                  copies, the gathered exemplars are decoded through the table where they are loaded
 #include "crop_flip.hpp"
+#include <type_traits>
 
 namespace {
 
 constexpr int ASM_BLOCK = 256;
 constexpr int ASM_VEC_PER_THREAD = 12;    // float4 per thread, all in flight at once: 48 KB per block = one 3x64x64 row
 constexpr size_t ASM_SEG = (size_t)ASM_BLOCK * ASM_VEC_PER_THREAD * 4;       // floats per block
+constexpr size_t ASM_SEG_U8 = (size_t)ASM_BLOCK * ASM_VEC_PER_THREAD * 16;   // bytes per block: the same 48 KB
+constexpr int ASM_BYTES_PER_THREAD = 16;  // byte accesses per thread in flight at once on the plain byte path
 static_assert(ASM_BLOCK == CF_BLOCK, "the crop rows of rehearsal_assemble_cf_kernel run cf_copy_window");
 
-// Segment `seg` (ASM_SEG floats, the last one shorter) of a row of `elems` floats, src -> dst.
-template <bool VEC>
-__device__ __forceinline__ void copy_segment(const float* src, float* dst, size_t elems, unsigned seg) {
+template <typename T> constexpr size_t asm_seg = std::is_same<T, uint8_t>::value ? ASM_SEG_U8 : ASM_SEG;   // elements per block
+
+// Segment `seg` (asm_seg<T> elements = 48 KB, the last one shorter) of a row of `elems` elements, src -> dst.
+// VEC: 16-byte accesses (elems * sizeof(T) % 16 == 0, both rows 16-byte aligned: decided on the host).  Otherwise element
+// accesses; a byte row of odd size starts at any address, so its plain path is byte loads and byte stores.
+template <bool VEC, typename T>
+__device__ __forceinline__ void copy_segment(const T* src, T* dst, size_t elems, unsigned seg) {
     if (VEC) {
-        const size_t nvec = elems / 4;
+        const size_t nvec = elems / (16 / sizeof(T));
         const float4* s4 = reinterpret_cast<const float4*>(src);
         float4* d4 = reinterpret_cast<float4*>(dst);
         const size_t base = (size_t)seg * ASM_BLOCK * ASM_VEC_PER_THREAD + threadIdx.x;
@@ -33,9 +42,24 @@ __device__ __forceinline__ void copy_segment(const float* src, float* dst, size_
             const size_t i = base + (size_t)k * ASM_BLOCK;
             if (i < nvec) d4[i] = v[k];
         }
+    } else if constexpr (std::is_same<T, uint8_t>::value) {
+        const size_t end = min(elems, ((size_t)seg + 1) * asm_seg<T>);
+        for (size_t i0 = (size_t)seg * asm_seg<T> + threadIdx.x; i0 < end; i0 += (size_t)ASM_BYTES_PER_THREAD * ASM_BLOCK) {
+            uint8_t v[ASM_BYTES_PER_THREAD];
+#pragma unroll
+            for (int k = 0; k < ASM_BYTES_PER_THREAD; ++k) {    // a batch of loads in flight before its first store
+                const size_t i = i0 + (size_t)k * ASM_BLOCK;
+                if (i < end) v[k] = src[i];
+            }
+#pragma unroll
+            for (int k = 0; k < ASM_BYTES_PER_THREAD; ++k) {
+                const size_t i = i0 + (size_t)k * ASM_BLOCK;
+                if (i < end) dst[i] = v[k];
+            }
+        }
     } else {
-        const size_t end = min(elems, ((size_t)seg + 1) * ASM_SEG);
-        for (size_t i = (size_t)seg * ASM_SEG + threadIdx.x; i < end; i += ASM_BLOCK) dst[i] = src[i];
+        const size_t end = min(elems, ((size_t)seg + 1) * asm_seg<T>);
+        for (size_t i = (size_t)seg * asm_seg<T> + threadIdx.x; i < end; i += ASM_BLOCK) dst[i] = src[i];
     }
 }
 
@@ -89,11 +113,16 @@ __global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_kernel(
 // Nothing outside a frame is addressed: a src_idx outside [0, src_rows) leaves its store row as it is and writes store label
 // -1; a gather row outside [0, store_rows), top outside [0, Hs - th], left outside [0, Ws - tw] or flip outside {0, 1} copies
 // nothing and writes label -1 (the host draws valid tables; this only keeps a bad one from faulting).
+// T: the element type of the frames (src_frames, store): float, or uint8_t for a byte store.  A stored byte v of channel c means
+// lut[c][v] (clhip.h, byte frames): the ring rows copy bytes, the crop rows decode them where they are loaded, through the block's
+// channel of the table staged in LDS (augment.hip), and everything after the load is the float code.
+template <typename T>
 struct assemble_cf_args {
     const float* x; const int64_t* y; int B, copy_rows;                        // copy_rows = B, or 0 without x_mix
     int C, Hs, Ws, th, tw;
-    const float* src_frames; long src_rows; const int64_t* src_idx;
-    float* store; int64_t* store_y; long store_rows, row0; int ring;
+    const float* lut;                                                          // [C][256], byte frames only
+    const T* src_frames; long src_rows; const int64_t* src_idx;
+    T* store; int64_t* store_y; long store_rows, row0; int ring;
     const int* gather; const int* params; int E;
     float* x_mix; int64_t* y_mix;
     unsigned row_blocks, frame_blocks, crop_blocks;                            // blocks per row of each run
@@ -101,42 +130,38 @@ struct assemble_cf_args {
     int vec_row, vec_frame;                                                    // 16-byte copies of the two full-row roles
 };
 
-template <bool VEC_CROP>
-__global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const assemble_cf_args a) {
+template <bool VEC_CROP, typename T>
+__global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const assemble_cf_args<T> a) {
     unsigned b = blockIdx.x;
     const size_t row_elems = (size_t)a.C * a.th * a.tw, frame_elems = (size_t)a.C * a.Hs * a.Ws;
     const unsigned n_row = (unsigned)a.copy_rows * a.row_blocks, n_ring = (unsigned)a.ring * a.frame_blocks;
-    if (b < n_row + n_ring) {
-        const float* src;
-        float* dst;
-        const int64_t* ysrc;
-        int64_t* ydst;
-        size_t elems;
-        unsigned seg;
-        bool vec;
-        if (b < n_row) {
-            const unsigned r = b / a.row_blocks;
-            seg = b - r * a.row_blocks; elems = row_elems; vec = a.vec_row;
-            src = a.x + r * row_elems; dst = a.x_mix + r * row_elems;
-            ysrc = a.y + r; ydst = a.y_mix + r;
-        } else {
-            b -= n_row;
-            const unsigned i = b / a.frame_blocks;
-            seg = b - i * a.frame_blocks; elems = frame_elems; vec = a.vec_frame;
-            const int64_t s = a.src_idx[i];
-            ysrc = a.y + i; ydst = a.store_y + a.row0 + i;
-            if (s < 0 || s >= a.src_rows) {
-                if (seg == 0 && threadIdx.x == 0) *ydst = -1;
-                return;
-            }
-            src = a.src_frames + (size_t)s * frame_elems; dst = a.store + (size_t)(a.row0 + i) * frame_elems;
-        }
-        if (seg == 0 && threadIdx.x == 0) *ydst = *ysrc;
-        if (vec) copy_segment<true>(src, dst, elems, seg);
-        else copy_segment<false>(src, dst, elems, seg);
+    if (b < n_row) {
+        const unsigned r = b / a.row_blocks;
+        const unsigned seg = b - r * a.row_blocks;
+        if (seg == 0 && threadIdx.x == 0) a.y_mix[r] = a.y[r];
+        if (a.vec_row) copy_segment<true>(a.x + r * row_elems, a.x_mix + r * row_elems, row_elems, seg);
+        else copy_segment<false>(a.x + r * row_elems, a.x_mix + r * row_elems, row_elems, seg);
         return;
     }
-    b -= n_row + n_ring;
+    b -= n_row;
+    if (b < n_ring) {
+        const unsigned i = b / a.frame_blocks;
+        const unsigned seg = b - i * a.frame_blocks;
+        const int64_t s = a.src_idx[i];
+        int64_t* ydst = a.store_y + a.row0 + i;
+        if (s < 0 || s >= a.src_rows) {
+            if (seg == 0 && threadIdx.x == 0) *ydst = -1;
+            return;
+        }
+        if (seg == 0 && threadIdx.x == 0) *ydst = a.y[i];
+        const T* src = a.src_frames + (size_t)s * frame_elems;
+        T* dst = a.store + (size_t)(a.row0 + i) * frame_elems;
+        if (a.vec_frame) copy_segment<true>(src, dst, frame_elems, seg);
+        else copy_segment<false>(src, dst, frame_elems, seg);
+        return;
+    }
+    b -= n_ring;
+    // (the role and the bad-row test are block-uniform: every thread of a block reaches the barrier below or none does)
     const unsigned e = b / a.crop_blocks;
     const int k = (int)(b - e * a.crop_blocks);
     const long g = a.gather[e];
@@ -150,12 +175,67 @@ __global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const 
     const int c = k / a.chunks;
     const int y0 = (k - c * a.chunks) * a.rpb;
     const int nrows = min(a.rpb, a.th - y0);
-    const float* src = a.store + ((size_t)g * a.C + c) * a.Hs * a.Ws + (size_t)(top + y0) * a.Ws + left;
+    const T* src = a.store + ((size_t)g * a.C + c) * a.Hs * a.Ws + (size_t)(top + y0) * a.Ws + left;
     float* dst = a.x_mix + (((size_t)(a.B + e) * a.C + c) * a.th + y0) * a.tw;
-    cf_copy_window<VEC_CROP>(src, a.Ws, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip);   // total <= max(CF_SEG, tw) < 2^31
+    if constexpr (std::is_same<T, uint8_t>::value) {
+        __shared__ float lut_s[256];                                           // the table of channel c (CF_BLOCK == 256: one entry each)
+        lut_s[threadIdx.x] = a.lut[c * 256 + (int)threadIdx.x];
+        __syncthreads();
+        typedef const uint8_t __attribute__((address_space(1))) gbyte;       // (device memory: global_load, not flat_load)
+        cf_copy_window<VEC_CROP>((gbyte*)src, a.Ws, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip, cf_load_u8{lut_s});
+    } else {
+        cf_copy_window<VEC_CROP>(src, a.Ws, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip);   // total <= max(CF_SEG, tw) < 2^31
+    }
 }
 
 }  // namespace
+
+// One body for the pair of frame-mode entries: T selects the frames' element type, lut is NULL for floats.
+template <typename T>
+static int assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                              const float* lut, const T* src_frames, long src_rows, const int64_t* src_idx, T* store_frames,
+                              int64_t* store_labels, long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
+                              const int* gather_params, int E, float* x_mix, int64_t* labels_mix, void* stream) {
+    if (B < 0 || E < 0 || ring_rows < 0 || store_rows < 0 || src_rows < 0) return CLHIP_EINVAL;
+    if (C < 1 || th < 1 || tw < 1 || th > Hs || tw > Ws) return CLHIP_EINVAL;
+    if (ring_rows > B) return CLHIP_EINVAL;                                      // ring rows are a prefix of the batch
+    if (E > 0 && (!x_mix || !gather_rows || !gather_params)) return CLHIP_EINVAL;
+    if (std::is_same<T, uint8_t>::value && E > 0 && !lut) return CLHIP_EINVAL;   // (a ring-only call decodes nothing)
+    const int copy_rows = x_mix ? B : 0;                                         // no x_mix (E == 0): the ring update alone
+    if (copy_rows > 0 && !x) return CLHIP_EINVAL;
+    if ((copy_rows > 0 || ring_rows > 0) && !labels_i64) return CLHIP_EINVAL;
+    if ((copy_rows > 0 || E > 0) && !labels_mix) return CLHIP_EINVAL;
+    if (ring_rows > 0 && (!src_frames || !src_idx)) return CLHIP_EINVAL;
+    if ((ring_rows > 0 || E > 0) && (!store_frames || !store_labels)) return CLHIP_EINVAL;
+    if (ring_rows > 0 && (ring_row0 < 0 || ring_row0 + ring_rows > store_rows)) return CLHIP_EINVAL;
+    const long rows = (long)copy_rows + ring_rows + E;
+    if (rows == 0) return 0;
+    if (rows > 65535) return CLHIP_EINVAL;
+    const size_t row_elems = (size_t)C * th * tw, frame_elems = (size_t)C * Hs * Ws;
+    assemble_cf_args<T> a;
+    a.x = x; a.y = labels_i64; a.B = B; a.copy_rows = copy_rows;
+    a.C = C; a.Hs = Hs; a.Ws = Ws; a.th = th; a.tw = tw;
+    a.lut = lut;
+    a.src_frames = src_frames; a.src_rows = src_rows; a.src_idx = src_idx;
+    a.store = store_frames; a.store_y = store_labels; a.store_rows = store_rows; a.row0 = ring_row0; a.ring = ring_rows;
+    a.gather = gather_rows; a.params = gather_params; a.E = E;
+    a.x_mix = x_mix; a.y_mix = labels_mix;
+    a.rpb = cf_rows_per_block(tw);
+    a.chunks = (th + a.rpb - 1) / a.rpb;
+    const size_t row_blocks = (row_elems + ASM_SEG - 1) / ASM_SEG, frame_blocks = (frame_elems + asm_seg<T> - 1) / asm_seg<T>;
+    const size_t crop_blocks = (size_t)C * a.chunks;
+    const size_t blocks = copy_rows * row_blocks + ring_rows * frame_blocks + E * crop_blocks;
+    if (row_blocks > 0xffffu || frame_blocks > 0xffffu || crop_blocks > 0xffffu || blocks > 0x7fffffffull) return CLHIP_EINVAL;
+    a.row_blocks = (unsigned)row_blocks; a.frame_blocks = (unsigned)frame_blocks; a.crop_blocks = (unsigned)crop_blocks;
+    a.vec_row = row_elems % 4 == 0 && aligned16(x) && aligned16(x_mix);
+    a.vec_frame = (frame_elems * sizeof(T)) % 16 == 0 && aligned16(src_frames) && aligned16(store_frames);
+    if (tw % 4 == 0 && aligned16(x_mix))
+        hipLaunchKernelGGL((rehearsal_assemble_cf_kernel<true, T>), dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL((rehearsal_assemble_cf_kernel<false, T>), dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" {
 
@@ -189,43 +269,19 @@ int clhip_rehearsal_assemble_crop_flip(const float* x, const int64_t* labels_i64
                                        int64_t* store_labels, long store_rows, long ring_row0, int ring_rows,
                                        const int* gather_rows, const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
                                        void* stream) {
-    if (B < 0 || E < 0 || ring_rows < 0 || store_rows < 0 || src_rows < 0) return CLHIP_EINVAL;
-    if (C < 1 || th < 1 || tw < 1 || th > Hs || tw > Ws) return CLHIP_EINVAL;
-    if (ring_rows > B) return CLHIP_EINVAL;                                      // ring rows are a prefix of the batch
-    if (E > 0 && (!x_mix || !gather_rows || !gather_params)) return CLHIP_EINVAL;
-    const int copy_rows = x_mix ? B : 0;                                         // no x_mix (E == 0): the ring update alone
-    if (copy_rows > 0 && !x) return CLHIP_EINVAL;
-    if ((copy_rows > 0 || ring_rows > 0) && !labels_i64) return CLHIP_EINVAL;
-    if ((copy_rows > 0 || E > 0) && !labels_mix) return CLHIP_EINVAL;
-    if (ring_rows > 0 && (!src_frames || !src_idx)) return CLHIP_EINVAL;
-    if ((ring_rows > 0 || E > 0) && (!store_frames || !store_labels)) return CLHIP_EINVAL;
-    if (ring_rows > 0 && (ring_row0 < 0 || ring_row0 + ring_rows > store_rows)) return CLHIP_EINVAL;
-    const long rows = (long)copy_rows + ring_rows + E;
-    if (rows == 0) return 0;
-    if (rows > 65535) return CLHIP_EINVAL;
-    const size_t row_elems = (size_t)C * th * tw, frame_elems = (size_t)C * Hs * Ws;
-    assemble_cf_args a;
-    a.x = x; a.y = labels_i64; a.B = B; a.copy_rows = copy_rows;
-    a.C = C; a.Hs = Hs; a.Ws = Ws; a.th = th; a.tw = tw;
-    a.src_frames = src_frames; a.src_rows = src_rows; a.src_idx = src_idx;
-    a.store = store_frames; a.store_y = store_labels; a.store_rows = store_rows; a.row0 = ring_row0; a.ring = ring_rows;
-    a.gather = gather_rows; a.params = gather_params; a.E = E;
-    a.x_mix = x_mix; a.y_mix = labels_mix;
-    a.rpb = cf_rows_per_block(tw);
-    a.chunks = (th + a.rpb - 1) / a.rpb;
-    const size_t row_blocks = (row_elems + ASM_SEG - 1) / ASM_SEG, frame_blocks = (frame_elems + ASM_SEG - 1) / ASM_SEG;
-    const size_t crop_blocks = (size_t)C * a.chunks;
-    const size_t blocks = copy_rows * row_blocks + ring_rows * frame_blocks + E * crop_blocks;
-    if (row_blocks > 0xffffu || frame_blocks > 0xffffu || crop_blocks > 0xffffu || blocks > 0x7fffffffull) return CLHIP_EINVAL;
-    a.row_blocks = (unsigned)row_blocks; a.frame_blocks = (unsigned)frame_blocks; a.crop_blocks = (unsigned)crop_blocks;
-    a.vec_row = row_elems % 4 == 0 && aligned16(x) && aligned16(x_mix);
-    a.vec_frame = frame_elems % 4 == 0 && aligned16(src_frames) && aligned16(store_frames);
-    if (tw % 4 == 0 && aligned16(x_mix))
-        hipLaunchKernelGGL(rehearsal_assemble_cf_kernel<true>, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
-    else
-        hipLaunchKernelGGL(rehearsal_assemble_cf_kernel<false>, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
-    CLHIP_LAUNCH_CHECK();
-    return 0;
+    return assemble_crop_flip<float>(x, labels_i64, B, C, Hs, Ws, th, tw, nullptr, src_frames, src_rows, src_idx, store_frames,
+                                     store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
+                                     labels_mix, stream);
+}
+
+int clhip_rehearsal_assemble_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                          const float* lut, const uint8_t* src_frames, long src_rows, const int64_t* src_idx,
+                                          uint8_t* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
+                                          int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
+                                          int64_t* labels_mix, void* stream) {
+    return assemble_crop_flip<uint8_t>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, src_frames, src_rows, src_idx, store_frames,
+                                       store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
+                                       labels_mix, stream);
 }
 
 }  // extern "C"

@@ -91,6 +91,10 @@ def build_parser():
                    help="with --synthetic: the task files hold the images as uint8 frames with their mean / std (data.ByteTaskDataset) "
                         "and the loaders normalise them inside their batch gathers: a quarter of the bytes in HBM, bitwise the "
                         "batches of the float files of the same quantised images.  Combines with --rnd_margin / --rnd_resized")
+    p.add_argument("--u8_exemplars", action="store_true",
+                   help="GEM and the rehearsal baselines: the exemplar store holds uint8 frames, decoded where they are replayed (a "
+                        "quarter of the store's bytes in HBM and in every checkpoint, bitwise the run on the decoded files).  "
+                        "Belongs with --u8_frames --rnd_margin: the train splits are augmented byte splits")
     p.add_argument("--rnd_resized", type=int, default=0,
                    help="with --synthetic, instead of --rnd_margin: images are generated M pixels larger than hw and every training "
                         "pass sees a fresh RandomResizedCrop to hw x hw (scale 0.08 - 1, ratio 3/4 - 4/3, antialiased bilinear) + "
@@ -766,6 +770,8 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         raise SystemExit("--rnd_resized belongs to --synthetic: a dataset object says itself which of its files are augmented")
     if args.u8_frames and (dataset is not None or not args.synthetic):
         raise SystemExit("--u8_frames belongs to --synthetic: a dataset object says itself how its files store their frames")
+    if args.u8_exemplars and not (args.u8_frames and args.rnd_margin):
+        raise SystemExit("--u8_exemplars belongs with --u8_frames --rnd_margin: a byte exemplar store holds the frames of augmented byte splits")
     if args.rnd_resized and args.rnd_margin:
         raise SystemExit("--rnd_margin and --rnd_resized exclude each other: a train split carries one transform")
     if args.rnd_resized < 0:

@@ -11,6 +11,11 @@ the current task's train transform (gem.py:233-234, baseline_rehearsal_partial_m
 exemplar is cropped and mirrored afresh at every draw.  A wrapper built with a RandomCropFlip spec does the same: its store
 holds the loader's FRAMES (copied by sample number: BatchSource, the counterpart of the reference's `paths`), `store_ext`-style
 host tables hold each stored frame's valid (h, w), and the crop happens when the exemplars are replayed.
+
+Byte store (frame mode with frame_norm = (mean, std)): the loader holds uint8 frames (data.ByteTaskDataset) and the store holds
+their bytes; a stored byte v of channel c means norm_lut(mean, std)[c][v], decoded where the exemplars are replayed
+(clhip_rehearsal_assemble_crop_flip_u8, GEM: the ..._u8 crop gather of its memory loader).  One table decodes a store, so every
+batch source carries the store's mean and std.
 """
 import collections
 
@@ -19,7 +24,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ..data import RandomCropFlip, draw_crop_flip
+from ..data import RandomCropFlip, draw_crop_flip, norm_lut
 from ..net import NetEngine
 
 FUSED_MAX_ROWS, FUSED_MAX_SEGS = ops.LOSS_MAX_ROWS, ops.LOSS_MAX_SEGS        # the fused loss's limits (include/clhip.h)
@@ -36,8 +41,9 @@ def compute_offsets(task_idx, cum_nc_per_task):
 
 
 # Where a batch of an augmented loader came from: the loader's frame tensor, the sample numbers it just gathered (device and
-# host) and the valid (h, w) of the loader's frames (host int64 [n][2], None: every frame is full).
-BatchSource = collections.namedtuple("BatchSource", ["frames", "idx", "idx_host", "extents"])
+# host), the valid (h, w) of the loader's frames (host int64 [n][2], None: every frame is full) and, for uint8 frames, their
+# (mean, std) (CPU fp32 [C] each; None: the frames are floats).
+BatchSource = collections.namedtuple("BatchSource", ["frames", "idx", "idx_host", "extents", "norm"], defaults=(None,))
 
 
 def batch_source(loader):
@@ -47,7 +53,7 @@ def batch_source(loader):
         return None
     if len(loader.frames) != 1:
         raise ValueError("exemplar frames are copied out of ONE frame tensor (a DeviceLoader over one task)")
-    return BatchSource(loader.frames[0], loader.last_idx, loader.last_idx_host, spec.extents)
+    return BatchSource(loader.frames[0], loader.last_idx, loader.last_idx_host, spec.extents, getattr(loader, "_norm", None))
 
 
 def compact_blocks(tensors, old_stride, new_stride, keep_per_block):
@@ -128,7 +134,7 @@ class ExemplarNet:
     pickle carries the wrapped net, the counters and what _rows_state() returns of the store; engine / workspaces /
     optimizer are rebuilt on load (_bind, then the trainer's init_setup)."""
 
-    _TRANSIENT = ("engine", "A", "stats", "opt", "x_mix", "y_mix", "_acc")
+    _TRANSIENT = ("engine", "A", "stats", "opt", "x_mix", "y_mix", "_acc", "lut")
     _TRANSIENT_POLICY = ()          # the dropout policy's state
     _TRANSIENT_EXTRA = ()           # the subclass's own device state
     _HOST_ROWS = ("_rows_ext",)     # rows of _rows_state() that stay on the host
@@ -136,12 +142,17 @@ class ExemplarNet:
     # class-level defaults: a wrapper pickled before frame mode existed loads in crop mode
     exemplar_transform = None       # RandomCropFlip(size, p) of the replayed exemplars, or None: the store holds crops
     frame_shape = None              # (C, Hs, Ws) of the stored frames
+    frame_norm = None               # (mean, std), CPU fp32 [C] each: the frames are stored as uint8 and mean norm_lut(mean, std)
+    lut = None                      # device fp32 [C][256] of a byte store (transient: rebuilt by _bind)
 
-    def _init_frames(self, exemplar_transform, frame_shape):
-        """Frame mode on (a spec and the frame shape) or off (both None).  in_shape stays the crop shape."""
+    def _init_frames(self, exemplar_transform, frame_shape, frame_norm=None):
+        """Frame mode on (a spec and the frame shape) or off (both None).  in_shape stays the crop shape.  frame_norm = (mean,
+        std): the frames are stored as bytes."""
         if exemplar_transform is None:
             if frame_shape is not None and tuple(frame_shape) != tuple(self.in_shape):
                 raise ValueError("exemplar wrapper: a frame shape needs an exemplar_transform")
+            if frame_norm is not None:
+                raise ValueError("exemplar wrapper: a byte store holds frames (frame_norm needs an exemplar_transform)")
             return
         if not isinstance(exemplar_transform, RandomCropFlip) or frame_shape is None:
             raise TypeError("exemplar wrapper: exemplar_transform is a RandomCropFlip and comes with the frame shape (C, Hs, Ws)")
@@ -151,6 +162,24 @@ class ExemplarNet:
                                                                                  self.in_shape))
         self.exemplar_transform = RandomCropFlip(exemplar_transform.size, exemplar_transform.p)     # (the extents are a task's)
         self.frame_shape = (C, Hs, Ws)
+        if frame_norm is not None:
+            mean, std = (torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(-1).clone() for v in frame_norm)
+            if mean.numel() != C or std.numel() != C:
+                raise ValueError("exemplar wrapper: %d channels, %d means, %d stds" % (C, mean.numel(), std.numel()))
+            self.frame_norm = (mean, std)
+
+    @property
+    def store_dtype(self):
+        """Element type of the exemplar store."""
+        return torch.float32 if self.frame_norm is None else torch.uint8
+
+    def _assemble(self, *args):
+        """The frame-mode assembly launch of this wrapper's store kind (ops.rehearsal_assemble_crop_flip's arguments after the
+        geometry)."""
+        if self.frame_norm is None:
+            ops.rehearsal_assemble_crop_flip(self.geometry, *args)
+        else:
+            ops.rehearsal_assemble_crop_flip_u8(self.geometry, self.lut, *args)
 
     @property
     def store_shape(self):
@@ -176,6 +205,14 @@ class ExemplarNet:
                              "(pass batch_source(loader))")
         if tuple(source.frames.shape[1:]) != self.frame_shape:
             raise ValueError("exemplar wrapper: frames %s, store %s" % (tuple(source.frames.shape[1:]), self.frame_shape))
+        if source.frames.dtype != self.store_dtype or (source.norm is None) != (self.frame_norm is None):
+            raise ValueError("exemplar wrapper: %s frames %s mean / std for a %s store (a byte store takes byte frames with their "
+                             "mean and std, an fp32 store float frames)"
+                             % (source.frames.dtype, "without" if source.norm is None else "with", self.store_dtype))
+        if self.frame_norm is not None and not all(torch.equal(torch.as_tensor(a, dtype=torch.float32).cpu().reshape(-1), b)
+                                                   for a, b in zip(source.norm, self.frame_norm)):
+            raise ValueError("exemplar wrapper: one table decodes a byte store; the batch's mean / std %s differ from the store's %s"
+                             % ([torch.as_tensor(v).tolist() for v in source.norm], [v.tolist() for v in self.frame_norm]))
 
     def _source_ext(self, source, n):
         """Host int64 [n][2]: the valid (h, w) of the first n samples of the batch."""
@@ -198,6 +235,7 @@ class ExemplarNet:
         self.engine.auto_dropout = False        # the masks are the wrapper's own (its dropout policy), not the engine's
         self.A = self.engine.arena
         self.stats = torch.zeros(2, dtype=torch.float64, device=self.device)
+        self.lut = None if self.frame_norm is None else norm_lut(*self.frame_norm).to(self.device)
         if mix:
             self.x_mix = torch.empty((rows,) + self.in_shape, dtype=torch.float32, device=self.device)
             self.y_mix = torch.empty((rows,), dtype=torch.int64, device=self.device)

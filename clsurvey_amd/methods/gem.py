@@ -9,7 +9,8 @@ runs on the device in float64 (clhip_gem_qp) — no host round trip per batch.
 
 Frame mode (exemplar.py): memory[t] holds the loader's frames, fill_buffer copies them by sample number (the ring-only form of
 clhip_rehearsal_assemble_crop_flip), and a past-task pass serves memory[t] through the augmented DeviceLoader, a fresh crop
-and flip per exemplar per pass as gem.py:233-234 rebuilds its ImagePathlist with the train transform.
+and flip per exemplar per pass as gem.py:233-234 rebuilds its ImagePathlist with the train transform.  With a byte store
+(frame_norm) memory[t] holds uint8 frames and the memory loader is one over a ByteTaskDataset: the ..._u8 crop gather decodes them.
 """
 import copy
 import ctypes as C
@@ -19,7 +20,7 @@ import torch.nn as nn
 
 from .. import _lib, ops
 from .._lib import check
-from ..data import DeviceLoader, RandomCropFlip, TensorTaskDataset
+from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, TensorTaskDataset
 from ..optim import SGD
 from .exemplar import ExemplarNet, SharedRowDropout, _stream, batch_source, compute_offsets  # noqa: F401  (compute_offsets: imported from here)
 
@@ -43,14 +44,14 @@ class GemNet(SharedRowDropout, ExemplarNet):
     _TRANSIENT_EXTRA = ("G", "_gram_ws", "_gram", "_v", "_info", "_qp_bad", "host_qp")
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, memory_strength=1.0,
-                 batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None):
+                 batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None, frame_norm=None):
         self.net = model.to(device)
         self.device = torch.device(device)
         self.n_outputs, self.n_tasks, self.n_memories = n_outputs, n_tasks, n_memories
         self.batch_size = batch_size
         self.in_shape = tuple(in_shape)
-        self._init_frames(exemplar_transform, frame_shape)
-        self.memory_x = torch.zeros((n_tasks, n_memories) + self.store_shape, dtype=torch.float32, device=self.device)
+        self._init_frames(exemplar_transform, frame_shape, frame_norm)
+        self.memory_x = torch.zeros((n_tasks, n_memories) + self.store_shape, dtype=self.store_dtype, device=self.device)
         self.memory_labels = torch.zeros((n_tasks, n_memories), dtype=torch.int64, device=self.device)
         if self.exemplar_transform is not None:                     # host: valid (h, w) of every stored frame
             self.memory_ext = self._full_ext(n_tasks * n_memories).view(n_tasks, n_memories, 2)
@@ -87,9 +88,8 @@ class GemNet(SharedRowDropout, ExemplarNet):
         endcnt = min(self.mem_cnt + bsz, self.n_memories)
         eff = endcnt - self.mem_cnt
         if self.exemplar_transform is not None:
-            ops.rehearsal_assemble_crop_flip(self.geometry, None, y, bsz, source.frames, source.idx,
-                                             self.memory_x.view((-1,) + self.frame_shape), self.memory_labels.view(-1),
-                                             t * self.n_memories + self.mem_cnt, eff, None, None, None, None)
+            self._assemble(None, y, bsz, source.frames, source.idx, self.memory_x.view((-1,) + self.frame_shape),
+                           self.memory_labels.view(-1), t * self.n_memories + self.mem_cnt, eff, None, None, None, None)
             self.memory_ext[t, self.mem_cnt:endcnt] = self._source_ext(source, eff)
         else:
             self.memory_x[t, self.mem_cnt:endcnt] = x[:eff]
@@ -111,8 +111,10 @@ class GemNet(SharedRowDropout, ExemplarNet):
 
     def _memory_loader(self, past):
         """The shuffled loader of one past task's memory pass; frame mode: augmented with the stored frames' own extents."""
-        mem = TensorTaskDataset.__new__(TensorTaskDataset)
+        mem = TensorTaskDataset.__new__(TensorTaskDataset) if self.frame_norm is None else ByteTaskDataset.__new__(ByteTaskDataset)
         mem.x, mem.y, mem.classes = self.memory_x[past], self.memory_labels[past], []
+        if self.frame_norm is not None:
+            mem.mean, mem.std = self.frame_norm                     # the ..._u8 crop gather decodes the stored bytes
         if self.exemplar_transform is not None:
             mem.transform = RandomCropFlip(self.exemplar_transform.size, self.exemplar_transform.p, self.memory_ext[past])
         return DeviceLoader(mem, self.batch_size, True, self.device)

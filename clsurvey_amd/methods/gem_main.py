@@ -17,7 +17,7 @@ import numpy as np
 import torch
 from ..data import load_task_datasets
 
-from ..data import ByteTaskDataset, DeviceLoader, RandomResizedCropFlip
+from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, RandomResizedCropFlip
 from .exemplar import batch_source
 from . import gem as G
 from . import rehearsal as R
@@ -131,7 +131,9 @@ def exemplar_split(args, dset_sizes):
 
 
 def main(overwrite_args, nc_per_task, device="cuda"):
-    """main_rehearsal.py:69-255 for method 'gem' and the rehearsal baselines ('baseline_rehearsal_{partial,full}_mem')."""
+    """main_rehearsal.py:69-255 for method 'gem' and the rehearsal baselines ('baseline_rehearsal_{partial,full}_mem').
+    overwrite_args['exemplar_dtype'] (not in the reference; default 'float32'): 'uint8' stores the exemplars of an augmented byte
+    train split as byte frames (exemplar.py, byte store)."""
     parser = argparse.ArgumentParser()
     for name, kw in (("--task_name", dict(type=str)), ("--task_count", dict(type=int)),
                      ("--prev_model_path", dict(type=str)), ("--save_path", dict(type=str, default="results/")),
@@ -140,7 +142,8 @@ def main(overwrite_args, nc_per_task, device="cuda"):
                      ("--is_scratch_model", dict(action="store_true")), ("--n_memories", dict(type=int, default=0)),
                      ("--memory_strength", dict(default=0, type=float)), ("--finetune", dict(action="store_true")),
                      ("--n_epochs", dict(type=int, default=1)), ("--batch_size", dict(type=int, default=70)),
-                     ("--lr", dict(type=float, default=1e-3)), ("--n_tasks", dict(type=int, default=10))):
+                     ("--lr", dict(type=float, default=1e-3)), ("--n_tasks", dict(type=int, default=10)),
+                     ("--exemplar_dtype", dict(type=str, default="float32"))):
         parser.add_argument(name, **kw)
     args = parser.parse_known_args([])[0]
     args.nc_per_task = nc_per_task
@@ -168,16 +171,27 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         # the exemplar wrappers replay stored frames through clhip_rehearsal_assemble_crop_flip, which does not resample
         raise NotImplementedError("rehearsal method %r: exemplars are replayed with RandomCropFlip only, the train split carries %r"
                                   % (args.method, dsets["train"].transform))
-    if isinstance(dsets["train"], ByteTaskDataset) and getattr(dsets["train"], "transform", None) is not None:
+    if args.exemplar_dtype not in ("float32", "uint8"):
+        raise ValueError("rehearsal method %r: exemplar_dtype is 'float32' or 'uint8', got %r" % (args.method, args.exemplar_dtype))
+    byte_store = args.exemplar_dtype == "uint8"
+    byte_frames = isinstance(dsets["train"], ByteTaskDataset) and isinstance(getattr(dsets["train"], "transform", None), RandomCropFlip)
+    if byte_store and not byte_frames:
+        raise ValueError("rehearsal method %r: exemplar_dtype='uint8' stores the byte frames of a train split that is a "
+                         "ByteTaskDataset carrying a RandomCropFlip; this one is a %s with transform %r"
+                         % (args.method, type(dsets["train"]).__name__, getattr(dsets["train"], "transform", None)))
+    if isinstance(dsets["train"], ByteTaskDataset) and getattr(dsets["train"], "transform", None) is not None and not byte_store:
         # frame mode copies fp32 frames into an fp32 store; without a transform the store holds the fp32 crops the loader served
-        raise NotImplementedError("rehearsal method %r: the exemplar store holds fp32 frames, the augmented train split holds byte "
-                                  "frames (a byte exemplar store does not exist yet)" % (args.method,))
+        raise NotImplementedError("rehearsal method %r: the default exemplar store holds fp32 frames, the augmented train split holds "
+                                  "byte frames; pass exemplar_dtype='uint8' (the driver's --u8_exemplars) for a byte exemplar store"
+                                  % (args.method,))
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}
     in_shape = tuple(args.dset_loaders["train"].x.shape[1:])
     # a train split with a transform: the wrapper stores frames and re-augments them at every replay (exemplar.py)
     spec = args.dset_loaders["train"].transform
     frames = dict(exemplar_transform=spec, frame_shape=tuple(dsets["train"].x.shape[1:])) if spec is not None else {}
+    if byte_store:
+        frames["frame_norm"] = (dsets["train"].mean, dsets["train"].std)
     if baseline:
         step_rows = exemplar_split(args, dset_sizes)
 
@@ -203,6 +217,9 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         if model.batch_size < args.batch_size:
             model.batch_size = args.batch_size
             model._bind()
+    if (getattr(model, "frame_norm", None) is not None) != byte_store:
+        raise ValueError("rehearsal method %r: exemplar_dtype=%r, the loaded wrapper's exemplar store is %s"
+                         % (args.method, args.exemplar_dtype, "uint8" if getattr(model, "frame_norm", None) is not None else "float32"))
     model.init_setup(args)
     assert model.n_tasks == args.n_tasks, "model tasks={}, args tasks={}".format(model.n_tasks, args.n_tasks)
     assert model.n_outputs == args.n_outputs

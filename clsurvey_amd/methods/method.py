@@ -404,6 +404,8 @@ def _gem_run(self, args, manager, strength, out_dir, prev=None, finetune=False, 
     kw.update(prev_model_path=manager.previous_task_model_path if prev is None else prev, save_path=out_dir,
               n_outputs=sum(nc), memory_strength=strength, n_tasks=manager.dataset.task_count, finetune=finetune,
               is_scratch_model=args.task_counter == 1, postprocess=postprocess)
+    if getattr(args, "u8_exemplars", False):                    # (only then: the recorded trainer arguments stay what they were)
+        kw["exemplar_dtype"] = "uint8"
     manager.overwrite_args = kw
     return _gem.main(kw, nc, device=_dev(args))
 
@@ -486,6 +488,8 @@ def _rehearsal_grid_train(self, args, manager, lr):
               method=self.arg_string, n_memories=args.mem_per_task, n_epochs=args.num_epochs, cuda=True,
               dataset_path=manager.current_task_dataset_path, n_tasks=manager.dataset.task_count,
               batch_size=args.batch_size, lr=lr, finetune=True, is_scratch_model=args.task_counter == 1)
+    if getattr(args, "u8_exemplars", False):                    # (only then: the recorded trainer arguments stay what they were)
+        kw["exemplar_dtype"] = "uint8"
     manager.overwrite_args = kw
     return _gem.main(kw, nc, device=_dev(args))
 

@@ -16,7 +16,8 @@ accumulation with clhip_axpy.
 
 Frame mode (exemplar.py): the store holds the loader's frames, the ring update copies them by sample number, and the step's
 exemplars get one fresh (top, left, flip) each, drawn on the host after the plan and applied by the assembly launch
-(clhip_rehearsal_assemble_crop_flip in place of clhip_rehearsal_assemble; everything after it is the same).
+(clhip_rehearsal_assemble_crop_flip in place of clhip_rehearsal_assemble; everything after it is the same).  With a byte
+store (frame_norm) the launch is clhip_rehearsal_assemble_crop_flip_u8: byte ring rows, exemplars decoded as they are cropped.
 """
 import random
 
@@ -93,7 +94,8 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
     last_gather = last_exemplar_params = None                        # host: the last step's store rows and their draws
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, full_mem_mode=False,
-                 batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None):
+                 batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None,
+                 frame_norm=None):
         self.net = model.to(device)
         self.device = torch.device(device)
         self.n_outputs, self.n_tasks = n_outputs, n_tasks
@@ -103,7 +105,7 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
         self.n_memories = self.n_total_memories if self.full_mem_mode else n_memories
         self.batch_size = batch_size
         self.in_shape = tuple(in_shape)
-        self._init_frames(exemplar_transform, frame_shape)
+        self._init_frames(exemplar_transform, frame_shape, frame_norm)
         self.cum_nc_per_task = [sum(nc_per_task[:i + 1]) for i in range(len(nc_per_task))]
         self.observed_tasks, self.old_task, self.mem_cnt = [], -1, 0
         self.filled = [0] * n_tasks                                 # slots of each task written at least once
@@ -137,7 +139,7 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
 
     def _load_rows(self, rows):
         n = self.n_total_memories
-        self.store_x = torch.zeros((n,) + self.store_shape, dtype=torch.float32, device=self.device)
+        self.store_x = torch.zeros((n,) + self.store_shape, dtype=self.store_dtype, device=self.device)
         self.store_y = torch.zeros((n,), dtype=torch.int64, device=self.device)
         if self.exemplar_transform is not None:
             self.store_ext = self._full_ext(n)                       # host [rows][2]: valid (h, w) of every stored frame
@@ -220,9 +222,8 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
         if frames:
             self.last_exemplar_params = self.exemplar_params(gather, seeds)
             gather_dev, segs_dev, params_dev = self._upload(gather, ops.loss_segment_rows(segs), self.last_exemplar_params)
-            ops.rehearsal_assemble_crop_flip(self.geometry, x, y, B, source.frames, source.idx, self.store_x, self.store_y,
-                                             ring_row0, eff, gather_dev if E else None, params_dev if E else None, self.x_mix,
-                                             self.y_mix)
+            self._assemble(x, y, B, source.frames, source.idx, self.store_x, self.store_y, ring_row0, eff,
+                           gather_dev if E else None, params_dev if E else None, self.x_mix, self.y_mix)
         else:
             gather_dev, segs_dev = self._upload(gather, ops.loss_segment_rows(segs))
             row_elems = int(np.prod(self.in_shape))

@@ -904,30 +904,54 @@ def gather_tasks_resized_crop_flip_u8(table, geometry, lut, idx, params, x_out=N
     return _gather_window_u8("clhip_gather_tasks_resized_crop_flip_u8", 5, table, geometry, lut, idx, params, x_out, labels_out)
 
 
-def rehearsal_assemble_crop_flip(geometry, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows, gather, params,
-                                 x_mix, y_mix):
-    """clhip_rehearsal_assemble_crop_flip: geometry = (C, Hs, Ws, th, tw); store [rows, C, Hs, Ws] frames, x / x_mix rows
-    [C, th, tw].  src_frames / src_idx (device int64) feed the ring rows, gather (device int32[E]) and params (device
-    int32[E, 3]) the exemplar rows; any of them may be None when its count is 0, x_mix None: the ring update alone."""
-    _chk(x, y, src_frames, src_idx, store, store_y, gather, params, x_mix, y_mix)
+def _assemble_crop_flip(entry, frame_dtype, geometry, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows,
+                        gather, params, x_mix, y_mix):
+    _chk(lut, x, y, src_frames, src_idx, store, store_y, gather, params, x_mix, y_mix)
     C, Hs, Ws, th, tw = (int(v) for v in geometry)
     E = 0 if gather is None else int(gather.shape[0])
-    assert store.dtype == torch.float32 and store_y.dtype == torch.int64 and store.numel() == store.shape[0] * C * Hs * Ws
+    assert store.dtype == frame_dtype and store_y.dtype == torch.int64 and store.numel() == store.shape[0] * C * Hs * Ws
     assert store_y.numel() >= store.shape[0]
     assert x is None or (x.dtype == torch.float32 and x.numel() >= B * C * th * tw)
     assert y is None or (y.dtype == torch.int64 and y.numel() >= max(B if x_mix is not None else 0, ring_rows))
     if ring_rows:
-        assert src_frames.dtype == torch.float32 and src_frames.numel() == src_frames.shape[0] * C * Hs * Ws
+        assert src_frames.dtype == frame_dtype and src_frames.numel() == src_frames.shape[0] * C * Hs * Ws
         assert src_idx.dtype == torch.int64 and src_idx.numel() >= ring_rows
     if E:
         assert gather.dtype == torch.int32 and params.dtype == torch.int32 and tuple(params.shape) == (E, 3)
     if x_mix is not None:
         assert x_mix.dtype == torch.float32 and x_mix.numel() >= (B + E) * C * th * tw
         assert y_mix.dtype == torch.int64 and y_mix.numel() >= B + E
-    check(_lib.lib().clhip_rehearsal_assemble_crop_flip(
-        _ptr(x), _ptr(y), B, C, Hs, Ws, th, tw, _ptr(src_frames), 0 if src_frames is None else src_frames.shape[0], _ptr(src_idx),
-        _ptr(store), _ptr(store_y), store.shape[0], ring_row0, ring_rows, _ptr(gather) if E else None, _ptr(params) if E else None,
-        E, _ptr(x_mix), _ptr(y_mix), _stream()), "clhip_rehearsal_assemble_crop_flip")
+    table = ()
+    if frame_dtype == torch.uint8:
+        if E:
+            assert lut is not None, "lut: needed to decode the exemplar rows"
+            _chk_lut(lut, C)
+        table = (_ptr(lut),)
+    check(getattr(_lib.lib(), entry)(
+        _ptr(x), _ptr(y), B, C, Hs, Ws, th, tw, *table, _ptr(src_frames), 0 if src_frames is None else src_frames.shape[0],
+        _ptr(src_idx), _ptr(store), _ptr(store_y), store.shape[0], ring_row0, ring_rows, _ptr(gather) if E else None,
+        _ptr(params) if E else None, E, _ptr(x_mix), _ptr(y_mix), _stream()), entry)
+
+
+def rehearsal_assemble_crop_flip(geometry, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows, gather, params,
+                                 x_mix, y_mix):
+    """clhip_rehearsal_assemble_crop_flip: geometry = (C, Hs, Ws, th, tw); store [rows, C, Hs, Ws] frames, x / x_mix rows
+    [C, th, tw].  src_frames / src_idx (device int64) feed the ring rows, gather (device int32[E]) and params (device
+    int32[E, 3]) the exemplar rows; any of them may be None when its count is 0, x_mix None: the ring update alone."""
+    _assemble_crop_flip("clhip_rehearsal_assemble_crop_flip", torch.float32, geometry, None, x, y, B, src_frames, src_idx, store,
+                        store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix)
+
+
+ASSEMBLE_SEG_BYTES = 256 * 12 * 16        # what one block of the assembly's full-row roles copies (csrc/rehearsal.hip: ASM_SEG_U8)
+
+
+def rehearsal_assemble_crop_flip_u8(geometry, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows, gather, params,
+                                    x_mix, y_mix):
+    """clhip_rehearsal_assemble_crop_flip_u8: rehearsal_assemble_crop_flip with uint8 frames in src_frames and store; the ring rows
+    are byte copies, the exemplar rows are decoded through lut (device float32 [C, 256]; may be None without exemplars): bitwise
+    rehearsal_assemble_crop_flip on the decoded store.  x / x_mix stay float32."""
+    _assemble_crop_flip("clhip_rehearsal_assemble_crop_flip_u8", torch.uint8, geometry, lut, x, y, B, src_frames, src_idx, store,
+                        store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix)
 
 
 def slice_argmax_count(logits, cols, labels, correct, total, out_of_range):

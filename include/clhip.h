@@ -658,7 +658,21 @@ int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T,
  *                       flip) table, plan, taps, summation order and stores: the bytes are decoded through the block's channel
  *                       of the table (staged in LDS; the plan counts its 1 KB) while the source band is staged, everything
  *                       after is the fp32 entry's code.  Same bad rows, CLHIP_EINVAL checks plus lut == NULL, CLHIP_ENOTSUP
- *                       as there (with the table's 1 KB counted).  Byte loads. */
+ *                       as there (with the table's 1 KB counted).  Byte loads.
+ *   rehearsal_assemble_crop_flip_u8   clhip_rehearsal_assemble_crop_flip for a store of BYTE frames: src_frames and store_frames
+ *                       are uint8 [rows][C][Hs][Ws], x and x_mix stay fp32 [C][th][tw] (the loader decoded the current batch):
+ *                         x[0:B)                          -> x_mix[0:B)
+ *                         src_frames[src_idx[i]] (whole)  -> store rows [ring_row0, +ring_rows), the C Hs Ws bytes as they are
+ *                         x_mix[B + e][c][y][x] = lut[c][store[gather_rows[e]][c][top_e + y][left_e + (flip_e ? tw - 1 - x : x)]]
+ *                       Bitwise the fp32 entry on the decoded store, and the stored bytes are bitwise those of the source
+ *                       frames: one table (one mean / std) decodes a store.  Same bad rows (nothing copied, label -1, no
+ *                       address outside a frame formed), same labels, same x_mix == NULL form, same CLHIP_EINVAL checks, plus
+ *                       lut == NULL with E > 0 (a ring-only call decodes nothing and may pass NULL).  Ring rows: 48 KB
+ *                       segments; 16-byte accesses only when C Hs Ws % 16 == 0 and both frame tensors are 16-byte aligned (a
+ *                       frame of odd size starts at any byte), byte accesses otherwise.  Exemplar rows: as
+ *                       gather_tasks_crop_flip_u8 (float4 stores when tw % 4 == 0 and x_mix is 16-byte aligned; byte loads, one
+ *                       dword load per 4 columns only behind a test of that address; the block's channel of the table staged in
+ *                       LDS, 1 KB). */
 typedef struct clhip_task_src_u8 { const uint8_t* x; const int64_t* labels; int64_t cum_rows; int64_t label_shift; } clhip_task_src_u8;
 int clhip_gather_tasks_u8(const clhip_task_src_u8* tasks_dev, int T, int C, size_t plane_elems, const float* lut,
                           const int64_t* idx, int B, float* x_out, int64_t* labels_out, void* stream);
@@ -667,6 +681,11 @@ int clhip_gather_tasks_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, i
 int clhip_gather_tasks_resized_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,
                                             const float* lut, const int64_t* idx, const int* params, int B, float* x_out,
                                             int64_t* labels_out, void* stream);
+int clhip_rehearsal_assemble_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                          const float* lut, const uint8_t* src_frames, long src_rows, const int64_t* src_idx,
+                                          uint8_t* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
+                                          int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
+                                          int64_t* labels_mix, void* stream);
 
 /* ------------------------------------------------------------------ iCaRL
  * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471) and the nearest-mean-of-exemplars classifier of
