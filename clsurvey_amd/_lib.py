@@ -156,6 +156,7 @@ SIGNATURES = {
     "clhip_net_loss_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "clhip_rehearsal_assemble": (_i, [_p, _p, _i, _z, _p, _p, _l, _l, _i, _p, _i, _p, _p, _p]),
     "clhip_rehearsal_assemble_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
+    "clhip_rehearsal_assemble_resized_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
     "clhip_loss_segments": (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _f, _p, _p, _p, _p]),
     "clhip_net_loss_step_loss_segments": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _f, _p, _p, _p, _p, _p]),
     "clhip_gather_tasks": (_i, [_p, _i, _z, _p, _i, _p, _p, _p]),
@@ -166,6 +167,7 @@ SIGNATURES = {
     "clhip_gather_tasks_crop_flip_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "clhip_gather_tasks_resized_crop_flip_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "clhip_rehearsal_assemble_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
+    "clhip_rehearsal_assemble_resized_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
     "clhip_icarl_herd": (_i, [_p, _l, _i, _p, C.POINTER(IcarlClass), _i, _p, _l, _p]),
     "clhip_icarl_nme": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
 }

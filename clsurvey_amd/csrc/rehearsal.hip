@@ -7,7 +7,9 @@
 //                                  are cropped and mirrored in the same launch
 //   rehearsal_assemble_crop_flip_u8  the same with BYTE frames in the store (clhip.h, byte frames): the ring rows are raw byte
 //                                  copies, the gathered exemplars are decoded through the table where they are loaded
-#include "crop_flip.hpp"
+//   rehearsal_assemble_resized_crop_flip[_u8]  the train transform is RandomResizedCrop + flip: the gathered exemplars are
+//                                  RESAMPLED in the same launch, by the block body of the loaders' resizing gather
+#include "resized_crop.hpp"
 #include <type_traits>
 
 namespace {
@@ -127,12 +129,14 @@ struct assemble_cf_args {
     float* x_mix; int64_t* y_mix;
     unsigned row_blocks, frame_blocks, crop_blocks;                            // blocks per row of each run
     int rpb, chunks;                                                           // crop_blocks = C * chunks, rpb lines each
+    int nb, wmax, ktx, kty;                                                    // the rest of the rz_plan (resized entries only)
     int vec_row, vec_frame;                                                    // 16-byte copies of the two full-row roles
 };
 
-template <bool VEC_CROP, typename T>
-__global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const assemble_cf_args<T> a) {
-    unsigned b = blockIdx.x;
+// The copy and ring runs of the 1-D grid, shared by the frame-mode kernels.  True: block b served one of them; false: b is now
+// the block's number inside the exemplar run.  Block-uniform.
+template <typename T>
+__device__ __forceinline__ bool assemble_copy_ring(const assemble_cf_args<T>& a, unsigned& b) {
     const size_t row_elems = (size_t)a.C * a.th * a.tw, frame_elems = (size_t)a.C * a.Hs * a.Ws;
     const unsigned n_row = (unsigned)a.copy_rows * a.row_blocks, n_ring = (unsigned)a.ring * a.frame_blocks;
     if (b < n_row) {
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const 
         if (seg == 0 && threadIdx.x == 0) a.y_mix[r] = a.y[r];
         if (a.vec_row) copy_segment<true>(a.x + r * row_elems, a.x_mix + r * row_elems, row_elems, seg);
         else copy_segment<false>(a.x + r * row_elems, a.x_mix + r * row_elems, row_elems, seg);
-        return;
+        return true;
     }
     b -= n_row;
     if (b < n_ring) {
@@ -151,16 +155,23 @@ __global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const 
         int64_t* ydst = a.store_y + a.row0 + i;
         if (s < 0 || s >= a.src_rows) {
             if (seg == 0 && threadIdx.x == 0) *ydst = -1;
-            return;
+            return true;
         }
         if (seg == 0 && threadIdx.x == 0) *ydst = a.y[i];
         const T* src = a.src_frames + (size_t)s * frame_elems;
         T* dst = a.store + (size_t)(a.row0 + i) * frame_elems;
         if (a.vec_frame) copy_segment<true>(src, dst, frame_elems, seg);
         else copy_segment<false>(src, dst, frame_elems, seg);
-        return;
+        return true;
     }
     b -= n_ring;
+    return false;
+}
+
+template <bool VEC_CROP, typename T>
+__global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const assemble_cf_args<T> a) {
+    unsigned b = blockIdx.x;
+    if (assemble_copy_ring(a, b)) return;
     // (the role and the bad-row test are block-uniform: every thread of a block reaches the barrier below or none does)
     const unsigned e = b / a.crop_blocks;
     const int k = (int)(b - e * a.crop_blocks);
@@ -188,16 +199,57 @@ __global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_cf_kernel(const 
     }
 }
 
+// The frame-mode assembly under RandomResizedCrop + flip: the grid and the copy / ring runs of rehearsal_assemble_cf_kernel; the
+// exemplar run is E x (C * chunks) blocks of the launch's rz_plan, each resampling the (top, left, h, w) window of
+// store[gather[e]] to rpb output lines of x_mix[B + e] by rz_resample_block (resized_crop.hpp), the block body of
+// gather_resized_kernel (augment.hip): bitwise that gather's result for the same frame and window.  params: int32[E][5] of
+// (top, left, h, w, flip).  The launch's dynamic LDS is the plan's (the copy and ring blocks carry it unused).
+// A gather row outside [0, store_rows), h < 1, w < 1, top < 0, left < 0, top + h > Hs, left + w > Ws, flip outside {0, 1},
+// h > CLHIP_RESIZE_MAX_RATIO th or w > CLHIP_RESIZE_MAX_RATIO tw copies nothing and writes label -1 (the gather's rule); no
+// address outside a frame is formed.
+template <bool VEC, typename T>
+__global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_rz_kernel(const assemble_cf_args<T> a) {
+    extern __shared__ __attribute__((aligned(16))) float asm_rz_lds[];
+    unsigned b = blockIdx.x;
+    if (assemble_copy_ring(a, b)) return;
+    // (the role and the bad-row test are block-uniform: every thread of a block reaches the body's barriers or none does)
+    const unsigned e = b / a.crop_blocks;
+    const int k = (int)(b - e * a.crop_blocks);
+    const long g = a.gather[e];
+    const int top = a.params[5 * e], left = a.params[5 * e + 1], h = a.params[5 * e + 2], w = a.params[5 * e + 3],
+              flip = a.params[5 * e + 4];
+    int64_t* ydst = a.y_mix + a.B + e;
+    if (g < 0 || g >= a.store_rows || h < 1 || w < 1 || top < 0 || left < 0 || top > a.Hs - h || left > a.Ws - w ||
+        (flip != 0 && flip != 1) || (int64_t)h > (int64_t)CLHIP_RESIZE_MAX_RATIO * a.th ||
+        (int64_t)w > (int64_t)CLHIP_RESIZE_MAX_RATIO * a.tw) {
+        if (k == 0 && threadIdx.x == 0) *ydst = -1;
+        return;
+    }
+    if (k == 0 && threadIdx.x == 0) *ydst = a.store_y[g];
+    const int c = k / a.chunks;
+    const int y0 = (k - c * a.chunks) * a.rpb;
+    const int nrows = min(a.rpb, a.th - y0);
+    constexpr bool U8 = std::is_same<T, uint8_t>::value;
+    typedef const T __attribute__((address_space(1))) gelem;                   // (device memory: global_load, not flat_load)
+    gelem* plane = (gelem*)(a.store + ((size_t)g * a.C + c) * a.Hs * a.Ws);
+    const float* lut_c = nullptr;
+    if constexpr (U8) lut_c = a.lut + c * 256;
+    rz_resample_block<VEC, U8>(asm_rz_lds, plane, a.Ws, top, left, h, w, flip, a.th, a.tw, y0, nrows, a.rpb, a.nb, a.wmax, a.ktx,
+                               a.kty, lut_c, a.x_mix + (((size_t)(a.B + e) * a.C + c) * a.th + y0) * a.tw);
+}
+
 }  // namespace
 
-// One body for the pair of frame-mode entries: T selects the frames' element type, lut is NULL for floats.
-template <typename T>
-static int assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
-                              const float* lut, const T* src_frames, long src_rows, const int64_t* src_idx, T* store_frames,
-                              int64_t* store_labels, long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
-                              const int* gather_params, int E, float* x_mix, int64_t* labels_mix, void* stream) {
+// One body for the frame-mode entries: T selects the frames' element type, lut is NULL for floats; RESIZED: gather_params rows
+// are (top, left, h, w, flip) and the exemplar run resamples, under a plan made here for the frame (needed only with E > 0).
+template <typename T, bool RESIZED>
+static int assemble_frames(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                           const float* lut, const T* src_frames, long src_rows, const int64_t* src_idx, T* store_frames,
+                           int64_t* store_labels, long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
+                           const int* gather_params, int E, float* x_mix, int64_t* labels_mix, void* stream) {
     if (B < 0 || E < 0 || ring_rows < 0 || store_rows < 0 || src_rows < 0) return CLHIP_EINVAL;
-    if (C < 1 || th < 1 || tw < 1 || th > Hs || tw > Ws) return CLHIP_EINVAL;
+    if (C < 1 || th < 1 || tw < 1 || Hs < 1 || Ws < 1) return CLHIP_EINVAL;
+    if (!RESIZED && (th > Hs || tw > Ws)) return CLHIP_EINVAL;                   // (a resized window may be enlarged)
     if (ring_rows > B) return CLHIP_EINVAL;                                      // ring rows are a prefix of the batch
     if (E > 0 && (!x_mix || !gather_rows || !gather_params)) return CLHIP_EINVAL;
     if (std::is_same<T, uint8_t>::value && E > 0 && !lut) return CLHIP_EINVAL;   // (a ring-only call decodes nothing)
@@ -222,6 +274,14 @@ static int assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, 
     a.x_mix = x_mix; a.y_mix = labels_mix;
     a.rpb = cf_rows_per_block(tw);
     a.chunks = (th + a.rpb - 1) / a.rpb;
+    a.nb = a.wmax = a.ktx = a.kty = 0;
+    size_t lds = 0;
+    if (RESIZED && E > 0) {
+        rz_plan p;
+        if (!rz_make_plan(Hs, Ws, th, tw, std::is_same<T, uint8_t>::value ? 256 * sizeof(float) : 0, &p)) return CLHIP_ENOTSUP;
+        a.rpb = p.rpb; a.chunks = p.chunks; a.nb = p.nb; a.wmax = p.wmax; a.ktx = p.ktx; a.kty = p.kty;
+        lds = p.lds;
+    }
     const size_t row_blocks = (row_elems + ASM_SEG - 1) / ASM_SEG, frame_blocks = (frame_elems + asm_seg<T> - 1) / asm_seg<T>;
     const size_t crop_blocks = (size_t)C * a.chunks;
     const size_t blocks = copy_rows * row_blocks + ring_rows * frame_blocks + E * crop_blocks;
@@ -229,10 +289,15 @@ static int assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, 
     a.row_blocks = (unsigned)row_blocks; a.frame_blocks = (unsigned)frame_blocks; a.crop_blocks = (unsigned)crop_blocks;
     a.vec_row = row_elems % 4 == 0 && aligned16(x) && aligned16(x_mix);
     a.vec_frame = (frame_elems * sizeof(T)) % 16 == 0 && aligned16(src_frames) && aligned16(store_frames);
-    if (tw % 4 == 0 && aligned16(x_mix))
-        hipLaunchKernelGGL((rehearsal_assemble_cf_kernel<true, T>), dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
-    else
-        hipLaunchKernelGGL((rehearsal_assemble_cf_kernel<false, T>), dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, as_stream(stream), a);
+    const bool vec = tw % 4 == 0 && aligned16(x_mix);
+    const dim3 grid((unsigned)blocks), block(ASM_BLOCK);
+    if constexpr (RESIZED) {
+        if (vec) hipLaunchKernelGGL((rehearsal_assemble_rz_kernel<true, T>), grid, block, lds, as_stream(stream), a);
+        else hipLaunchKernelGGL((rehearsal_assemble_rz_kernel<false, T>), grid, block, lds, as_stream(stream), a);
+    } else {
+        if (vec) hipLaunchKernelGGL((rehearsal_assemble_cf_kernel<true, T>), grid, block, 0, as_stream(stream), a);
+        else hipLaunchKernelGGL((rehearsal_assemble_cf_kernel<false, T>), grid, block, 0, as_stream(stream), a);
+    }
     CLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -269,7 +334,7 @@ int clhip_rehearsal_assemble_crop_flip(const float* x, const int64_t* labels_i64
                                        int64_t* store_labels, long store_rows, long ring_row0, int ring_rows,
                                        const int* gather_rows, const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
                                        void* stream) {
-    return assemble_crop_flip<float>(x, labels_i64, B, C, Hs, Ws, th, tw, nullptr, src_frames, src_rows, src_idx, store_frames,
+    return assemble_frames<float, false>(x, labels_i64, B, C, Hs, Ws, th, tw, nullptr, src_frames, src_rows, src_idx, store_frames,
                                      store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
                                      labels_mix, stream);
 }
@@ -279,9 +344,30 @@ int clhip_rehearsal_assemble_crop_flip_u8(const float* x, const int64_t* labels_
                                           uint8_t* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
                                           int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
                                           int64_t* labels_mix, void* stream) {
-    return assemble_crop_flip<uint8_t>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, src_frames, src_rows, src_idx, store_frames,
+    return assemble_frames<uint8_t, false>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, src_frames, src_rows, src_idx, store_frames,
                                        store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
                                        labels_mix, stream);
+}
+
+int clhip_rehearsal_assemble_resized_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th,
+                                               int tw, const float* src_frames, long src_rows, const int64_t* src_idx,
+                                               float* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
+                                               int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
+                                               int64_t* labels_mix, void* stream) {
+    return assemble_frames<float, true>(x, labels_i64, B, C, Hs, Ws, th, tw, nullptr, src_frames, src_rows, src_idx, store_frames,
+                                        store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
+                                        labels_mix, stream);
+}
+
+int clhip_rehearsal_assemble_resized_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th,
+                                                  int tw, const float* lut, const uint8_t* src_frames, long src_rows,
+                                                  const int64_t* src_idx, uint8_t* store_frames, int64_t* store_labels,
+                                                  long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
+                                                  const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
+                                                  void* stream) {
+    return assemble_frames<uint8_t, true>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, src_frames, src_rows, src_idx, store_frames,
+                                          store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
+                                          labels_mix, stream);
 }
 
 }  // extern "C"

@@ -94,7 +94,12 @@ def build_parser():
     p.add_argument("--u8_exemplars", action="store_true",
                    help="GEM and the rehearsal baselines: the exemplar store holds uint8 frames, decoded where they are replayed (a "
                         "quarter of the store's bytes in HBM and in every checkpoint, bitwise the run on the decoded files).  "
-                        "Belongs with --u8_frames --rnd_margin: the train splits are augmented byte splits")
+                        "Belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars): the train "
+                        "splits are augmented byte splits")
+    p.add_argument("--resized_exemplars", action="store_true",
+                   help="GEM and the rehearsal baselines with --rnd_resized: the stored exemplar frames are replayed through the "
+                        "task's RandomResizedCrop + flip, a fresh window per exemplar and replay, resampled inside the step's batch "
+                        "assembly launch.  Without it these methods refuse --rnd_resized tasks")
     p.add_argument("--rnd_resized", type=int, default=0,
                    help="with --synthetic, instead of --rnd_margin: images are generated M pixels larger than hw and every training "
                         "pass sees a fresh RandomResizedCrop to hw x hw (scale 0.08 - 1, ratio 3/4 - 4/3, antialiased bilinear) + "
@@ -770,8 +775,11 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         raise SystemExit("--rnd_resized belongs to --synthetic: a dataset object says itself which of its files are augmented")
     if args.u8_frames and (dataset is not None or not args.synthetic):
         raise SystemExit("--u8_frames belongs to --synthetic: a dataset object says itself how its files store their frames")
-    if args.u8_exemplars and not (args.u8_frames and args.rnd_margin):
-        raise SystemExit("--u8_exemplars belongs with --u8_frames --rnd_margin: a byte exemplar store holds the frames of augmented byte splits")
+    if args.resized_exemplars and not args.rnd_resized:
+        raise SystemExit("--resized_exemplars belongs with --rnd_resized: it replays the exemplars through the tasks' RandomResizedCrop")
+    if args.u8_exemplars and not (args.u8_frames and (args.rnd_margin or (args.rnd_resized and args.resized_exemplars))):
+        raise SystemExit("--u8_exemplars belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars): a "
+                         "byte exemplar store holds the frames of augmented byte splits")
     if args.rnd_resized and args.rnd_margin:
         raise SystemExit("--rnd_margin and --rnd_resized exclude each other: a train split carries one transform")
     if args.rnd_resized < 0:

@@ -16,6 +16,11 @@ Byte store (frame mode with frame_norm = (mean, std)): the loader holds uint8 fr
 their bytes; a stored byte v of channel c means norm_lut(mean, std)[c][v], decoded where the exemplars are replayed
 (clhip_rehearsal_assemble_crop_flip_u8, GEM: the ..._u8 crop gather of its memory loader).  One table decodes a store, so every
 batch source carries the store's mean and std.
+
+Resized replay (frame mode with a RandomResizedCropFlip spec, the cropped Tiny-ImageNet rule): the replayed exemplar is a fresh
+RandomResizedCrop window of its stored frame, drawn over the frame's own extent and resampled inside the assembly launch
+(clhip_rehearsal_assemble_resized_crop_flip[_u8], the block body of the loaders' resizing gather); the draws are rows of
+(top, left, h, w, flip).  Store, ring update and extents are those of frame mode.
 """
 import collections
 
@@ -24,7 +29,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ..data import RandomCropFlip, draw_crop_flip, norm_lut
+from ..data import RandomCropFlip, RandomResizedCropFlip, _respec, draw_crop_flip, draw_resized_crop_flip, norm_lut
 from ..net import NetEngine
 
 FUSED_MAX_ROWS, FUSED_MAX_SEGS = ops.LOSS_MAX_ROWS, ops.LOSS_MAX_SEGS        # the fused loss's limits (include/clhip.h)
@@ -140,7 +145,8 @@ class ExemplarNet:
     _HOST_ROWS = ("_rows_ext",)     # rows of _rows_state() that stay on the host
 
     # class-level defaults: a wrapper pickled before frame mode existed loads in crop mode
-    exemplar_transform = None       # RandomCropFlip(size, p) of the replayed exemplars, or None: the store holds crops
+    exemplar_transform = None       # RandomCropFlip(size, p) or RandomResizedCropFlip(size, scale, ratio, p) of the replayed
+                                    # exemplars, or None: the store holds crops
     frame_shape = None              # (C, Hs, Ws) of the stored frames
     frame_norm = None               # (mean, std), CPU fp32 [C] each: the frames are stored as uint8 and mean norm_lut(mean, std)
     lut = None                      # device fp32 [C][256] of a byte store (transient: rebuilt by _bind)
@@ -154,13 +160,14 @@ class ExemplarNet:
             if frame_norm is not None:
                 raise ValueError("exemplar wrapper: a byte store holds frames (frame_norm needs an exemplar_transform)")
             return
-        if not isinstance(exemplar_transform, RandomCropFlip) or frame_shape is None:
-            raise TypeError("exemplar wrapper: exemplar_transform is a RandomCropFlip and comes with the frame shape (C, Hs, Ws)")
+        if not isinstance(exemplar_transform, (RandomCropFlip, RandomResizedCropFlip)) or frame_shape is None:
+            raise TypeError("exemplar wrapper: exemplar_transform is a RandomCropFlip and comes with the frame shape (C, Hs, Ws) "
+                            "(or a RandomResizedCropFlip: resized replay)")
         C, Hs, Ws = (int(v) for v in frame_shape)
         if (C,) + exemplar_transform.size != tuple(self.in_shape) or Hs < self.in_shape[1] or Ws < self.in_shape[2]:
             raise ValueError("exemplar wrapper: frames %s, crop %s, net input %s" % (tuple(frame_shape), exemplar_transform.size,
                                                                                  self.in_shape))
-        self.exemplar_transform = RandomCropFlip(exemplar_transform.size, exemplar_transform.p)     # (the extents are a task's)
+        self.exemplar_transform = _respec(exemplar_transform)                                       # (the extents are a task's)
         self.frame_shape = (C, Hs, Ws)
         if frame_norm is not None:
             mean, std = (torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(-1).clone() for v in frame_norm)
@@ -173,13 +180,20 @@ class ExemplarNet:
         """Element type of the exemplar store."""
         return torch.float32 if self.frame_norm is None else torch.uint8
 
+    @property
+    def params_width(self):
+        """Columns of an exemplar's draw: (top, left, flip), or (top, left, h, w, flip) of a resized spec."""
+        return 5 if isinstance(self.exemplar_transform, RandomResizedCropFlip) else 3
+
     def _assemble(self, *args):
-        """The frame-mode assembly launch of this wrapper's store kind (ops.rehearsal_assemble_crop_flip's arguments after the
-        geometry)."""
+        """The frame-mode assembly launch of this wrapper's spec and store kind (ops.rehearsal_assemble_crop_flip's arguments
+        after the geometry)."""
+        resized = isinstance(self.exemplar_transform, RandomResizedCropFlip)
         if self.frame_norm is None:
-            ops.rehearsal_assemble_crop_flip(self.geometry, *args)
+            (ops.rehearsal_assemble_resized_crop_flip if resized else ops.rehearsal_assemble_crop_flip)(self.geometry, *args)
         else:
-            ops.rehearsal_assemble_crop_flip_u8(self.geometry, self.lut, *args)
+            (ops.rehearsal_assemble_resized_crop_flip_u8 if resized else ops.rehearsal_assemble_crop_flip_u8)(
+                self.geometry, self.lut, *args)
 
     @property
     def store_shape(self):
@@ -222,11 +236,13 @@ class ExemplarNet:
 
     def draw_exemplar_params(self, ext, seed):
         """Host int32 [n][3] of (top, left, flip) for exemplars whose frames have the valid sizes ext [n][2], in that order, from
-        a private CPU generator: the global one is not touched (DeviceLoader's rule for its epoch table)."""
+        a private CPU generator: the global one is not touched (DeviceLoader's rule for its epoch table).  A resized spec:
+        [n][5] of (top, left, h, w, flip), RandomResizedCrop's windows over the same extents."""
         g = torch.Generator()
         g.manual_seed(seed)
-        spec = RandomCropFlip(self.exemplar_transform.size, self.exemplar_transform.p, ext)
-        return draw_crop_flip(ext.shape[0], spec, self.frame_shape[1:], g)
+        spec = _respec(self.exemplar_transform, ext)
+        draw = draw_resized_crop_flip if isinstance(spec, RandomResizedCropFlip) else draw_crop_flip
+        return draw(ext.shape[0], spec, self.frame_shape[1:], g)
 
     def _bind(self, mix=True):
         """Engine and work buffers; mix: the [current batch | exemplar chunks] rows of a step."""
@@ -286,10 +302,11 @@ class ExemplarNet:
     # ------------------------------------------------------------------ the step over [current batch | exemplar chunks]
     def _upload(self, gather, rows, params=None):
         """Gather rows (int32), rows of int32 columns (clhip_loss_segment tables: ops.loss_segment_rows) and, in frame mode, the
-        exemplars' (top, left, flip) rows (int32 [len(gather)][3]) in ONE pinned host buffer, one non-blocking copy.  Returns
+        exemplars' draws (int32 [len(gather)][params_width]) in ONE pinned host buffer, one non-blocking copy.  Returns
         the device parts, the second one flat; the third one only when params is given."""
         n, m = len(gather), rows.size
-        pinned = torch.empty(n + m + (0 if params is None else 3 * n), dtype=torch.int32, pin_memory=True)
+        width = 0 if params is None else self.params_width
+        pinned = torch.empty(n + m + width * n, dtype=torch.int32, pin_memory=True)
         host = pinned.numpy()
         host[:n] = gather
         host[n:n + m] = rows.reshape(-1)
@@ -298,7 +315,7 @@ class ExemplarNet:
         dev = pinned.to(self.device, non_blocking=True)     # the caching host allocator keeps `pinned` until the copy ran
         if params is None:
             return dev[:n], dev[n:]
-        return dev[:n], dev[n:n + m], dev[n + m:].view(n, 3)
+        return dev[:n], dev[n:n + m], dev[n + m:].view(n, width)
 
     def _fused(self, N, n_segs):
         """One fused pass, or segment by segment: a plan with BatchNorm normalises every chunk with its own statistics, and

@@ -11,6 +11,7 @@ Frame mode (exemplar.py): memory[t] holds the loader's frames, fill_buffer copie
 clhip_rehearsal_assemble_crop_flip), and a past-task pass serves memory[t] through the augmented DeviceLoader, a fresh crop
 and flip per exemplar per pass as gem.py:233-234 rebuilds its ImagePathlist with the train transform.  With a byte store
 (frame_norm) memory[t] holds uint8 frames and the memory loader is one over a ByteTaskDataset: the ..._u8 crop gather decodes them.
+With a RandomResizedCropFlip spec the memory loader carries it, so a past-task pass runs the loaders' resizing gather.
 """
 import copy
 import ctypes as C
@@ -20,7 +21,7 @@ import torch.nn as nn
 
 from .. import _lib, ops
 from .._lib import check
-from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, TensorTaskDataset
+from ..data import ByteTaskDataset, DeviceLoader, TensorTaskDataset, _respec
 from ..optim import SGD
 from .exemplar import ExemplarNet, SharedRowDropout, _stream, batch_source, compute_offsets  # noqa: F401  (compute_offsets: imported from here)
 
@@ -116,7 +117,7 @@ class GemNet(SharedRowDropout, ExemplarNet):
         if self.frame_norm is not None:
             mem.mean, mem.std = self.frame_norm                     # the ..._u8 crop gather decodes the stored bytes
         if self.exemplar_transform is not None:
-            mem.transform = RandomCropFlip(self.exemplar_transform.size, self.exemplar_transform.p, self.memory_ext[past])
+            mem.transform = _respec(self.exemplar_transform, self.memory_ext[past])     # (crop or resized: the loader serves both)
         return DeviceLoader(mem, self.batch_size, True, self.device)
 
     # ------------------------------------------------------------------ kernels

@@ -133,7 +133,9 @@ def exemplar_split(args, dset_sizes):
 def main(overwrite_args, nc_per_task, device="cuda"):
     """main_rehearsal.py:69-255 for method 'gem' and the rehearsal baselines ('baseline_rehearsal_{partial,full}_mem').
     overwrite_args['exemplar_dtype'] (not in the reference; default 'float32'): 'uint8' stores the exemplars of an augmented byte
-    train split as byte frames (exemplar.py, byte store)."""
+    train split as byte frames (exemplar.py, byte store).  overwrite_args['exemplar_resized'] (not in the reference; default
+    False): True replays the exemplars through the RandomResizedCropFlip of the train split (exemplar.py, resized replay);
+    without it such a split is refused."""
     parser = argparse.ArgumentParser()
     for name, kw in (("--task_name", dict(type=str)), ("--task_count", dict(type=int)),
                      ("--prev_model_path", dict(type=str)), ("--save_path", dict(type=str, default="results/")),
@@ -143,7 +145,8 @@ def main(overwrite_args, nc_per_task, device="cuda"):
                      ("--memory_strength", dict(default=0, type=float)), ("--finetune", dict(action="store_true")),
                      ("--n_epochs", dict(type=int, default=1)), ("--batch_size", dict(type=int, default=70)),
                      ("--lr", dict(type=float, default=1e-3)), ("--n_tasks", dict(type=int, default=10)),
-                     ("--exemplar_dtype", dict(type=str, default="float32"))):
+                     ("--exemplar_dtype", dict(type=str, default="float32")),
+                     ("--exemplar_resized", dict(action="store_true"))):
         parser.add_argument(name, **kw)
     args = parser.parse_known_args([])[0]
     args.nc_per_task = nc_per_task
@@ -167,17 +170,24 @@ def main(overwrite_args, nc_per_task, device="cuda"):
 
     dsets = load_task_datasets(args.dataset_path)
     args.task_imgfolders = dsets
-    if isinstance(getattr(dsets["train"], "transform", None), RandomResizedCropFlip):
-        # the exemplar wrappers replay stored frames through clhip_rehearsal_assemble_crop_flip, which does not resample
-        raise NotImplementedError("rehearsal method %r: exemplars are replayed with RandomCropFlip only, the train split carries %r"
+    resized = isinstance(getattr(dsets["train"], "transform", None), RandomResizedCropFlip)
+    if resized and not args.exemplar_resized:
+        # by default the exemplar wrappers replay stored frames through clhip_rehearsal_assemble_crop_flip, which does not resample
+        raise NotImplementedError("rehearsal method %r: exemplars are replayed with RandomCropFlip only, the train split carries %r.  "
+                                  "Resized replay is opt-in: pass exemplar_resized=True (the driver's --resized_exemplars)"
                                   % (args.method, dsets["train"].transform))
+    if args.exemplar_resized and not resized:
+        raise ValueError("rehearsal method %r: exemplar_resized=True replays the exemplars through the RandomResizedCropFlip of the "
+                         "train split; this one carries %r" % (args.method, getattr(dsets["train"], "transform", None)))
     if args.exemplar_dtype not in ("float32", "uint8"):
         raise ValueError("rehearsal method %r: exemplar_dtype is 'float32' or 'uint8', got %r" % (args.method, args.exemplar_dtype))
     byte_store = args.exemplar_dtype == "uint8"
-    byte_frames = isinstance(dsets["train"], ByteTaskDataset) and isinstance(getattr(dsets["train"], "transform", None), RandomCropFlip)
+    byte_frames = isinstance(dsets["train"], ByteTaskDataset) and isinstance(getattr(dsets["train"], "transform", None),
+                                                                             (RandomCropFlip, RandomResizedCropFlip))
     if byte_store and not byte_frames:
         raise ValueError("rehearsal method %r: exemplar_dtype='uint8' stores the byte frames of a train split that is a "
-                         "ByteTaskDataset carrying a RandomCropFlip; this one is a %s with transform %r"
+                         "ByteTaskDataset carrying a RandomCropFlip (or, with exemplar_resized=True, a RandomResizedCropFlip); "
+                         "this one is a %s with transform %r"
                          % (args.method, type(dsets["train"]).__name__, getattr(dsets["train"], "transform", None)))
     if isinstance(dsets["train"], ByteTaskDataset) and getattr(dsets["train"], "transform", None) is not None and not byte_store:
         # frame mode copies fp32 frames into an fp32 store; without a transform the store holds the fp32 crops the loader served

@@ -406,6 +406,8 @@ def _gem_run(self, args, manager, strength, out_dir, prev=None, finetune=False, 
               is_scratch_model=args.task_counter == 1, postprocess=postprocess)
     if getattr(args, "u8_exemplars", False):                    # (only then: the recorded trainer arguments stay what they were)
         kw["exemplar_dtype"] = "uint8"
+    if getattr(args, "resized_exemplars", False):               # (only then, as above)
+        kw["exemplar_resized"] = True
     manager.overwrite_args = kw
     return _gem.main(kw, nc, device=_dev(args))
 
@@ -490,6 +492,8 @@ def _rehearsal_grid_train(self, args, manager, lr):
               batch_size=args.batch_size, lr=lr, finetune=True, is_scratch_model=args.task_counter == 1)
     if getattr(args, "u8_exemplars", False):                    # (only then: the recorded trainer arguments stay what they were)
         kw["exemplar_dtype"] = "uint8"
+    if getattr(args, "resized_exemplars", False):               # (only then, as above)
+        kw["exemplar_resized"] = True
     manager.overwrite_args = kw
     return _gem.main(kw, nc, device=_dev(args))
 

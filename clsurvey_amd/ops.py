@@ -904,8 +904,9 @@ def gather_tasks_resized_crop_flip_u8(table, geometry, lut, idx, params, x_out=N
     return _gather_window_u8("clhip_gather_tasks_resized_crop_flip_u8", 5, table, geometry, lut, idx, params, x_out, labels_out)
 
 
-def _assemble_crop_flip(entry, frame_dtype, geometry, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows,
-                        gather, params, x_mix, y_mix):
+def _assemble_crop_flip(entry, frame_dtype, ncols, geometry, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0,
+                        ring_rows, gather, params, x_mix, y_mix):
+    """The frame-mode assembly entries: ncols = 3, params rows (top, left, flip); 5, (top, left, h, w, flip)."""
     _chk(lut, x, y, src_frames, src_idx, store, store_y, gather, params, x_mix, y_mix)
     C, Hs, Ws, th, tw = (int(v) for v in geometry)
     E = 0 if gather is None else int(gather.shape[0])
@@ -917,7 +918,8 @@ def _assemble_crop_flip(entry, frame_dtype, geometry, lut, x, y, B, src_frames, 
         assert src_frames.dtype == frame_dtype and src_frames.numel() == src_frames.shape[0] * C * Hs * Ws
         assert src_idx.dtype == torch.int64 and src_idx.numel() >= ring_rows
     if E:
-        assert gather.dtype == torch.int32 and params.dtype == torch.int32 and tuple(params.shape) == (E, 3)
+        assert gather.dtype == torch.int32 and params.dtype == torch.int32 and tuple(params.shape) == (E, ncols)
+        assert params.is_contiguous()
     if x_mix is not None:
         assert x_mix.dtype == torch.float32 and x_mix.numel() >= (B + E) * C * th * tw
         assert y_mix.dtype == torch.int64 and y_mix.numel() >= B + E
@@ -938,7 +940,7 @@ def rehearsal_assemble_crop_flip(geometry, x, y, B, src_frames, src_idx, store, 
     """clhip_rehearsal_assemble_crop_flip: geometry = (C, Hs, Ws, th, tw); store [rows, C, Hs, Ws] frames, x / x_mix rows
     [C, th, tw].  src_frames / src_idx (device int64) feed the ring rows, gather (device int32[E]) and params (device
     int32[E, 3]) the exemplar rows; any of them may be None when its count is 0, x_mix None: the ring update alone."""
-    _assemble_crop_flip("clhip_rehearsal_assemble_crop_flip", torch.float32, geometry, None, x, y, B, src_frames, src_idx, store,
+    _assemble_crop_flip("clhip_rehearsal_assemble_crop_flip", torch.float32, 3, geometry, None, x, y, B, src_frames, src_idx, store,
                         store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix)
 
 
@@ -950,8 +952,24 @@ def rehearsal_assemble_crop_flip_u8(geometry, lut, x, y, B, src_frames, src_idx,
     """clhip_rehearsal_assemble_crop_flip_u8: rehearsal_assemble_crop_flip with uint8 frames in src_frames and store; the ring rows
     are byte copies, the exemplar rows are decoded through lut (device float32 [C, 256]; may be None without exemplars): bitwise
     rehearsal_assemble_crop_flip on the decoded store.  x / x_mix stay float32."""
-    _assemble_crop_flip("clhip_rehearsal_assemble_crop_flip_u8", torch.uint8, geometry, lut, x, y, B, src_frames, src_idx, store,
+    _assemble_crop_flip("clhip_rehearsal_assemble_crop_flip_u8", torch.uint8, 3, geometry, lut, x, y, B, src_frames, src_idx, store,
                         store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix)
+
+
+def rehearsal_assemble_resized_crop_flip(geometry, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows, gather,
+                                         params, x_mix, y_mix):
+    """clhip_rehearsal_assemble_resized_crop_flip: rehearsal_assemble_crop_flip with params device int32[E, 5] of (top, left, h,
+    w, flip): the exemplar rows are the windows resized to th x tw, bitwise gather_tasks_resized_crop_flip over the store."""
+    _assemble_crop_flip("clhip_rehearsal_assemble_resized_crop_flip", torch.float32, 5, geometry, None, x, y, B, src_frames, src_idx,
+                        store, store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix)
+
+
+def rehearsal_assemble_resized_crop_flip_u8(geometry, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows,
+                                            gather, params, x_mix, y_mix):
+    """clhip_rehearsal_assemble_resized_crop_flip_u8: rehearsal_assemble_resized_crop_flip with uint8 frames in src_frames and
+    store (lut as rehearsal_assemble_crop_flip_u8): bitwise the fp32 entry on the decoded store."""
+    _assemble_crop_flip("clhip_rehearsal_assemble_resized_crop_flip_u8", torch.uint8, 5, geometry, lut, x, y, B, src_frames,
+                        src_idx, store, store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix)
 
 
 def slice_argmax_count(logits, cols, labels, correct, total, out_of_range):

@@ -507,6 +507,29 @@ int clhip_gem_project_dev(const float* G, size_t ld, const int* row_idx_host, co
  *                       the checks of clhip_rehearsal_assemble and of clhip_gather_tasks_crop_flip's geometry.  16-byte
  *                       copies of full rows / frames under the rule above; float4 stores of the cropped rows when
  *                       tw % 4 == 0 and x_mix is 16-byte aligned, loads at dword alignment.
+ *   rehearsal_assemble_resized_crop_flip  rehearsal_assemble_crop_flip when the task's train transform is RandomResizedCrop +
+ *                       RandomHorizontalFlip (data/tinyimgnet_dataprep.py:105-122): :215-216, gem.py:233-234 and common.py:57-72
+ *                       rebuild the exemplar loader with THAT transform, so a replayed exemplar is a fresh resized window of
+ *                       its stored frame.  Same arguments, same single launch (a 1-D grid of the copy rows, the ring rows and
+ *                       the exemplar rows), same copy and ring rows; gather_params is device int32[E][5] of (top, left, h, w,
+ *                       flip) and
+ *                         x_mix[B + e] = the h x w window at (top, left) of store[gather_rows[e]], resized to th x tw and
+ *                                        mirrored: the formula, taps and SUMMATION ORDER of clhip_gather_tasks_resized_crop_flip
+ *                                        below, by the same device code
+ *                       so the exemplar rows are BITWISE what that gather yields for a one-task table laid over the store,
+ *                       idx = gather_rows and the same params, and a window with h == th and w == tw is bitwise
+ *                       rehearsal_assemble_crop_flip for (top, left, flip).  The exemplar rows take E x C x chunks blocks
+ *                       under that gather's plan for the frame, made once on the host; the launch carries the plan's dynamic LDS.
+ *                       A src_idx outside [0, src_rows): as rehearsal_assemble_crop_flip.  An exemplar row copies nothing and
+ *                       writes label -1 when its gather row is outside [0, store_rows), h < 1, w < 1, top < 0, left < 0,
+ *                       top + h > Hs, left + w > Ws, flip is outside {0, 1}, or h > CLHIP_RESIZE_MAX_RATIO th or
+ *                       w > CLHIP_RESIZE_MAX_RATIO tw (the gather's rule); no address outside a frame is formed.
+ *                       CLHIP_EINVAL before any launch: the checks of clhip_rehearsal_assemble, and the geometry rule of
+ *                       clhip_gather_tasks_resized_crop_flip (C, th, tw, Hs or Ws < 1; th > Hs is an enlargement, not an
+ *                       error).  CLHIP_ENOTSUP before any launch: E > 0 and the plan does not fit the LDS (as that gather:
+ *                       1000 -> 125 is not served).  With E == 0 (the ring update alone, x_mix == NULL allowed) no plan is
+ *                       needed and CLHIP_ENOTSUP is never returned.  float4 stores of the exemplar rows when tw % 4 == 0 and
+ *                       x_mix is 16-byte aligned, dword loads of the frames.
  *   loss_segments       segs (device, n_segs <= CLHIP_LOSS_MAX_SEGS) cover rows of logits[N][ld], N <= CLHIP_LOSS_MAX_ROWS, each
  *                       with a class slice [col_off, col_off + ncols), a scale and a kind:
  *                         kind 0  scale * mean_i CE_i over the slice against labels (relative to the slice)
@@ -535,6 +558,11 @@ int clhip_rehearsal_assemble_crop_flip(const float* x, const int64_t* labels_i64
                                        int64_t* store_labels, long store_rows, long ring_row0, int ring_rows,
                                        const int* gather_rows, const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
                                        void* stream);
+int clhip_rehearsal_assemble_resized_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th,
+                                               int tw, const float* src_frames, long src_rows, const int64_t* src_idx,
+                                               float* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
+                                               int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
+                                               int64_t* labels_mix, void* stream);
 int clhip_loss_segments(const float* logits, const int64_t* labels_i64, const float* targets, int ld_t, int N, int ld,
                         const clhip_loss_segment* segs, int n_segs, float T, float* dlogits, float* loss_out, double* stats,
                         void* stream);
@@ -672,7 +700,13 @@ int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T,
  *                       frame of odd size starts at any byte), byte accesses otherwise.  Exemplar rows: as
  *                       gather_tasks_crop_flip_u8 (float4 stores when tw % 4 == 0 and x_mix is 16-byte aligned; byte loads, one
  *                       dword load per 4 columns only behind a test of that address; the block's channel of the table staged in
- *                       LDS, 1 KB). */
+ *                       LDS, 1 KB).
+ *   rehearsal_assemble_resized_crop_flip_u8   clhip_rehearsal_assemble_resized_crop_flip for a store of BYTE frames: frames, ring
+ *                       rows and the lut rule (NULL allowed with E == 0) as rehearsal_assemble_crop_flip_u8, (top, left, h, w,
+ *                       flip) rows, bad rows, CLHIP_EINVAL and CLHIP_ENOTSUP (the table's 1 KB counted in the plan) as the fp32
+ *                       entry.  The bytes of the source band are decoded through the block's channel of the table as they are
+ *                       staged, everything after is the fp32 code: bitwise the fp32 entry on the decoded store, and bitwise
+ *                       clhip_gather_tasks_resized_crop_flip_u8 over the store.  Byte loads of the frames. */
 typedef struct clhip_task_src_u8 { const uint8_t* x; const int64_t* labels; int64_t cum_rows; int64_t label_shift; } clhip_task_src_u8;
 int clhip_gather_tasks_u8(const clhip_task_src_u8* tasks_dev, int T, int C, size_t plane_elems, const float* lut,
                           const int64_t* idx, int B, float* x_out, int64_t* labels_out, void* stream);
@@ -686,6 +720,12 @@ int clhip_rehearsal_assemble_crop_flip_u8(const float* x, const int64_t* labels_
                                           uint8_t* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
                                           int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
                                           int64_t* labels_mix, void* stream);
+int clhip_rehearsal_assemble_resized_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th,
+                                                  int tw, const float* lut, const uint8_t* src_frames, long src_rows,
+                                                  const int64_t* src_idx, uint8_t* store_frames, int64_t* store_labels,
+                                                  long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
+                                                  const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
+                                                  void* stream);
 
 /* ------------------------------------------------------------------ iCaRL
  * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471) and the nearest-mean-of-exemplars classifier of
