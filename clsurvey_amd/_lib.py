@@ -170,6 +170,10 @@ SIGNATURES = {
     "clhip_rehearsal_assemble_resized_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
     "clhip_icarl_herd": (_i, [_p, _l, _i, _p, C.POINTER(IcarlClass), _i, _p, _l, _p]),
     "clhip_icarl_nme": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "clhip_icarl_assemble_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
+    "clhip_icarl_assemble_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
+    "clhip_icarl_assemble_resized_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
+    "clhip_icarl_assemble_resized_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

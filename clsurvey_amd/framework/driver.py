@@ -91,13 +91,18 @@ def build_parser():
                    help="with --synthetic: the task files hold the images as uint8 frames with their mean / std (data.ByteTaskDataset) "
                         "and the loaders normalise them inside their batch gathers: a quarter of the bytes in HBM, bitwise the "
                         "batches of the float files of the same quantised images.  Combines with --rnd_margin / --rnd_resized")
+    p.add_argument("--icarl_frames", action="store_true",
+                   help="iCaRL on augmented tasks (--rnd_margin or --rnd_resized): the exemplar store holds the tasks' frames, "
+                        "herding ranks one draw of the train transform per training image (the herding view) and every replay "
+                        "crops the stored frames afresh inside the step's one assembly launch.  Without it iCaRL refuses "
+                        "augmented tasks.  With --rnd_resized it goes with --resized_exemplars, with --u8_frames with --u8_exemplars")
     p.add_argument("--u8_exemplars", action="store_true",
-                   help="GEM and the rehearsal baselines: the exemplar store holds uint8 frames, decoded where they are replayed (a "
+                   help="GEM, the rehearsal baselines and iCaRL (--icarl_frames): the exemplar store holds uint8 frames, decoded where they are replayed (a "
                         "quarter of the store's bytes in HBM and in every checkpoint, bitwise the run on the decoded files).  "
                         "Belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars): the train "
                         "splits are augmented byte splits")
     p.add_argument("--resized_exemplars", action="store_true",
-                   help="GEM and the rehearsal baselines with --rnd_resized: the stored exemplar frames are replayed through the "
+                   help="GEM, the rehearsal baselines and iCaRL (--icarl_frames) with --rnd_resized: the stored exemplar frames are replayed through the "
                         "task's RandomResizedCrop + flip, a fresh window per exemplar and replay, resampled inside the step's batch "
                         "assembly launch.  Without it these methods refuse --rnd_resized tasks")
     p.add_argument("--rnd_resized", type=int, default=0,
@@ -775,6 +780,8 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         raise SystemExit("--rnd_resized belongs to --synthetic: a dataset object says itself which of its files are augmented")
     if args.u8_frames and (dataset is not None or not args.synthetic):
         raise SystemExit("--u8_frames belongs to --synthetic: a dataset object says itself how its files store their frames")
+    if args.icarl_frames and not (args.rnd_margin or args.rnd_resized):
+        raise SystemExit("--icarl_frames belongs with --rnd_margin or --rnd_resized: iCaRL stores frames only of augmented tasks")
     if args.resized_exemplars and not args.rnd_resized:
         raise SystemExit("--resized_exemplars belongs with --rnd_resized: it replays the exemplars through the tasks' RandomResizedCrop")
     if args.u8_exemplars and not (args.u8_frames and (args.rnd_margin or (args.rnd_resized and args.resized_exemplars))):

@@ -21,6 +21,13 @@ Resized replay (frame mode with a RandomResizedCropFlip spec, the cropped Tiny-I
 RandomResizedCrop window of its stored frame, drawn over the frame's own extent and resampled inside the assembly launch
 (clhip_rehearsal_assemble_resized_crop_flip[_u8], the block body of the loaders' resizing gather); the draws are rows of
 (top, left, h, w, flip).  Store, ring update and extents are those of frame mode.
+
+iCaRL in frame mode (icarl.py): the same store of frames, extents and replay draws, but its exemplars are chosen by herding, not
+copied out of the batches, and each carries a distillation row.  Two things need ONE fixed image of a randomly transformed
+frame: the ranking (the herding view, one draw per training image at manage_memory) and the class means of the nearest-mean
+classifier (the class-mean view, one draw per stored exemplar).  Both come from a private CPU generator seeded by
+icarl.view_seed_of(view_seed, task, kind), a function of those three alone.  The step is assembled by clhip_icarl_assemble_*: the
+exemplar windows and their stored distillation rows in one launch.
 """
 import collections
 

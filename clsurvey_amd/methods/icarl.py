@@ -15,6 +15,29 @@ image and of every exemplar chosen so far once per pick (:394-427).  Here the ex
 A plan with BatchNorm, or a step over the loss kernel's limits, takes the segmented path: one pass per chunk in the
 reference's order (as RehearsalNet does).  Herding needs features that do not depend on the batch: manage_memory refuses a
 net with BatchNorm in `features`.
+
+Frame mode (a wrapper built with exemplar_transform, exemplar.py): iCaRL on AUGMENTED tasks.  The reference's memory holds
+paths; under a random train transform every replay is a fresh crop (:560-561) while the distillation targets stay the rows
+computed once at herding time on the crop the winner had then (:476-479).  Here
+
+    store           store_x holds the winners' FRAMES (fp32, or bytes with frame_norm), store_ext (host) their valid (h, w),
+                    store_t their distillation rows; all three move together through _truncate
+    manage_memory   the HERDING VIEW: one draw of the train transform per training image, dataset order, over the split's own
+                    extents, private CPU generator seeded view_seed_of(view_seed, t, VIEW_HERD); features once on those crops
+                    (the loaders' gathers over a one-task table, chunks of the engine's batch), ranking and K_c as above;
+                    store_t = forward_training of the winners' herding-view crops
+    observe         a fresh draw per gathered exemplar (draw_exemplar_params over store_ext, seeded with the base seed the plan's
+                    last exemplar loader drew anyway: the global generators are consumed as in crop mode), then ONE
+                    clhip_icarl_assemble_* launch: current rows, exemplar windows, label 0, target rows -> x_mix, y_mix, t_mix
+    class_means     the CLASS-MEAN VIEW: one draw per stored exemplar, seed kind VIEW_MEANS, cropped by the same entry with B = 0
+
+Seed rule: view_seed_of(view_seed, t, kind) = (view_seed * 1000003 + t) * 2 + kind, nothing else; view_seed is a wrapper
+attribute (default 0, pickled).  Neither view touches the global torch generator, numpy or Python `random`.
+What differs from the reference: its manage_memory runs the class loader once per pick (:394-451), so with a random transform
+the mean, the costs of every pick and the stored target each see other crops of the images; the herding view is that procedure
+with the loader's draws frozen over the passes.  Its forward redraws the exemplars' crops for every evaluated batch (:160-167);
+the class-mean view is one draw per (model, task, batch size), so an evaluation is reproducible.  Without freedom (frames of
+the crop size, p = 0) frame mode is bitwise crop mode.
 """
 import random
 
@@ -23,9 +46,9 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ..data import ByteTaskDataset
+from ..data import ByteTaskDataset, RandomResizedCropFlip, _spec_key, _transform_of
 from ..optim import SGD
-from .exemplar import ExemplarNet, PerRowDropout, _stream, compact_blocks, compute_offsets
+from .exemplar import BatchSource, ExemplarNet, PerRowDropout, _stream, compact_blocks, compute_offsets
 from .gem import extend_head
 from .rehearsal import _Order
 
@@ -49,11 +72,23 @@ def mean_weights(n, batch_size):
     return w
 
 
-def exemplar_draws(t, n_append, class_len, exemplar_count, nc_per_task, cum_nc_per_task, total_batch_size):
+VIEW_HERD, VIEW_MEANS = 0, 1     # the two private draws of a frame-mode wrapper (view_seed_of's `kind`)
+
+
+def view_seed_of(view_seed, t, kind):
+    """Seed of the private CPU generator that draws a view of task t: the herding view (kind VIEW_HERD, one draw of the train
+    transform per training image at manage_memory) or the class-mean view (VIEW_MEANS, one per stored exemplar at class_means).
+    A function of (view_seed, t, kind) alone: (view_seed * 1000003 + t) * 2 + kind."""
+    return (int(view_seed) * 1000003 + int(t)) * 2 + int(kind)
+
+
+def exemplar_draws(t, n_append, class_len, exemplar_count, nc_per_task, cum_nc_per_task, total_batch_size, seeds=None):
     """The host draws of update_representation (:507-562) for one step at task index t, on Python `random`, numpy's global
     generator and the global torch CPU generator, in the reference's order.  class_len[c] = exemplars stored for class c
     (every class stored so far).  Returns (counts per class, [(task, chunks)]) with chunks = lists of (class, exemplar
-    index) in the order the task's DataLoader(shuffle=True, batch_size=total_batch_size) yields them."""
+    index) in the order the task's DataLoader(shuffle=True, batch_size=total_batch_size) yields them.  `seeds` (optional list)
+    collects the worker base seed every exemplar DataLoader draws (rehearsal.sample_plan's rule); the draws are the same with or
+    without it."""
     n_classes = len(class_len)
     if exemplar_count <= 0 or n_classes == 0:
         return [], []
@@ -85,7 +120,10 @@ def exemplar_draws(t, n_append, class_len, exemplar_count, nc_per_task, cum_nc_p
             continue
         if total_batch_size <= 0:
             raise ValueError("icarl: distillation chunk size %d" % total_batch_size)
-        ordered = [rows[i] for i in _Order(len(rows)).order().tolist()]
+        loader = _Order(len(rows))
+        ordered = [rows[i] for i in loader.order().tolist()]
+        if seeds is not None:
+            seeds.append(loader.base_seed)
         out.append((task, [ordered[s:s + total_batch_size] for s in range(0, len(ordered), total_batch_size)]))
     return counts, out
 
@@ -112,10 +150,14 @@ class IcarlNet(PerRowDropout, ExemplarNet):
     """icarl.Net.  The pickle carries the net, the counters, the stored exemplar rows and their distillation targets only.
     Dropout: the net's own nn.Dropout, one mask per step over the MIXED batch."""
 
-    _TRANSIENT_EXTRA = ("t_mix", "store_x", "store_t", "_store_lab", "_means", "_scratch_lab", "last_ranking")
+    _TRANSIENT_EXTRA = ("t_mix", "store_x", "store_t", "_store_lab", "_means", "_scratch_lab", "last_ranking", "store_ext",
+                        "last_gather", "last_exemplar_params", "last_herd_params")
+    view_seed = 0                                                    # class-level default: an older pickle loads with 0
+    last_gather = last_exemplar_params = last_herd_params = None     # host: the last step's store rows and draws, the last herding view
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, memory_strength=0.0,
-                 batch_size=200, in_shape=(3, 64, 64), device="cuda"):
+                 batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None,
+                 frame_norm=None):
         self.net = init_head(model, n_outputs).to(device)
         self.device = torch.device(device)
         self.n_outputs, self.n_tasks = n_outputs, n_tasks
@@ -123,6 +165,9 @@ class IcarlNet(PerRowDropout, ExemplarNet):
         self.n_total_memories = int(n_memories) * n_tasks            # :41, fixed at creation
         self.batch_size = batch_size
         self.in_shape = tuple(in_shape)
+        self._init_frames(exemplar_transform, frame_shape, frame_norm)
+        if self.exemplar_transform is not None:                      # (a crop-mode wrapper draws no view: its pickle keeps its keys)
+            self.view_seed = 0                                       # seeds the herding and class-mean views (view_seed_of)
         self.nc_per_task = list(nc_per_task)
         self.cum_nc_per_task = [sum(nc_per_task[:i + 1]) for i in range(len(nc_per_task))]
         self.exemplar_count = 0          # K/m of the last manage_memory = the row stride of a class block in the store
@@ -180,17 +225,24 @@ class IcarlNet(PerRowDropout, ExemplarNet):
 
     def _rows_state(self):
         idx = torch.tensor(self.stored_rows(), dtype=torch.int64, device=self.device)
-        return {"_rows_x": self.store_x.index_select(0, idx), "_rows_t": self.store_t.index_select(0, idx)}
+        state = {"_rows_x": self.store_x.index_select(0, idx), "_rows_t": self.store_t.index_select(0, idx)}
+        if self.exemplar_transform is not None:
+            state["_rows_ext"] = self.store_ext.index_select(0, idx.cpu())
+        return state
 
     def _load_rows(self, rows):
         n = self.n_total_memories
-        self.store_x = torch.zeros((n,) + self.in_shape, dtype=torch.float32, device=self.device)
+        self.store_x = torch.zeros((n,) + self.store_shape, dtype=self.store_dtype, device=self.device)
+        if self.exemplar_transform is not None:
+            self.store_ext = self._full_ext(n)                       # host [rows][2]: valid (h, w) of every stored frame
         self.store_t = torch.zeros((n, self.n_outputs), dtype=torch.float32, device=self.device)     # mem_class_y rows
         self._store_lab = torch.zeros((n,), dtype=torch.int64, device=self.device)      # (the assemble kernel copies a label per row)
         if rows and rows["_rows_x"].shape[0]:
             idx = torch.tensor(self.stored_rows(), dtype=torch.int64, device=self.device)
             self.store_x[idx] = rows["_rows_x"]
             self.store_t[idx] = rows["_rows_t"]
+            if self.exemplar_transform is not None:
+                self.store_ext[idx.cpu()] = rows["_rows_ext"]
 
     # ------------------------------------------------------------------ features / training output
     def features(self, x):
@@ -216,7 +268,8 @@ class IcarlNet(PerRowDropout, ExemplarNet):
     def _truncate(self, new_count):
         """Every stored class keeps its first new_count entries; the class blocks are compacted in place."""
         self.class_len = [min(n, new_count) for n in self.class_len]
-        compact_blocks((self.store_x, self.store_t), self.exemplar_count, new_count, self.class_len)
+        stores = (self.store_x, self.store_t) + (() if self.exemplar_transform is None else (self.store_ext,))
+        compact_blocks(stores, self.exemplar_count, new_count, self.class_len)
         self.exemplar_count = new_count
 
     def herd(self, feats, ranges, weights, ks):
@@ -241,6 +294,8 @@ class IcarlNet(PerRowDropout, ExemplarNet):
                                % (t, len(self.class_len), o1))
         self._truncate(count)
         train = args.task_imgfolders["train"]
+        if self.exemplar_transform is not None:
+            return self._manage_memory_frames(t, train, count, int(args.batch_size))
         if getattr(train, "transform", None) is not None:
             raise NotImplementedError("icarl: herding ranks the stored images of the task; an augmented split (%r) stores frames "
                                       "larger than the net's input" % (train.transform,))
@@ -274,9 +329,97 @@ class IcarlNet(PerRowDropout, ExemplarNet):
         self.net.train(was_training)
         self._means = {}
 
+    # ------------------------------------------------------------------ frame mode: views of stored frames
+    def view_params(self, t, kind, ext):
+        """Host int32 [n][params_width]: one draw of the train transform per frame of valid sizes ext [n][2], in that order, from
+        a private CPU generator seeded view_seed_of(self.view_seed, t, kind).  No global generator is touched."""
+        return self.draw_exemplar_params(ext, view_seed_of(self.view_seed, t, kind))
+
+    def _gather_view(self, table, idx, params):
+        """The loaders' gather of this wrapper's spec and store kind: crops [len(idx)][C][th][tw] of the frames in `table`."""
+        resized = isinstance(self.exemplar_transform, RandomResizedCropFlip)
+        if self.frame_norm is None:
+            gather = ops.gather_tasks_resized_crop_flip if resized else ops.gather_tasks_crop_flip
+            return gather(table, self.geometry, idx, params)[0]
+        gather = ops.gather_tasks_resized_crop_flip_u8 if resized else ops.gather_tasks_crop_flip_u8
+        return gather(table, self.geometry, self.lut, idx, params)[0]
+
+    def _assemble_step(self, x, y, B, gather_dev, params_dev):
+        """The step-assembly launch of this wrapper's spec and store kind: x_mix, y_mix and t_mix[B:B + E) in one launch."""
+        resized = isinstance(self.exemplar_transform, RandomResizedCropFlip)
+        args = (x, y, B, self.store_x, gather_dev, params_dev, self.store_t, self.x_mix, self.y_mix, self.t_mix)
+        if self.frame_norm is None:
+            (ops.icarl_assemble_resized_crop_flip if resized else ops.icarl_assemble_crop_flip)(self.geometry, *args)
+        else:
+            (ops.icarl_assemble_resized_crop_flip_u8 if resized else ops.icarl_assemble_crop_flip_u8)(self.geometry, self.lut, *args)
+
+    def _manage_memory_frames(self, t, train, count, batch_size):
+        """manage_memory on an augmented split (the store is truncated already).  The reference runs the class loader once
+        per pick (:394-451): with a random train transform every pick sees new crops of every image.  Here ONE draw per
+        training image, the herding view (view_params(t, VIEW_HERD, the split's extents), dataset order), stands for all
+        passes: features once on those crops, mean weights, ranking and K_c as in crop mode; the winners' FRAMES and extents
+        go to the store, their targets are forward_training of their herding-view crops (:476-479)."""
+        spec = _transform_of(train)
+        if spec is None:
+            raise ValueError("icarl: a frame-mode wrapper herds the frames of an augmented train split; this one carries no transform")
+        if _spec_key(spec) != _spec_key(self.exemplar_transform):
+            raise ValueError("icarl: the train split carries %r, the wrapper replays %r" % (spec, self.exemplar_transform))
+        byte = isinstance(train, ByteTaskDataset)
+        ext = spec.extents if spec.extents is not None else self._full_ext(len(train))
+        self._check_source(BatchSource(train.x, None, None, ext, (train.mean, train.std) if byte else None))
+        o1, o2 = compute_offsets(t, self.cum_nc_per_task)
+        y, n = train.y, len(train)
+        order = torch.sort(y, stable=True)[1]
+        sizes = torch.bincount(y, minlength=o2 - o1).cpu().tolist()
+        if len(sizes) != o2 - o1 or min(sizes) <= 0:
+            raise ValueError("icarl: every class of the task needs at least one training image, got sizes %s" % sizes)
+        F = self.engine.layer_input(self.fc_first, 1).shape[1]
+        if F > HERD_MAX_FEATS:
+            raise NotImplementedError("icarl: %d features > %d of the herding kernel" % (F, HERD_MAX_FEATS))
+        herd_params = self.view_params(t, VIEW_HERD, ext)
+        params_dev = herd_params.to(self.device)
+        table = ops.task_table([train.x], [train.y], [n], [0], self.device)
+        was_training = self.net.training
+        self.net.train(False)
+        self._dropout(1)
+        step, feats = self.engine.max_batch, []
+        for s in range(0, n, step):                                             # the chunks of features()
+            idx = torch.arange(s, min(n, s + step), dtype=torch.int64, device=self.device)
+            feats.append(self.features(self._gather_view(table, idx, params_dev[s:s + step].contiguous())))
+        feats = torch.cat(feats).index_select(0, order)
+        bounds = np.concatenate([[0], np.cumsum(sizes)])
+        ranges = [(int(bounds[c]), int(bounds[c + 1])) for c in range(o2 - o1)]
+        ks = [min(count, m) for m in sizes]
+        w = torch.from_numpy(np.concatenate([mean_weights(m, batch_size) for m in sizes])).to(self.device)
+        ranking, offs = self.herd(feats, ranges, w, ks)
+        base = torch.from_numpy(np.repeat(bounds[:-1], ks)).to(self.device)
+        rows = base + ranking[:int(offs[-1])].long()
+        dst = torch.from_numpy(np.concatenate([(o1 + c) * count + np.arange(ks[c]) for c in range(o2 - o1)]))
+        win = order.index_select(0, rows)                                       # sample numbers of the winners, class after class
+        self.store_x[dst.to(self.device)] = train.x.index_select(0, win)
+        self.store_ext[dst] = ext.index_select(0, win.cpu())
+        crops = torch.cat([self._gather_view(table, win[s:s + step].contiguous(), params_dev.index_select(0, win[s:s + step]))
+                           for s in range(0, win.shape[0], step)])
+        self.store_t[dst.to(self.device)] = self.forward_training(crops, t)     # :476-479, eval mode
+        self.class_len.extend(ks)
+        self.last_ranking = (ranking, offs)
+        self.last_herd_params = herd_params
+        self.net.train(was_training)
+        self._means = {}
+
+    def exemplar_params(self, gather, seeds):
+        """Frame mode: host int32 [len(gather)][params_width], one fresh draw per gathered store row in gather order over the
+        rows' own extents (RehearsalNet.exemplar_params's rule: the generator is seeded with the base seed the plan's last
+        exemplar loader drew anyway, so the global generators are consumed exactly as in crop mode)."""
+        if not gather:
+            return torch.zeros((0, self.params_width), dtype=torch.int32)
+        return self.draw_exemplar_params(self.store_ext[torch.tensor(gather, dtype=torch.int64)], seeds[-1])
+
     # ------------------------------------------------------------------ the steps
-    def observe_FT(self, x, t, y):
-        """:209-223: CE on the task's slice of the current batch only, SGD step."""
+    def observe_FT(self, x, t, y, source=None):
+        """:209-223: CE on the task's slice of the current batch only, SGD step.  source: the batch's BatchSource in frame mode
+        (checked only: iCaRL copies nothing from the batch), None in crop mode."""
+        self._check_source(source)
         self.net.train(True)
         self._means = {}
         self.stats.zero_()
@@ -285,19 +428,23 @@ class IcarlNet(PerRowDropout, ExemplarNet):
         self.opt.step()
         return loss, self.stats[1]
 
-    def plan(self, t):
+    def plan(self, t, seeds=None):
         return exemplar_draws(t, self.n_append, self.class_len, self.exemplar_count, self.nc_per_task, self.cum_nc_per_task,
-                              self.total_batch_size)
+                              self.total_batch_size, seeds)
 
-    def observe(self, x, t, y):
+    def observe(self, x, t, y, source=None):
         """:229-246 -> update_representation (:482-598).  Returns device (loss, hits on the current batch) and the batch_stats
-        dictionary the shared training loop reads (no projections here)."""
+        dictionary the shared training loop reads (no projections here).  source: as observe_FT.  Frame mode: every gathered
+        exemplar gets a fresh draw (exemplar_params), and ONE clhip_icarl_assemble_* launch fills x_mix, y_mix and t_mix[B:N)."""
+        self._check_source(source)
+        frames = self.exemplar_transform is not None
         self.net.train(True)
         self._means = {}
         if t != self.old_task:
             self.init_new_task(t)
         B = int(y.shape[0])
-        _, plan = self.plan(t)
+        seeds = []
+        _, plan = self.plan(t, seeds)
         scales = segment_scales([len(chunks) for _, chunks in plan], float(self.reg))
         segs = [(0, B) + self._slice(t) + (1.0, 0)]
         gather = []
@@ -310,17 +457,23 @@ class IcarlNet(PerRowDropout, ExemplarNet):
             raise RuntimeError("icarl: step of %d rows > engine batch %d" % (N, self.batch_size))
         # two tables in the one upload: the mixed batch's rows, then each segment alone from row 0 (the segmented path)
         local = [(0, sg[1] - sg[0]) + sg[2:] for sg in segs]
-        gather_dev, tabs = self._upload(gather, ops.loss_segment_rows(segs + local))
-        L = _lib.lib()
-        check(L.clhip_rehearsal_assemble(
-            x.data_ptr(), y.data_ptr(), B, int(np.prod(self.in_shape)), self.store_x.data_ptr(), self._store_lab.data_ptr(),
-            self.store_x.shape[0], 0, 0, gather_dev.data_ptr() if E else None, E, self.x_mix.data_ptr(), self.y_mix.data_ptr(),
-            _stream()), "clhip_rehearsal_assemble")
-        if E:                      # the stored distillation rows of the same exemplars -> t_mix[B:N)
+        self.last_gather = list(gather)
+        if frames:
+            self.last_exemplar_params = self.exemplar_params(gather, seeds)
+            gather_dev, tabs, params_dev = self._upload(gather, ops.loss_segment_rows(segs + local), self.last_exemplar_params)
+            self._assemble_step(x, y, B, gather_dev if E else None, params_dev if E else None)
+        else:
+            gather_dev, tabs = self._upload(gather, ops.loss_segment_rows(segs + local))
+            L = _lib.lib()
             check(L.clhip_rehearsal_assemble(
-                None, None, 0, self.n_outputs, self.store_t.data_ptr(), self._store_lab.data_ptr(), self.store_t.shape[0], 0, 0,
-                gather_dev.data_ptr(), E, self.t_mix[B:].data_ptr(), self._scratch_lab.data_ptr(), _stream()),
-                "clhip_rehearsal_assemble")
+                x.data_ptr(), y.data_ptr(), B, int(np.prod(self.in_shape)), self.store_x.data_ptr(), self._store_lab.data_ptr(),
+                self.store_x.shape[0], 0, 0, gather_dev.data_ptr() if E else None, E, self.x_mix.data_ptr(), self.y_mix.data_ptr(),
+                _stream()), "clhip_rehearsal_assemble")
+            if E:                      # the stored distillation rows of the same exemplars -> t_mix[B:N)
+                check(L.clhip_rehearsal_assemble(
+                    None, None, 0, self.n_outputs, self.store_t.data_ptr(), self._store_lab.data_ptr(), self.store_t.shape[0], 0, 0,
+                    gather_dev.data_ptr(), E, self.t_mix[B:].data_ptr(), self._scratch_lab.data_ptr(), _stream()),
+                    "clhip_rehearsal_assemble")
         xm, ym = self.x_mix[:N], self.y_mix[:N]
         masks = self._dropout(N)
         self.stats.zero_()
@@ -350,7 +503,10 @@ class IcarlNet(PerRowDropout, ExemplarNet):
     # ------------------------------------------------------------------ evaluation
     def class_means(self, t, batch_size):
         """[nc_t][n_feat] means of the stored exemplars of task t: per class the mean of batch means (:160-167) over the
-        exemplars in STORED order in batches of batch_size; None while the task's first class has no exemplars."""
+        exemplars in STORED order in batches of batch_size; None while the task's first class has no exemplars.
+        Frame mode: the stored frames are cropped under ONE draw of the train transform, the class-mean view
+        (view_params(t, VIEW_MEANS, the rows' extents), stored order), by the assembly launch with B = 0 in chunks of the
+        engine's batch; the reference redraws per evaluated batch (forward's docstring)."""
         key = (t, int(batch_size))
         if key not in self._means:
             o1, o2 = compute_offsets(t, self.cum_nc_per_task)
@@ -360,7 +516,10 @@ class IcarlNet(PerRowDropout, ExemplarNet):
                 if o2 > len(self.class_len):
                     raise RuntimeError("icarl: task %d is stored in part only" % t)
                 rows = [c * self.exemplar_count + e for c in range(o1, o2) for e in range(self.class_len[c])]
-                feats = self.features(self.store_x.index_select(0, torch.tensor(rows, dtype=torch.int64, device=self.device)))
+                if self.exemplar_transform is None:
+                    feats = self.features(self.store_x.index_select(0, torch.tensor(rows, dtype=torch.int64, device=self.device)))
+                else:
+                    feats = self._view_features(t, rows)
                 means, lo = [], 0
                 for c in range(o1, o2):
                     n = self.class_len[c]
@@ -369,6 +528,18 @@ class IcarlNet(PerRowDropout, ExemplarNet):
                     lo += n
                 self._means[key] = torch.stack(means).contiguous()
         return self._means[key]
+
+    def _view_features(self, t, rows):
+        """Features of the class-mean view of the store rows `rows` (class_means, frame mode)."""
+        params = self.view_params(t, VIEW_MEANS, self.store_ext[torch.tensor(rows, dtype=torch.int64)])
+        gather_dev = torch.tensor(rows, dtype=torch.int32).to(self.device)
+        params_dev = params.to(self.device)
+        step, out = self.engine.max_batch, []
+        for s in range(0, len(rows), step):
+            n = min(step, len(rows) - s)
+            self._assemble_step(None, None, 0, gather_dev[s:s + n], params_dev[s:s + n].contiguous())
+            out.append(self.features(self.x_mix[:n]))
+        return torch.cat(out)
 
     def __call__(self, x, t, args=None, train_mode=False, **kw):
         return self.forward(x, t, args, train_mode)
@@ -379,7 +550,10 @@ class IcarlNet(PerRowDropout, ExemplarNet):
 
         The class means are computed once per (model, task, evaluation batch size) and cached, not once per batch.  One
         difference from the reference: its exemplar loader is shuffled, this one takes the stored order; the mean of batch
-        means depends on the order only when a class holds more exemplars than one batch and the last batch is short."""
+        means depends on the order only when a class holds more exemplars than one batch and the last batch is short.
+        Frame mode, a second one: the reference's exemplar loader carries the train transform, so it recomputes the means
+        from freshly cropped exemplars for every evaluated batch (:160-167); here they come from one draw per (model, task,
+        batch size), the class-mean view (class_means), so an evaluation is reproducible."""
         if train_mode:
             return self.forward_training(x, t)
         self._eval_dropout(1)

@@ -1,20 +1,70 @@
 """iCaRL trainer on the HIP path — mirror of src/methods/rehearsal/main_rehearsal.py:main for method 'icarl' (:140-255):
 argument handling, loaders at the original batch size and the batch split with the full-memory ratio, scratch wrap or
 load of the IcarlNet wrapper, postprocess = manage_memory (exemplar herding) + save, else the shared rehearsal training loop
-(gem_main.train_model, which dispatches observe / observe_FT)."""
+(gem_main.train_model, which dispatches observe / observe_FT).
+
+Augmented train splits (not in the reference's arguments): overwrite_args['exemplar_frames'] = True builds the wrapper in frame
+mode (icarl.py): the store holds the split's frames, herding ranks the herding view, every replay crops afresh.  Without it an
+augmented split is refused by manage_memory as before.  exemplar_resized / exemplar_dtype follow gem_main.main's rules."""
 import argparse
 import os
 
 import torch
 
-from ..data import DeviceLoader, load_task_datasets
+from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, RandomResizedCropFlip, load_task_datasets
 from . import gem_main
 from . import icarl as I
 
 
+def _frame_arguments(args, train):
+    """exemplar_frames=True: the frame arguments of IcarlNet for the train split, after gem_main.main's rules for
+    exemplar_resized and exemplar_dtype.  Decided before a device is needed."""
+    spec = getattr(train, "transform", None)
+    if not isinstance(spec, (RandomCropFlip, RandomResizedCropFlip)):
+        raise ValueError("icarl: exemplar_frames=True stores the frames of an augmented train split and replays them through its "
+                         "transform; this one carries %r" % (spec,))
+    resized = isinstance(spec, RandomResizedCropFlip)
+    if resized and not args.exemplar_resized:
+        raise NotImplementedError("icarl: exemplars are replayed with RandomCropFlip only, the train split carries %r.  Resized "
+                                  "replay is opt-in: pass exemplar_resized=True (the driver's --resized_exemplars)" % (spec,))
+    if args.exemplar_resized and not resized:
+        raise ValueError("icarl: exemplar_resized=True replays the exemplars through the RandomResizedCropFlip of the train split; "
+                         "this one carries %r" % (spec,))
+    if args.exemplar_dtype not in ("float32", "uint8"):
+        raise ValueError("icarl: exemplar_dtype is 'float32' or 'uint8', got %r" % (args.exemplar_dtype,))
+    byte_store, byte_frames = args.exemplar_dtype == "uint8", isinstance(train, ByteTaskDataset)
+    if byte_store and not byte_frames:
+        raise ValueError("icarl: exemplar_dtype='uint8' stores the byte frames of a train split that is a ByteTaskDataset; this one "
+                         "is a %s" % type(train).__name__)
+    if byte_frames and not byte_store:
+        raise NotImplementedError("icarl: the default exemplar store holds fp32 frames, the augmented train split holds byte frames; "
+                                  "pass exemplar_dtype='uint8' (the driver's --u8_exemplars) for a byte exemplar store")
+    frames = dict(exemplar_transform=spec, frame_shape=tuple(train.x.shape[1:]))
+    if byte_store:
+        frames["frame_norm"] = (train.mean, train.std)
+    return frames
+
+
+def _check_loaded(model, frames):
+    """A loaded wrapper keeps the store it was built with: its kind and mode agree with this call's arguments."""
+    if getattr(model, "exemplar_transform", None) is None:
+        raise ValueError("icarl: exemplar_frames=True, the loaded wrapper's store holds crops (it was built without it)")
+    if isinstance(model.exemplar_transform, RandomResizedCropFlip) != isinstance(frames["exemplar_transform"], RandomResizedCropFlip):
+        raise ValueError("icarl: the loaded wrapper replays %r, the train split carries %r"
+                         % (model.exemplar_transform, frames["exemplar_transform"]))
+    if (model.frame_norm is not None) != ("frame_norm" in frames):
+        raise ValueError("icarl: exemplar_dtype=%r, the loaded wrapper's exemplar store is %s"
+                         % ("uint8" if "frame_norm" in frames else "float32", "uint8" if model.frame_norm is not None else "float32"))
+
+
 def main(overwrite_args, nc_per_task, device="cuda"):
     """main_rehearsal.py:69-255 for method 'icarl'.  Returns (model, best validation accuracy), (None, None) after a
-    postprocess."""
+    postprocess.
+    overwrite_args['exemplar_frames'] (default False): True stores the frames of an augmented train split and replays them through
+    its transform (a split without a transform is a ValueError).  With it, overwrite_args['exemplar_resized'] = True goes with a
+    RandomResizedCropFlip split (either without the other is refused) and overwrite_args['exemplar_dtype'] = 'uint8' with an
+    augmented ByteTaskDataset (a byte store; 'uint8' on anything else is a ValueError).  Without exemplar_frames the other two are
+    not looked at and nothing differs from the plain entry."""
     parser = argparse.ArgumentParser()
     for name, kw in (("--task_name", dict(type=str)), ("--task_count", dict(type=int)),
                      ("--prev_model_path", dict(type=str)), ("--save_path", dict(type=str, default="results/")),
@@ -23,7 +73,9 @@ def main(overwrite_args, nc_per_task, device="cuda"):
                      ("--is_scratch_model", dict(action="store_true")), ("--n_memories", dict(type=int, default=0)),
                      ("--memory_strength", dict(default=0, type=float)), ("--finetune", dict(action="store_true")),
                      ("--n_epochs", dict(type=int, default=1)), ("--batch_size", dict(type=int, default=70)),
-                     ("--lr", dict(type=float, default=1e-3)), ("--n_tasks", dict(type=int, default=10))):
+                     ("--lr", dict(type=float, default=1e-3)), ("--n_tasks", dict(type=int, default=10)),
+                     ("--exemplar_frames", dict(action="store_true")), ("--exemplar_resized", dict(action="store_true")),
+                     ("--exemplar_dtype", dict(type=str, default="float32"))):
         parser.add_argument(name, **kw)
     args = parser.parse_known_args([])[0]
     args.nc_per_task = nc_per_task
@@ -44,6 +96,7 @@ def main(overwrite_args, nc_per_task, device="cuda"):
 
     dsets = load_task_datasets(args.dataset_path, device)
     args.task_imgfolders = dsets
+    frames = _frame_arguments(args, dsets["train"]) if args.exemplar_frames else {}
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}
     in_shape = tuple(args.dset_loaders["train"].x.shape[1:])
@@ -53,12 +106,16 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         assert args.task_idx == 0
         raw = torch.load(args.prev_model_path, weights_only=False)
         model = I.IcarlNet(raw, args.n_outputs, args.n_tasks, args.nc_per_task, args.n_memories, args.lr, args.weight_decay,
-                           args.memory_strength, step_rows, in_shape, device)
+                           args.memory_strength, step_rows, in_shape, device, **frames)
     else:
         model = torch.load(args.prev_model_path, weights_only=False)
         if model.batch_size < step_rows:
             model.batch_size = step_rows
             model._bind()
+    if args.exemplar_frames:
+        _check_loaded(model, frames)
+    elif getattr(model, "exemplar_transform", None) is not None:
+        raise ValueError("icarl: the loaded wrapper's store holds frames (it was built with exemplar_frames=True); pass it again")
     model.init_setup(args)
     assert model.n_tasks == args.n_tasks, "model tasks={}, args tasks={}".format(model.n_tasks, args.n_tasks)
     assert model.n_outputs == args.n_outputs

@@ -446,6 +446,12 @@ def _icarl_run(self, args, manager, strength, out_dir, prev=None, finetune=False
     kw.update(method="icarl", prev_model_path=manager.previous_task_model_path if prev is None else prev, save_path=out_dir,
               n_outputs=sum(nc), memory_strength=strength, n_tasks=manager.dataset.task_count, finetune=finetune,
               is_scratch_model=args.task_counter == 1, postprocess=postprocess)
+    if getattr(args, "icarl_frames", False):                    # (only then: the recorded trainer arguments stay what they were)
+        kw["exemplar_frames"] = True
+    if getattr(args, "u8_exemplars", False):                    # (only then, as above)
+        kw["exemplar_dtype"] = "uint8"
+    if getattr(args, "resized_exemplars", False):               # (only then, as above)
+        kw["exemplar_resized"] = True
     manager.overwrite_args = kw
     return _icarl.main(kw, nc, device=_dev(args))
 

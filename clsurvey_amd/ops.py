@@ -1051,3 +1051,63 @@ def icarl_nme(feats, means, offset1, nc, n_outputs, n_rows=None):
                                      feats.shape[1] if means is not None else 0, int(nc), int(offset1), int(n_outputs), _ptr(out),
                                      _stream()), "clhip_icarl_nme")
     return out
+
+
+def _icarl_assemble(entry, frame_dtype, ncols, geometry, lut, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
+    """The iCaRL step-assembly entries: ncols = 3, params rows (top, left, flip); 5, (top, left, h, w, flip)."""
+    _chk(lut, x, y, store, gather, params, store_t, x_mix, y_mix, t_mix)
+    C, Hs, Ws, th, tw = (int(v) for v in geometry)
+    B = int(B)
+    E = 0 if gather is None else int(gather.shape[0])
+    if B:
+        assert x.dtype == torch.float32 and x.numel() >= B * C * th * tw and y.dtype == torch.int64 and y.numel() >= B
+    n_outputs = 1 if store_t is None else int(store_t.shape[1])
+    if E:
+        assert store.dtype == frame_dtype and store.numel() == store.shape[0] * C * Hs * Ws
+        assert gather.dtype == torch.int32 and params.dtype == torch.int32 and tuple(params.shape) == (E, ncols)
+        assert params.is_contiguous()
+        assert store_t.dtype == torch.float32 and store_t.dim() == 2 and store_t.shape[0] >= store.shape[0]
+        assert t_mix.dtype == torch.float32 and t_mix.numel() >= (B + E) * n_outputs
+    if B or E:
+        assert x_mix.dtype == torch.float32 and x_mix.numel() >= (B + E) * C * th * tw
+        assert y_mix.dtype == torch.int64 and y_mix.numel() >= B + E
+    table = ()
+    if frame_dtype == torch.uint8:
+        if E:
+            assert lut is not None, "lut: needed to decode the exemplar rows"
+            _chk_lut(lut, C)
+        table = (_ptr(lut),)
+    check(getattr(_lib.lib(), entry)(
+        _ptr(x) if B else None, _ptr(y) if B else None, B, C, Hs, Ws, th, tw, *table, _ptr(store), 0 if store is None else store.shape[0],
+        _ptr(gather) if E else None, _ptr(params) if E else None, E, _ptr(store_t), n_outputs, _ptr(x_mix), _ptr(y_mix), _ptr(t_mix),
+        _stream()), entry)
+
+
+def icarl_assemble_crop_flip(geometry, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
+    """clhip_icarl_assemble_crop_flip: geometry = (C, Hs, Ws, th, tw); ONE launch writes x[:B] -> x_mix[:B], y[:B] -> y_mix[:B],
+    the (top, left, flip) windows params (device int32[E, 3]) of the frames store[gather] (device int32[E]) -> x_mix[B:B + E],
+    y_mix[B:B + E] = 0 and the target rows store_t[gather] ([rows, n_outputs]) -> t_mix[B:B + E] (t_mix [>= B + E, n_outputs]).
+    B = 0: x, y may be None; no exemplars: gather, params (and the store) may be None."""
+    _icarl_assemble("clhip_icarl_assemble_crop_flip", torch.float32, 3, geometry, None, x, y, B, store, gather, params, store_t,
+                    x_mix, y_mix, t_mix)
+
+
+def icarl_assemble_crop_flip_u8(geometry, lut, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
+    """clhip_icarl_assemble_crop_flip_u8: icarl_assemble_crop_flip with uint8 frames in store, decoded through lut (device float32
+    [C, 256]; may be None without exemplars): bitwise icarl_assemble_crop_flip on the decoded store."""
+    _icarl_assemble("clhip_icarl_assemble_crop_flip_u8", torch.uint8, 3, geometry, lut, x, y, B, store, gather, params, store_t,
+                    x_mix, y_mix, t_mix)
+
+
+def icarl_assemble_resized_crop_flip(geometry, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
+    """clhip_icarl_assemble_resized_crop_flip: icarl_assemble_crop_flip with params device int32[E, 5] of (top, left, h, w, flip):
+    the exemplar rows are the windows resized to th x tw, bitwise gather_tasks_resized_crop_flip over the store."""
+    _icarl_assemble("clhip_icarl_assemble_resized_crop_flip", torch.float32, 5, geometry, None, x, y, B, store, gather, params,
+                    store_t, x_mix, y_mix, t_mix)
+
+
+def icarl_assemble_resized_crop_flip_u8(geometry, lut, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
+    """clhip_icarl_assemble_resized_crop_flip_u8: icarl_assemble_resized_crop_flip with uint8 frames in store (lut as
+    icarl_assemble_crop_flip_u8): bitwise the fp32 entry on the decoded store."""
+    _icarl_assemble("clhip_icarl_assemble_resized_crop_flip_u8", torch.uint8, 5, geometry, lut, x, y, B, store, gather, params,
+                    store_t, x_mix, y_mix, t_mix)

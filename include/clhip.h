@@ -754,6 +754,56 @@ int clhip_icarl_herd(const float* feats, long n_rows, int F, const float* w, con
 int clhip_icarl_nme(const float* feats, const float* means, int N, int F, int C, int offset1, int n_outputs, float* out,
                     void* stream);
 
+/* iCaRL on augmented tasks: the assembly of one update_representation step when the store holds FRAMES.  The reference's
+ * memory holds paths; every step rebuilds the exemplar loader with the task's train transform (icarl.py:560-561), so a
+ * replayed exemplar is a fresh crop, while its distillation target is the row computed once at herding time (:476-479,
+ * mem_class_y, read back at :566-574).
+ *
+ *   icarl_assemble_crop_flip   ONE launch fills the mixed batch of the step: a 1-D grid of three runs of blocks,
+ *                         B x row_blocks     x[r] -> x_mix[r], labels[r] -> labels_mix[r]                  (48 KB segments)
+ *                         E x crop_blocks    the th x tw window at (top, left) of store_frames[gather_rows[e]] [C][Hs][Ws],
+ *                                            mirrored when flip, -> x_mix[B + e];  labels_mix[B + e] = 0   (a distillation
+ *                                            row has no label: the segmented loss reads its target row)
+ *                         target blocks      store_t[gather_rows[e]][0 .. n_outputs) -> t_mix[B + e][0 .. n_outputs)
+ *                       gather_params: device int32[E][3] of (top, left, flip).  The window is copied by the block body of
+ *                       clhip_gather_tasks_crop_flip / clhip_rehearsal_assemble_crop_flip (bitwise their result); the target
+ *                       rows move in 16-byte accesses when n_outputs % 4 == 0 and store_t and t_mix are 16-byte aligned, as
+ *                       floats otherwise; the copy run as clhip_rehearsal_assemble_crop_flip's.  It replaces the two launches
+ *                       of the crop-mode step (clhip_rehearsal_assemble over the images, again over the target rows).
+ *                       B == 0 is the cropping of stored frames alone (x, labels may be NULL); E == 0 the copy alone
+ *                       (everything of the store may be NULL); B == 0 and E == 0 returns 0 at once.
+ *                       A gather row outside [0, store_rows), top outside [0, Hs - th], left outside [0, Ws - tw] or flip
+ *                       outside {0, 1} copies nothing, neither window nor target row, and writes label -1; no address outside
+ *                       a frame or a target row is formed.
+ *                       CLHIP_EINVAL before any launch: a negative B, E or store_rows; C, Hs, Ws, th, tw or n_outputs < 1;
+ *                       th > Hs or tw > Ws; B > 0 without x, labels, x_mix or labels_mix; E > 0 without store_frames,
+ *                       gather_rows, gather_params, store_t, x_mix, labels_mix or t_mix; B + E > 65535.
+ *   icarl_assemble_resized_crop_flip   the same under RandomResizedCrop + flip: gather_params int32[E][5] of (top, left, h, w,
+ *                       flip), the window resampled to th x tw by the block body of clhip_gather_tasks_resized_crop_flip under a
+ *                       plan made for the frame (bitwise that gather's result).  A window may be enlarged (th > Hs is allowed).
+ *                       Bad rows: that gather's rule (h or w < 1, a window outside the frame, flip outside {0, 1}, h >
+ *                       CLHIP_RESIZE_MAX_RATIO th or w > CLHIP_RESIZE_MAX_RATIO tw), treated as above.  CLHIP_ENOTSUP: E > 0 and
+ *                       no plan fits the LDS (clhip_gather_tasks_resized_crop_flip's limit).
+ *   ..._u8              store_frames holds BYTE frames (byte frames, above): a stored byte v of channel c means lut[c][v]
+ *                       (device float32 [C][256], staged per block in LDS), decoded where the window is loaded: bitwise the
+ *                       fp32 entry on the decoded store.  lut may be NULL with E == 0, CLHIP_EINVAL otherwise.           */
+int clhip_icarl_assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                   const float* store_frames, long store_rows, const int* gather_rows, const int* gather_params,
+                                   int E, const float* store_t, int n_outputs, float* x_mix, int64_t* labels_mix, float* t_mix,
+                                   void* stream);
+int clhip_icarl_assemble_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                      const float* lut, const uint8_t* store_frames, long store_rows, const int* gather_rows,
+                                      const int* gather_params, int E, const float* store_t, int n_outputs, float* x_mix,
+                                      int64_t* labels_mix, float* t_mix, void* stream);
+int clhip_icarl_assemble_resized_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                           const float* store_frames, long store_rows, const int* gather_rows,
+                                           const int* gather_params, int E, const float* store_t, int n_outputs, float* x_mix,
+                                           int64_t* labels_mix, float* t_mix, void* stream);
+int clhip_icarl_assemble_resized_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th,
+                                              int tw, const float* lut, const uint8_t* store_frames, long store_rows,
+                                              const int* gather_rows, const int* gather_params, int E, const float* store_t,
+                                              int n_outputs, float* x_mix, int64_t* labels_mix, float* t_mix, void* stream);
+
 #ifdef CLHIP_VISIBILITY_PUSHED
 #pragma GCC visibility pop
 #undef CLHIP_VISIBILITY_PUSHED
