@@ -488,6 +488,16 @@ int clhip_net_layer_paths(void* handle, int layer) {
     // bits 3 / 4: the forward / backward-data launch is the bf16-split kernel (bsconv.hip), not Winograd (bits 0 / 1 then say
     // "prepared-weights path")
     // bit 5: the weight gradient is the bf16-split kernel (bswgrad.hip)
+    if (L.type == 1) {
+        // Linear layers.  bit 6: the layer's forward and backward-data run inside fc_tail_kernel (the layers behind the first
+        // Linear layer of a plan that takes the tail, while none of them has a dropout mask or an extra input gradient set:
+        // tail_usable's plan-side conditions; its per-call ones are the alignment of the caller's buffers and the batch).
+        // bit 7: dW / db come from the fused weight-gradient launch (fc_chain_wgrad_kernel / fc_bwd_combo_kernel).
+        bool tail = p->fc_tail && layer > p->fc_first;
+        for (size_t i = p->fc_first + 1; tail && i < p->layers.size(); ++i)
+            if (p->layers[i].drop || p->layers[i].extra_grad) tail = false;
+        return (tail ? 64 : 0) | ((p->fc_fused && layer >= p->fc_first) ? 128 : 0);
+    }
     return (L.wino_f ? 1 : 0) | (L.wino_d ? 2 : 0) | ((L.wino_w && defer_capable) ? 4 : 0) | ((L.bs_f || L.bs5_f) ? 8 : 0) |
            ((L.bs_d || L.bs5_d) ? 16 : 0) | ((L.bs_w && defer_capable) ? 32 : 0);
 }

@@ -346,15 +346,18 @@ __global__ __launch_bounds__(GB) void project_dev_kernel(const float* __restrict
                                                          const int* __restrict__ info, int m, const float* __restrict__ g,
                                                          float* __restrict__ out, size_t n) {
     if (info[0] == 0 && out == g) return;                   // no violated constraint: the gradient stays as it is (block-uniform)
+    // no violated constraint and out != g: out = g, bit for bit, and no memory row is read (g + 0.0 * G[row] would turn an
+    // Inf / NaN in a row into NaN where gem.py:275-277 leaves the gradient alone); block-uniform like the branch above
+    const int rows = info[0] == 0 ? 0 : m;
     __shared__ double cv[MAXM];                             // (indexed at run time: LDS, not scratch)
-    if ((int)threadIdx.x < m) cv[threadIdx.x] = info[0] == 0 ? 0.0 : (double)(float)v[threadIdx.x];   // v rounded to fp32 as torch.Tensor(x) does downstream
+    if ((int)threadIdx.x < rows) cv[threadIdx.x] = (double)(float)v[threadIdx.x];   // v rounded to fp32 as torch.Tensor(x) does downstream
     __syncthreads();
     size_t stride = (size_t)gridDim.x * GB;
     const size_t n4 = VEC ? n / 4 : 0;
     for (size_t c4 = (size_t)blockIdx.x * GB + threadIdx.x; c4 < n4; c4 += stride) {
         const float4 gv = reinterpret_cast<const float4*>(g)[c4];
         double s0 = (double)gv.x, s1 = (double)gv.y, s2 = (double)gv.z, s3 = (double)gv.w;
-        for (int i = 0; i < m; ++i) {
+        for (int i = 0; i < rows; ++i) {
             const float4 r = reinterpret_cast<const float4*>(G + (size_t)sel.idx[i] * ld)[c4];
             s0 += cv[i] * (double)r.x; s1 += cv[i] * (double)r.y; s2 += cv[i] * (double)r.z; s3 += cv[i] * (double)r.w;
         }
@@ -362,7 +365,7 @@ __global__ __launch_bounds__(GB) void project_dev_kernel(const float* __restrict
     }
     for (size_t c = n4 * 4 + (size_t)blockIdx.x * GB + threadIdx.x; c < n; c += stride) {
         double s = (double)g[c];
-        for (int i = 0; i < m; ++i) s += cv[i] * (double)G[(size_t)sel.idx[i] * ld + c];
+        for (int i = 0; i < rows; ++i) s += cv[i] * (double)G[(size_t)sel.idx[i] * ld + c];
         out[c] = (float)s;
     }
 }

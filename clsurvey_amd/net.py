@@ -292,12 +292,15 @@ class NetEngine:
     def layer_paths(self, layer):
         """{'fwd', 'bwd_data', 'bwd_weight'} -> True where the plan runs the layer's kernel through a prepared-weights path
         (Winograd, csrc/wino.hip) instead of the direct f32 kernels; 'bs_fwd' / 'bs_bwd_data' -> True where that launch is the
-        bf16-split kernel (csrc/bsconv.hip) instead of Winograd; 'bs_bwd_weight' -> the weight gradient is csrc/bswgrad.hip."""
+        bf16-split kernel (csrc/bsconv.hip) instead of Winograd; 'bs_bwd_weight' -> the weight gradient is csrc/bswgrad.hip.
+        Linear layers: 'fc_tail' -> forward and backward-data run inside the fused classifier tail, 'fc_fused' -> the weight
+        and bias gradient come from the fused launch of the whole classifier (csrc/fc_chain.hip; include/clhip.h)."""
         bits = _lib.lib().clhip_net_layer_paths(self._h, int(layer))
         if bits < 0:
             raise RuntimeError("clhip_net_layer_paths(%d)" % layer)
         return {"fwd": bool(bits & 1), "bwd_data": bool(bits & 2), "bwd_weight": bool(bits & 4),
-                "bs_fwd": bool(bits & 8), "bs_bwd_data": bool(bits & 16), "bs_bwd_weight": bool(bits & 32)}
+                "bs_fwd": bool(bits & 8), "bs_bwd_data": bool(bits & 16), "bs_bwd_weight": bool(bits & 32),
+                "fc_tail": bool(bits & 64), "fc_fused": bool(bits & 128)}
 
     def set_input_grad(self, layer, extra):
         """extra [N][in_elems] (or None) is added to the gradient w.r.t. layer_input(layer) in the following backward

@@ -420,7 +420,14 @@ int clhip_net_edge_grid_count(void* handle);
 /* Which kernels the plan chose for a layer (measurement harnesses time the same ones): bit 0 forward, bit 1 backward-data, bit 2
  * weight gradient through a prepared-weights path instead of the direct f32 MFMA kernels — Winograd F(2x2,3x3) (csrc/wino.hip)
  * unless bit 3 (forward) / bit 4 (backward-data) says the launch is the bf16-split kernel (csrc/bsconv.hip); bit 5: the weight
- * gradient is the bf16-split kernel (csrc/bswgrad.hip); < 0 on error. */
+ * gradient is the bf16-split kernel (csrc/bswgrad.hip); < 0 on error.
+ * Linear layers (bits 0 .. 5 are 0 for them): bit 6 (`fc_tail`) the layer's forward and backward-data run inside the fused
+ * classifier tail (fc_tail_kernel, csrc/fc_chain.hip) — set for the Linear layers behind the first one of a plan that takes
+ * the tail (created on a device, CLHIP_FC_TAIL != 0, max_batch <= 1024, widths inside the tail's envelope), as long as none
+ * of them has a dropout mask or an extra input gradient set; a single call still runs the per-layer launches when the
+ * caller's parameter / workspace pointers are not 16-byte aligned or N * (classes | 1) > 12288.  bit 7 (`fc_fused`) the
+ * layer's weight and bias gradient come from the fused launch of the whole classifier (fc_chain_wgrad_kernel, or
+ * fc_bwd_combo_kernel together with the first Linear layer's backward-data). */
 int clhip_net_layer_paths(void* handle, int layer);
 
 /* Side branches off a plan (EBLL's code layers on the flattened features, AlexNet_EBLL.py:110-117): the INPUT activation
