@@ -33,6 +33,12 @@ class HatEmbJob(C.Structure):                      # clhip_hat_emb_job
     _fields_ = [("dgate", _p), ("gate", _p), ("mask_pre", _p), ("demb", _p), ("n", _i), ("rows", _i), ("t", _i), ("reserved", _i)]
 
 
+class PathnetLayer(C.Structure):                    # clhip_pathnet_layer
+    _fields_ = [("w_off", _l), ("b_off", _l), ("pw_off", _l), ("pb_off", _l), ("mod_stride", _l), ("c_out", _i), ("c_in", _i),
+                ("R", _i), ("n_out", _i), ("n_in", _i), ("Kp", _i), ("Cp", _i), ("M", _i), ("path", _i * 8),
+                ("trainable", C.c_ulonglong)]
+
+
 class IcarlClass(C.Structure):                     # clhip_icarl_class
     _fields_ = [("row_begin", _i), ("row_end", _i), ("k", _i), ("out_off", _i)]
 
@@ -120,6 +126,10 @@ SIGNATURES = {
     "clhip_hat_scale_weights_multi": (_i, [_p, _i, _p]),
     "clhip_hat_weight_grads_multi": (_i, [_p, _i, _p]),
     "clhip_hat_emb_grads_multi": (_i, [_p, _i, _f, _f, _f, _p, _p]),
+    "clhip_pathnet_ws": (_z, [_p, _i]),
+    "clhip_pathnet_pack_multi": (_i, [_p, _i, _p, _z, _p, _z, _p]),
+    "clhip_pathnet_fold_grads_multi": (_i, [_p, _i, _p, _z, _p, _z, _p, _z, _p]),
+    "clhip_pathnet_sgd_step": (_i, [_p, _i, _p, _p, _p, _z, _f, _f, _f, _f, _i, _p, _z, _p]),
     "clhip_softmax_ce_slice": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "clhip_net_loss_step_slice": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "clhip_axpy": (_i, [_p, _p, _z, _f, _i, _p]),

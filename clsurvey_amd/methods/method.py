@@ -33,6 +33,7 @@ from . import ewc as _ewc
 from . import finetune as _ft
 from . import gem_main as _gem
 from . import hat_main as _hat
+from . import pathnet_main as _pathnet
 from . import icarl_main as _icarl
 from . import imm as _imm
 from . import lwf as _lwf
@@ -170,12 +171,29 @@ def _out_hat_gated(method, images, args):
     return eng.forward(args.task_idx, images, args.model.smax)
 
 
+def _out_pathnet(method, images, args):
+    """Pathnet.get_output (method.py:580-587): the task's head goes in, forward over bestPath[task_idx]; the path is packed
+    once per (model, head, task), not once per batch."""
+    from . import pathnet as PN
+    head = args.heads[args.current_head_idx]
+    eng = getattr(args, "_pathnet_engine", None)
+    if eng is None or eng.net is not args.model or eng.net.classifier[0] is not head or eng.N != args.model.N:
+        args.model.classifier = torch.nn.ModuleList([head])
+        eng = args._pathnet_engine = PN.PathEngine(args.model, args.batch_size, tuple(images.shape[1:]), images.device)
+        eng.task = None
+    args.model.eval()
+    if eng.task != args.task_idx:
+        eng.set_path(args.model.bestPath[args.task_idx], args.task_idx)
+        eng.task = args.task_idx
+    return eng.forward(images)
+
+
 def _out_joint(method, images, args):
     raise NotImplementedError("JOINT has custom testing method for shared head.")
 
 
 OUTPUT = {"swap_head": _out_swap_head, "own_heads": _out_own_heads, "gem_slice": _out_gem_slice, "hat_gated": _out_hat_gated,
-          "joint": _out_joint, "icarl_nme": _out_icarl_nme}
+          "joint": _out_joint, "icarl_nme": _out_icarl_nme, "pathnet": _out_pathnet}
 
 
 def _test(manager, model, args, head_idx, heads):
@@ -396,6 +414,33 @@ def _hat_grid_train(self, args, manager, lr):
 
 def _hat_train(self, args, manager, hyperparams):
     return _hat_run(self, args, manager, list(hyperparams.values()), manager.heuristic_exp_dir, False)
+
+
+def _pathnet_run(self, args, manager, parameter, out_dir, finetune):
+    kw = {k: _resolve(v, self, args, manager, None, None) for k, v in _HAT_ARGS.items()}
+    kw.update(prev_model_path=manager.previous_task_model_path, output=out_dir, parameter=parameter, approach="pathnet",
+              n_tasks=manager.dataset.task_count, is_scratch_model=args.task_counter == 1,
+              nc_per_task=_classes_per_task(manager), finetune_mode=finetune)
+    manager.overwrite_args = kw
+    return _pathnet.main(kw, device=_dev(args))
+
+
+def _pathnet_grid_train(self, args, manager, lr):
+    args.lr = lr
+    parameter = list(self.hyperparams.values()) + list(self.static_hyperparams.values())       # [N, M, generations]
+    return _pathnet_run(self, args, manager, parameter, manager.gridsearch_exp_dir, True)
+
+
+def _pathnet_train(self, args, manager, hyperparams):
+    assert args.decaying_factor == 1
+    parameter = list(hyperparams.values()) + list(self.static_hyperparams.values())
+    return _pathnet_run(self, args, manager, parameter, manager.heuristic_exp_dir, False)
+
+
+def _pathnet_decay_operator(a, decaying_factor):
+    """N grows by one per framework attempt instead of decaying (method.py:589-593)."""
+    assert decaying_factor == 1
+    return int(a + decaying_factor)
 
 
 def _gem_run(self, args, manager, strength, out_dir, prev=None, finetune=False, postprocess=False):
@@ -623,6 +668,11 @@ SPECS = [
     _spec("HAT", Category.MASK_BASED, hyper=[("smax", 800), ("c", 2.5)], flags=("start_scratch",), phase1=None,
           output="hat_gated", hooks={"grid_train": _hat_grid_train, "train": _hat_train},
           doc="hard attention to the task; accuracies are fractions in [0, 1] (method.py:600-660)"),
+    _spec("pathnet", Category.MASK_BASED, hyper=[("N", 3)], static=[("M", 20), ("generations", 35)], flags=("start_scratch",),
+          phase1=None, output="pathnet", attrs={"extra_hyperparams_count": 3},          # M, N, generations
+          hooks={"grid_train": _pathnet_grid_train, "train": _pathnet_train,
+                 "decay_operator": staticmethod(_pathnet_decay_operator)},
+          doc="N of M modules per layer, binary tournament over paths, the best path of a task frozen (method.py:559-597)"),
     _spec("GEM", Category.REHEARSAL_BASED, hyper=[("margin", 1)], static=[("mem_per_task", 1024)],
           flags=("wrap_first_task_model",), phase1=None, output="gem_slice", evaluate="as_is",
           hooks={"grid_train": _gem_grid_train, "train": _gem_train, "poststep": _gem_poststep},
@@ -688,7 +738,7 @@ def _build_class(spec):
     ns.update(spec["hooks"])
     if spec["phase2"] is None and "train" not in spec["hooks"]:
         ns["train"] = None                      # grid-only methods have no phase 2; the drivers never ask for it
-    cls_name = {"finetuning": "Finetune", "joint": "Joint", "packnet": "PackNet", "finetuning_rehearsal_partial_mem": "FinetuneRehearsalPartialMem",
+    cls_name = {"finetuning": "Finetune", "joint": "Joint", "packnet": "PackNet", "pathnet": "Pathnet", "finetuning_rehearsal_partial_mem": "FinetuneRehearsalPartialMem",
                 "finetuning_rehearsal_full_mem": "FinetuneRehearsalFullMem"}.get(spec["name"], spec["name"])
     return type(cls_name, (Method,), ns)
 

@@ -365,6 +365,46 @@ int clhip_hat_weight_grads_multi(const clhip_hat_wgrad_job* jobs, int n_jobs, vo
 int clhip_hat_emb_grads_multi(const clhip_hat_emb_job* jobs, int n_jobs, float s, float lamb, float count, const double* sums2,
                               void* stream);
 
+/* ------------------------------------------------------------------ PathNet (networks/vgg_pathnet.py, approaches/pathnet.py)
+ * A path (N of M modules per layer, summed behind ReLU / pool) runs as a plain narrow net over a PACKED arena:
+ *   layer 0     Wp[n*c_out + k][j][r]            = mod[path[n]].w[k][j][r]
+ *   layer l > 0 Wp[n*c_out + k][m*c_in + j][r]   = mod[path[n]].w[k][j][r]  for every m < n_in   (n_in = N of the layer before)
+ *   head        n_out = 1, M = 1, path[0] = 0
+ * with every packed width padded by zero rows / columns to Kp x Cp.  One table row per layer (the head is a row); all
+ * offsets count floats from the arena bases handed to the call; the modules of one layer lie mod_stride floats apart
+ * (weight and bias alike).  path[n] < 0: the slot contributes nothing.  trainable: bit i = module i trains
+ * (vgg_pathnet.py:130-150); only modules that are trainable AND in path[0..n_out) are folded / stepped, every other
+ * module's gradient, momentum and weights are left untouched.
+ *   pathnet_pack_multi        module arena -> packed arena (bitwise copies, padding = 0), ONE launch
+ *   pathnet_fold_grads_multi  packed gradient -> g[mod][k][j][r] = sum_{n: path[n]==mod} sum_m G[n*c_out+k][m*c_in+j][r]
+ *                             (n, then m, ascending); biases over the duplicate slots; ws receives one double per block:
+ *                             the sum of squares of what the block wrote (0 for a block without work)
+ *   pathnet_sgd_step          clip_grad_norm(active, clipgrad) (coef = clip / (norm + 1e-6), applied when < 1; the norm is the
+ *                             fixed-order sum of ws) then SGD: g += wd*p; buf = first ? g : momentum*buf + g; p -= lr*buf
+ * ws: clhip_pathnet_ws(layers, n_layers) bytes, the same table for fold and step.                                            */
+#define CLHIP_PATHNET_MAX_N 8
+#define CLHIP_PATHNET_MAX_LAYERS 24
+typedef struct {
+    long w_off, b_off;          /* module 0's weight / bias in the module arenas */
+    long pw_off, pb_off;        /* packed weight / bias in the packed arenas */
+    long mod_stride;
+    int c_out, c_in, R;         /* one module's weight is [c_out][c_in][R] */
+    int n_out, n_in;            /* slots of this layer, slots of the layer before (1 for layer 0) */
+    int Kp, Cp;                 /* packed weight is [Kp][Cp][R], Kp >= n_out*c_out, Cp >= n_in*c_in */
+    int M;
+    int path[CLHIP_PATHNET_MAX_N];
+    unsigned long long trainable;
+} clhip_pathnet_layer;
+size_t clhip_pathnet_ws(const clhip_pathnet_layer* layers, int n_layers);
+/* mod_numel / packed_numel: floats in the module / packed arenas; a table that names a slot beyond them is CLHIP_EINVAL */
+int clhip_pathnet_pack_multi(const clhip_pathnet_layer* layers, int n_layers, const float* mod_theta, size_t mod_numel,
+                             float* packed_theta, size_t packed_numel, void* stream);
+int clhip_pathnet_fold_grads_multi(const clhip_pathnet_layer* layers, int n_layers, const float* packed_grad, size_t packed_numel,
+                                   float* mod_grad, size_t mod_numel, void* ws, size_t ws_bytes, void* stream);
+int clhip_pathnet_sgd_step(const clhip_pathnet_layer* layers, int n_layers, float* mod_theta, float* mod_grad, float* mod_buf,
+                           size_t mod_numel, float lr, float momentum, float wd, float clipgrad, int first, const void* ws,
+                           size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ static-plan net executor
  * One call per pass for VGG-style nets instead of one Python dispatch per op
  * (replaces `outputs = model(inputs); loss.backward()` of EWC/train_EWC.py:181-187,
