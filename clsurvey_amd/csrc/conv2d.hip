@@ -378,6 +378,7 @@ __global__ void conv2d_bias_finish_kernel(const double* __restrict__ part, float
 bool conv_ok(int N, int C, int H, int W, int K, int R, int S, int st, int pad, int& OH, int& OW) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || R <= 0 || S <= 0 || st <= 0 || pad < 0) return false;
     if (R > 255 || S > 255) return false;
+    if (H + 2 * pad < R || W + 2 * pad < S) return false;     // (a negative numerator would round towards 0: OH = 1 for stride > R - H - 2 pad)
     OH = (H + 2 * pad - R) / st + 1; OW = (W + 2 * pad - S) / st + 1;
     if (OH <= 0 || OW <= 0) return false;
     if ((long long)N * C * H * W > 0x1fffffffLL || (long long)N * K * OH * OW > 0x1fffffffLL) return false;   // 32-bit byte offsets
@@ -410,7 +411,12 @@ int wgrad_splits(int M, int Nn, long Kd) {
 }
 
 // (the LDS-halo kernel of convkk.hip wherever its shape domain allows; the gather-GEMM serves the rest)
+// CLHIP_NO_HALO_CONV: test builds only (tests/test_gpu_conv2d_kernels.py runs the halo shapes through both kernels)
+#ifdef CLHIP_NO_HALO_CONV
+bool halo_kernel() { return false; }
+#else
 bool halo_kernel() { return true; }
+#endif
 
 }  // namespace
 

@@ -1,6 +1,7 @@
 """Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py,
 test_gpu_gemm_kernels.py, test_gpu_pool_kernels.py, test_gpu_bn_kernels.py, test_gpu_packnet_kernels.py,
-test_gpu_elementwise_kernels.py, test_gpu_gem_kernels.py, test_gpu_fc_chain_kernels.py) — test infrastructure.
+test_gpu_elementwise_kernels.py, test_gpu_gem_kernels.py, test_gpu_fc_chain_kernels.py, test_gpu_conv2d_kernels.py,
+test_gpu_conv5x5_bs_kernels.py) — test infrastructure.
 
 The fp32-chain rule is the one of assert_fp32_parity in test_gpu_parity.py with the bounds these two files use: the device
 result's distance from an fp64 evaluation of the same formula on the same float32 inputs, relative to the tensor's largest
@@ -62,6 +63,29 @@ def bit_pattern(n, bits):
 
 def all_bits(t, bits):
     return bool((t.detach().cpu().contiguous().view(torch.int32) == bits).all())
+
+
+class ConvRef:
+    """fp64 and float32-CPU results of one convolution layer on float32 operands x [N][C][H][W], w [K][C][R][S], dy [N][K][OH][OW]
+    (zero padding `pad`, stride `stride`): y (no bias), dx, dw, db, and for each product the same product of the operands'
+    absolute values (s_y, s_dx, s_dw: what a float32 rounding analysis of a dot product is measured in)."""
+
+    def __init__(self, x, w, dy, stride, pad):
+        import torch.nn.functional as F
+        from torch.nn.grad import conv2d_input, conv2d_weight
+        xd, wd, dyd = x.double(), w.double(), dy.double()
+        self.y64 = F.conv2d(xd, wd, None, stride, pad)
+        assert self.y64.shape == dy.shape, (self.y64.shape, dy.shape)
+        self.s_y = F.conv2d(xd.abs(), wd.abs(), None, stride, pad)
+        self.y32 = F.conv2d(x, w, None, stride, pad)
+        self.dx64 = conv2d_input(x.shape, wd, dyd, stride, pad)
+        self.s_dx = conv2d_input(x.shape, wd.abs(), dyd.abs(), stride, pad)
+        self.dx32 = conv2d_input(x.shape, w, dy, stride, pad)
+        self.dw64 = conv2d_weight(xd, w.shape, dyd, stride, pad)
+        self.s_dw = conv2d_weight(xd.abs(), w.shape, dyd.abs(), stride, pad)
+        self.dw32 = conv2d_weight(x, w.shape, dy, stride, pad)
+        self.db64 = dyd.sum((0, 2, 3))
+        self.s_db = dyd.abs().sum((0, 2, 3))
 
 
 class Arena:
