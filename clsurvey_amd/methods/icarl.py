@@ -53,7 +53,7 @@ from .gem import extend_head
 from .rehearsal import _Order
 
 T_DISTILL = 2.0                 # update_representation(..., T=2)
-HERD_MAX_FEATS = 4096           # CLHIP_ICARL_MAX_FEATS (include/clhip.h)
+HERD_MAX_FEATS = 16384          # CLHIP_ICARL_MAX_FEATS_WIDE (include/clhip.h): ops.icarl_herd picks the entry by width
 
 
 def init_head(model, n_outputs):

@@ -1020,24 +1020,39 @@ def loss_segments(logits, labels, targets, segs, n_segs, T=2.0, stats=None, dlog
 ICARL_MAX_CLASSES = 128          # CLHIP_ICARL_MAX_CLASSES (include/clhip.h): classes per herding launch
 
 
-def icarl_herd(feats, weights, ranges, ks, flat=False):
+ICARL_MAX_FEATS = 4096           # CLHIP_ICARL_MAX_FEATS: the widest features of clhip_icarl_herd (mu, S, r in LDS)
+
+
+def icarl_herd(feats, weights, ranges, ks, flat=False, wide=None):
     """clhip_icarl_herd: feats [n_rows, F] fp32, weights [n_rows] fp32 (per-row mean weights), ranges = [(row_begin, row_end)]
     per class (any number: ICARL_MAX_CLASSES per launch), ks the picks per class.  Returns [ranking of class c]
     as device int32 tensors (row numbers relative to the class's first row); flat=True: the one ranking tensor (classes back
-    to back) and the int64 offsets of the classes in it.  No synchronisation."""
+    to back) and the int64 offsets of the classes in it.  No synchronisation.
+    wide=None: F <= ICARL_MAX_FEATS takes clhip_icarl_herd, wider features clhip_icarl_herd_wide (mu and S in a workspace,
+    F <= 16384); True / False force the one or the other entry, which refuses what it cannot take."""
     import numpy as np
     _chk(feats, weights)
     if feats.dtype != torch.float32 or weights.dtype != torch.float32 or feats.dim() != 2 or weights.numel() != feats.shape[0]:
         raise RuntimeError("herding needs fp32 HIP tensors: feats [n_rows, F], weights [n_rows]")
     offs = np.concatenate([[0], np.cumsum(ks)]).astype(np.int64)
     ranking = torch.empty(max(int(offs[-1]), 1), dtype=torch.int32, device=feats.device)
+    L = _lib.lib()
+    F = int(feats.shape[1])
+    if wide is None:
+        wide = F > ICARL_MAX_FEATS
+    if wide:                                             # one workspace for every chunk: the launches are stream-ordered
+        ws = workspace(L.clhip_icarl_herd_wide_ws(min(len(ranges), ICARL_MAX_CLASSES), F), feats.device, "icarl_herd")
     for s in range(0, len(ranges), ICARL_MAX_CLASSES):
         part = ranges[s:s + ICARL_MAX_CLASSES]
         tab = (_lib.IcarlClass * len(part))()
         for i, (lo, hi) in enumerate(part):
             tab[i].row_begin, tab[i].row_end, tab[i].k, tab[i].out_off = int(lo), int(hi), int(ks[s + i]), int(offs[s + i])
-        check(_lib.lib().clhip_icarl_herd(_ptr(feats), feats.shape[0], feats.shape[1], _ptr(weights), tab, len(part), _ptr(ranking),
-                                          ranking.shape[0], _stream()), "clhip_icarl_herd")
+        if wide:
+            check(L.clhip_icarl_herd_wide(_ptr(feats), feats.shape[0], F, _ptr(weights), tab, len(part), _ptr(ranking),
+                                          ranking.shape[0], _ptr(ws), ws.numel(), _stream()), "clhip_icarl_herd_wide")
+        else:
+            check(L.clhip_icarl_herd(_ptr(feats), feats.shape[0], F, _ptr(weights), tab, len(part), _ptr(ranking),
+                                     ranking.shape[0], _stream()), "clhip_icarl_herd")
     return (ranking, offs) if flat else [ranking[int(offs[i]):int(offs[i + 1])] for i in range(len(ranges))]
 
 

@@ -789,15 +789,27 @@ int clhip_rehearsal_assemble_resized_crop_flip_u8(const float* x, const int64_t*
  *                       || r - f_i ||, r = (k + 1) mu - S_k (the same quantity times k + 1: no Gram matrix, no expanded
  *                       square), differences in fp32, squares summed in f64; the lowest row wins a tie.
  *                       F <= CLHIP_ICARL_MAX_FEATS (mu, S and r live in LDS).
- *   icarl_nme           out[N][n_outputs] = 0, and 1 at offset1 + argmin_c || means[c] - feats[i] || (c < C, the first
+ *   icarl_herd_wide     the same table, launch shape and result for F <= CLHIP_ICARL_MAX_FEATS_WIDE (deep_VGG22 at 64x64,
+ *                       the widest classifier input of the model table): one pick-loop body serves both entries, so the
+ *                       rankings are equal bit for bit wherever both accept F.  Only r, the vector the pick loop reads, and
+ *                       the taken bits are in LDS (72 KB, static); mu and S live in ws, fp32 [n_classes][2][F] in device
+ *                       memory, touched once per pick by the thread that wrote them.  ws_bytes >=
+ *                       clhip_icarl_herd_wide_ws(n_classes, F) = n_classes * 2 * F * 4 bytes exactly (no rounding; 0 for an
+ *                       n_classes or F outside the limits); ws == NULL or too small is CLHIP_EINVAL, as every other refusal,
+ *                       before any launch.  Launches on one stream may share ws.
+ *   icarl_nme          out[N][n_outputs] = 0, and 1 at offset1 + argmin_c || means[c] - feats[i] || (c < C, the first
  *                       minimum wins; squares summed in f64, distances compared in fp32).  means == NULL: the task has no
  *                       exemplars yet, out = -10e10 everywhere and 1 / C inside [offset1, offset1 + C) (:146-155).        */
 #define CLHIP_ICARL_MAX_CLASSES 128
 #define CLHIP_ICARL_MAX_FEATS 4096
+#define CLHIP_ICARL_MAX_FEATS_WIDE 16384
 #define CLHIP_ICARL_MAX_CLASS_ROWS 65536
 typedef struct clhip_icarl_class { int row_begin; int row_end; int k; int out_off; } clhip_icarl_class;
 int clhip_icarl_herd(const float* feats, long n_rows, int F, const float* w, const clhip_icarl_class* classes_host,
                      int n_classes, int* ranking, long ranking_len, void* stream);
+size_t clhip_icarl_herd_wide_ws(int n_classes, int F);
+int clhip_icarl_herd_wide(const float* feats, long n_rows, int F, const float* w, const clhip_icarl_class* classes_host,
+                          int n_classes, int* ranking, long ranking_len, void* ws, size_t ws_bytes, void* stream);
 int clhip_icarl_nme(const float* feats, const float* means, int N, int F, int C, int offset1, int n_outputs, float* out,
                     void* stream);
 

@@ -8,7 +8,14 @@
         fused_us       IcarlNet.observe: assemble + clhip_net_loss_step_loss_segments + SGD
         segmented_us   the same step, one pass per chunk (the BatchNorm path)
         plain_us       loss_step + SGD over 268 images: the floor
-python tools/icarl_bench.py [--rounds 7] [--iters 20] [--warmup 5] [--out profiles/icarl_bench.json]"""
+python tools/icarl_bench.py [--rounds 7] [--iters 20] [--warmup 5] [--out profiles/icarl_bench.json]
+  --herd_wide: herding ALONE over synthetic features (no net): 20 classes x 400 rows, K = 51 and K = 400, four variants that
+      alternate inside every round:
+        narrow_4096    clhip_icarl_herd at F = 4096 (mu, S, r in LDS)
+        wide_4096      clhip_icarl_herd_wide forced at the same features: what mu and S in device memory cost (never chosen there)
+        wide_8192      clhip_icarl_herd_wide at wide_VGG9's width
+        wide_16384     ... at deep_VGG22's
+python tools/icarl_bench.py --herd_wide [--rounds 7] [--out profiles/icarl_wide_bench.json]"""
 import argparse
 import json
 import os
@@ -86,13 +93,49 @@ def torch_herd(feats, w, ranges, ks):
     return out
 
 
+def herd_wide(a):
+    from clsurvey_amd import ops
+    from clsurvey_amd.methods.icarl import mean_weights
+    gen = torch.Generator(device="cuda").manual_seed(38)
+    n = 8000
+    z = torch.randn((n, 3), device="cuda", generator=gen)
+
+    def feats(F):                                  # the tests' features: a ReLU of a rank-3 pattern plus noise
+        return torch.relu(z @ torch.randn((3, F), device="cuda", generator=gen) + 0.05 * torch.randn((n, F), device="cuda", generator=gen))
+    f = {F: feats(F) for F in (4096, 8192, 16384)}
+    ranges = [(400 * c, 400 * (c + 1)) for c in range(20)]
+    wts = torch.from_numpy(np.concatenate([mean_weights(400, 132)] * 20)).cuda()
+    res = {"classes": 20, "rows_per_class": 400, "features": "relu(rank-3 pattern + 0.05 noise)"}
+    for K in (51, 400):
+        ks = [K] * 20
+        fns = {"narrow_4096": lambda: ops.icarl_herd(f[4096], wts, ranges, ks, flat=True, wide=False),
+               "wide_4096": lambda: ops.icarl_herd(f[4096], wts, ranges, ks, flat=True, wide=True),
+               "wide_8192": lambda: ops.icarl_herd(f[8192], wts, ranges, ks, flat=True),
+               "wide_16384": lambda: ops.icarl_herd(f[16384], wts, ranges, ks, flat=True)}
+        t = timed_together(fns, 1, 2, a.rounds)        # millisecond-scale calls: one call per window
+        out = {name: summary(v) for name, v in t.items()}
+        out["rankings_equal_at_4096"] = bool(torch.equal(fns["narrow_4096"]()[0], fns["wide_4096"]()[0]))
+        out["wide_over_narrow_at_4096"] = out["wide_4096"]["median_us"] / out["narrow_4096"]["median_us"]
+        res["K%d" % K] = out
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--herd_wide", action="store_true", help="time herding alone at F = 4096 (both entries), 8192 and 16384")
     a = ap.parse_args()
+    if a.herd_wide:
+        res = herd_wide(a)
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     from clsurvey_amd.methods.icarl import mean_weights
     random.seed(0)
     np.random.seed(0)
