@@ -933,9 +933,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c3_relu_pool_kernel(
 //   unit = (row pair, 32-channel half): 56 MFMAs.  Units are dealt to the 1024 SIMDs of the chip as contiguous ranges (12 or
 //   13 each at N = 200), split over the two resident waves of a SIMD (512-thread blocks, one per CU): the balance of the
 //   old kernel, and consecutive units of a wave share their staged halo (two channel halves per row pair).
-#ifndef CLHIP_C3W64
-#define CLHIP_C3W64 1
-#endif
 // (Measured and removed, round 6: the B operands of a unit as 12 ds_read2_b64 — the four floats X[c][halo row][2 li .. 2 li + 3] around a
 // lane's two pixel columns, even row stride, operands picked by name + 20 v_cndmask — instead of 22 two-dword reads: 43.0 against
 // 43.1 us; the 13.5 us the LDS reads cost by ablation are not a matter of the instruction count.  tools/experiments/r06_b9.sh)
@@ -943,47 +940,22 @@ constexpr int W6_TWP = 67;                          // odd row stride: the two t
 constexpr int W6_PLANE = 4 * W6_TWP;                // 4 halo rows per channel
 constexpr int W6_HALO = 3 * W6_PLANE;               // 804 floats per wave and buffer
 
-// Timing-only ablations (tools/experiments; results wrong by design; the product is built with 0): 1 no stores, 2 no pooling
-// arithmetic, 4 no LDS reads of the B operands, 8 no MFMAs
-#ifndef C3W64_ABL
-#define C3W64_ABL 0
-#endif
-// 1: the bias rides in the 28th slot of K (second half of the last k-pair; A = bias, B = 1.0 from ones_s) and arrives inside the last
-// MFMA of the chain instead of through 64 v_add_f32 per unit in the epilogue (measured ~ -0.8 us of 44).  The sum then differs from
-// "(sum over 27 taps) + bias" by the rounding of one addition — fp32-grade either way, but ANY change of the last bit re-draws the
-// outcome of the bench's ill-conditioned 10-task sweep, and the draw of the bit pattern of rounds 3 - 6 is the recorded one:
-// default 0, the product adds the bias behind the chain as every other conv kernel of the library does.
-#ifndef CLHIP_C3W64_BIAS_IN_K
-#define CLHIP_C3W64_BIAS_IN_K 0
-#endif
-#if C3W64_ABL & 8
-__device__ __forceinline__ floatx16 c3w64_fake_mfma(float a, float b, floatx16 c) { c[0] += a * b; return c; }
-#define C3W64_MFMA(a, b, c, x, y, z) c3w64_fake_mfma(a, b, c)
-#else
-#define C3W64_MFMA(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, x, y, z)
-#endif
+// (Measured and not adopted, round 6: the bias in the 28th slot of K — A = bias, B = 1.0 — instead of 64 v_add_f32 per unit in the
+// epilogue, ~ -0.8 us of 44.  The sum then differs from "(sum over 27 taps) + bias" by the rounding of one addition, and ANY change of
+// the last bit re-draws the outcome of the bench's ill-conditioned 10-task sweep: the bias is added behind the chain, as in
+// every other conv kernel of the library.)
 // The block body over an LDS base and a block index (bx of gx blocks along the units, by = channel tile), so that the SAME code is both
 // the launch of its own (conv3x3_c3w64_relu_pool_kernel) and the first-layer half of a merged grid (c3w64_relu_pool_wt_kernel below).
-// halo_s: 8 * 2 * W6_HALO floats, 16-byte aligned; aux_s: KT floats (bias) or W6_TWP + 5 (CLHIP_C3W64_BIAS_IN_K: ones).
-constexpr int W6_AUX = CLHIP_C3W64_BIAS_IN_K ? W6_TWP + 5 : KT;
+// halo_s: 8 * 2 * W6_HALO floats, 16-byte aligned; bias_s: KT floats.
 template <bool FULL>       // FULL: every block owns 64 real output channels (no per-store channel predicate)
 __device__ __forceinline__ void c3w64_relu_pool_body(
-    float* __restrict__ halo_s, float* __restrict__ aux_s, const int bx, const int by, const int gx,
+    float* __restrict__ halo_s, float* __restrict__ bias_s, const int bx, const int by, const int gx,
     const float* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ bias,
     float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N, int Cout, int H, int W,
     int tiles_w, int row_pairs, int ntiles) {
-#if CLHIP_C3W64_BIAS_IN_K
-    float* const ones_s = aux_s;
-#else
-    float* const bias_s = aux_s;
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kk = lane >> 5;
     const int ko0 = by * KT;
-#if CLHIP_C3W64_BIAS_IN_K
-    if (tid < W6_TWP + 5) ones_s[tid] = 1.f;
-#else
     if (tid < KT) bias_s[tid] = (bias && ko0 + tid < Cout) ? bias[ko0 + tid] : 0.f;
-#endif
 
     // K order and pairing: as in conv3x3_c3_relu_pool_kernel (the two taps of a pair differ by a fixed LDS offset)
     float a[2][14];
@@ -1001,9 +973,6 @@ __device__ __forceinline__ void c3w64_relu_pool_body(
         for (int half = 0; half < 2; ++half) {
             const int ch = ko0 + 32 * half + li;
             a[half][j] = (real && ch < Cout) ? wt[(size_t)ch * 27 + c * 9 + r * 3 + s2] : 0.f;
-#if CLHIP_C3W64_BIAS_IN_K
-            if (j == 13 && kk == 1) a[half][j] = (bias && ch < Cout) ? bias[ch] : 0.f;
-#endif
         }
     }
     const int b_row = 2 * li + kk * W6_TWP, b_col = 2 * li + kk, b_pln = 2 * li + kk * W6_PLANE;
@@ -1011,7 +980,7 @@ __device__ __forceinline__ void c3w64_relu_pool_body(
         if (j < 9) return b_row + (j / 3) * W6_PLANE + (j % 3);
         if (j < 12) return b_col + (j - 9) * W6_PLANE + 2 * W6_TWP;
         if (j == 12) return b_pln + 2 * W6_TWP + 2;
-        return 2 * li + 2 * W6_PLANE + 2 * W6_TWP + 2;              // kk = 1 reads the same finite value; its A is 0 (or: the bias slot, reads ones_s)
+        return 2 * li + 2 * W6_PLANE + 2 * W6_TWP + 2;              // kk = 1 reads the same finite value; its A is 0
     };
 
     // units of this wave
@@ -1060,7 +1029,7 @@ __device__ __forceinline__ void c3w64_relu_pool_body(
     const int chw = OH * OW;
     const __amdgpu_buffer_rsrc_t r_o = clhip_rsrc(out, (size_t)N * Cout * chw * 4);
     const __amdgpu_buffer_rsrc_t r_i = clhip_rsrc(pool_idx, (size_t)N * Cout * chw);
-    __syncthreads();                                // ones_s / bias_s
+    __syncthreads();                                // bias_s
     if (u0 >= u1) return;
     int t_cur = u0 >> 1;
     const int t_last = (u1 - 1) >> 1;
@@ -1082,29 +1051,21 @@ __device__ __forceinline__ void c3w64_relu_pool_body(
             for (int row = 0; row < 2; ++row)
 #pragma unroll
                 for (int par = 0; par < 2; ++par)
-#if C3W64_ABL & 4          // timing only: no LDS reads of the B operands
-                    b[row][par][j] = __int_as_float(0x3f800000 + j + row + par + lane);
-#else
-#if CLHIP_C3W64_BIAS_IN_K
-                    b[row][par][j] = (j == 13 && kk == 1) ? ones_s[row * W6_TWP + par] : xs[b_addr(j) + row * W6_TWP + par];
-#else
                     b[row][par][j] = xs[b_addr(j) + row * W6_TWP + par];
-#endif
-#endif
         __builtin_amdgcn_sched_barrier(0);          // all LDS reads in flight before the first MFMA
         {   // first k-pair: C operand is the constant 0 (no 64 v_mov to clear the accumulators)
             const floatx16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[0][0] = C3W64_MFMA(ac[0], b[0][0][0], zero, 0, 0, 0);
-            acc[0][1] = C3W64_MFMA(ac[0], b[0][1][0], zero, 0, 0, 0);
-            acc[1][0] = C3W64_MFMA(ac[0], b[1][0][0], zero, 0, 0, 0);
-            acc[1][1] = C3W64_MFMA(ac[0], b[1][1][0], zero, 0, 0, 0);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[0], b[0][0][0], zero, 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[0], b[0][1][0], zero, 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[0], b[1][0][0], zero, 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[0], b[1][1][0], zero, 0, 0, 0);
         }
 #pragma unroll
         for (int j = 1; j < 14; ++j) {
-            acc[0][0] = C3W64_MFMA(ac[j], b[0][0][j], acc[0][0], 0, 0, 0);
-            acc[0][1] = C3W64_MFMA(ac[j], b[0][1][j], acc[0][1], 0, 0, 0);
-            acc[1][0] = C3W64_MFMA(ac[j], b[1][0][j], acc[1][0], 0, 0, 0);
-            acc[1][1] = C3W64_MFMA(ac[j], b[1][1][j], acc[1][1], 0, 0, 0);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[j], b[0][0][j], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[j], b[0][1][j], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[j], b[1][0][j], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[j], b[1][1][j], acc[1][1], 0, 0, 0);
         }
         // The next row pair's halo (loaded while this one computed) goes to the other LDS buffer HERE, between the MFMAs and the
         // output stores, and the loads of the row pair after it are issued here too.  Vector-memory operations of a wave complete in
@@ -1128,22 +1089,11 @@ __device__ __forceinline__ void c3w64_relu_pool_body(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int c0 = (r & 3) + 8 * (r >> 2);
-#if CLHIP_C3W64_BIAS_IN_K
-            const float bv = 0.f;                   // (already in the accumulators: see a[][13])
-#else
             const float bv = bias_s[32 * half + 4 * kk + c0];
-#endif
             // max(relu(.)) = relu(max(.)), and while the maximum is positive the first window position that holds it is the same before
             // and after the ReLU (smaller positions are <= it either way); a non-positive maximum is a dead window: same values and
             // codes as the scan over the four ReLU outputs, 15 instead of 21 VALU instructions per pooled value (they add to the
             // f32-MFMA time of the SIMD's other wave)
-#if C3W64_ABL & 2          // timing only: no pooling arithmetic
-            const float m2 = acc[0][0][r] + acc[0][1][r] + acc[1][0][r] + acc[1][1][r];
-            const bool cok2 = FULL || cbase + c0 + 4 * kk < Cout;
-            clhip_buf_store(m2, r_o, cok2 ? ovoff * 4 : CLHIP_OOB, (obase + c0 * chw) * 4);
-            clhip_buf_store_u8((uint8_t)r, r_i, cok2 ? ovoff : CLHIP_OOB, obase + c0 * chw);
-            continue;
-#endif
             const float tl = acc[0][0][r] + bv, tr = acc[0][1][r] + bv, bl = acc[1][0][r] + bv, br = acc[1][1][r] + bv;
             // (v_max3 / v_max by name: fmaxf() on an MFMA result first canonicalises it with a v_max_f32 x, x of its own)
             float mx, m;
@@ -1156,14 +1106,8 @@ __device__ __forceinline__ void c3w64_relu_pool_body(
             if (!(mx > 0.f)) am = CLHIP_POOL_DEAD;
             asm("v_max_f32 %0, 0, %1" : "=v"(m) : "v"(mx));
             const bool cok = FULL || cbase + c0 + 4 * kk < Cout;
-#if C3W64_ABL & 1          // timing only: no stores (one lane keeps the values alive)
-            if (m == 12345.678f) {
-#endif
             clhip_buf_store(m, r_o, cok ? ovoff * 4 : CLHIP_OOB, (obase + c0 * chw) * 4);
             clhip_buf_store_u8((uint8_t)am, r_i, cok ? ovoff : CLHIP_OOB, obase + c0 * chw);
-#if C3W64_ABL & 1
-            }
-#endif
         }
         if (last_of_tile) buf ^= 1;
     }
@@ -1175,8 +1119,8 @@ __global__ __launch_bounds__(512) void conv3x3_c3w64_relu_pool_kernel(
     float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N, int Cout, int H, int W,
     int tiles_w, int row_pairs, int ntiles) {
     __shared__ __attribute__((aligned(16))) float halo_s[8 * 2 * W6_HALO];
-    __shared__ float aux_s[W6_AUX];
-    c3w64_relu_pool_body<FULL>(halo_s, aux_s, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, x, wt, bias, out, pool_idx, N, Cout, H, W,
+    __shared__ float bias_s[KT];
+    c3w64_relu_pool_body<FULL>(halo_s, bias_s, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, x, wt, bias, out, pool_idx, N, Cout, H, W,
                                tiles_w, row_pairs, ntiles);
 }
 
@@ -1202,7 +1146,7 @@ __global__ __launch_bounds__(512) void c3w64_relu_pool_wt_kernel(
     float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N, int Cout, int H, int W,
     int tiles_w, int row_pairs, int ntiles, int gx, int nfl, int nwb, int wt_first, WtJobs J) {
     __shared__ __attribute__((aligned(16))) float halo_s[8 * 2 * W6_HALO];
-    __shared__ float aux_s[W6_AUX];
+    __shared__ float bias_s[KT];
     const int b = (int)blockIdx.x;
     const int fb = wt_first ? b - nwb : b;              // first-layer block, or out of [0, nfl): a weight block
     if ((unsigned)fb >= (unsigned)nfl) {
@@ -1210,7 +1154,7 @@ __global__ __launch_bounds__(512) void c3w64_relu_pool_wt_kernel(
         if (vb < J.first[J.n]) weight_image_block(J, vb, (int)threadIdx.x & 255);
         return;
     }
-    c3w64_relu_pool_body<FULL>(halo_s, aux_s, fb % gx, fb / gx, gx, x, wt, bias, out, pool_idx, N, Cout, H, W, tiles_w, row_pairs, ntiles);
+    c3w64_relu_pool_body<FULL>(halo_s, bias_s, fb % gx, fb / gx, gx, x, wt, bias, out, pool_idx, N, Cout, H, W, tiles_w, row_pairs, ntiles);
 }
 
 // grid of the first-layer launch: one 8-wave block per CU along the units x channel tiles
@@ -1270,7 +1214,7 @@ int launch_c3_pool(const float* x, const float* wt, const float* bias, float* ou
 
 // shapes of conv3x3_c3w64_relu_pool_kernel (32-bit byte offsets into x and the pooled output)
 bool c3w64_shape(int N, int C, int K, int H, int W) {
-    return CLHIP_C3W64 && C == 3 && W % 64 == 0 && H % 2 == 0 && (size_t)N * 3 * H * W < ((size_t)1 << 29) &&
+    return C == 3 && W % 64 == 0 && H % 2 == 0 && (size_t)N * 3 * H * W < ((size_t)1 << 29) &&
            (size_t)N * K * (H / 2) * (W / 2) < ((size_t)1 << 29);
 }
 

@@ -8,43 +8,30 @@
 
 namespace {
 
-#ifndef CLHIP_W16G_ADIRECT
-#define CLHIP_W16G_ADIRECT 1 // 1: wino_conv16g_kernel loads its A operands (transformed weights) from L2 straight into registers, from a
-#endif                       // second, lane-ordered image of U behind the LDS image; LDS then holds the halo planes only (see there).
-                             // 0: through LDS (the A/B reference; profiles/r04_w16g_adirect.txt: conv time of a pass -1.4 / -2.4 / -3.6 %
-                             // on small / base / wide_VGG9, the instances that un-pool while staging -7 .. -13 %)
-
 constexpr int WKT = 64;      // out channels per block
 constexpr int WCK = 8;       // in channels per chunk
 constexpr int WFP = 20;      // floats per (channel, out-channel) in the U tile: 16 frequencies + 4 pad — an 80-byte stride makes
                              // the 16-byte reads of 16 consecutive lanes land on 64 distinct LDS banks
 constexpr int W_FLOATS = WCK * WKT * WFP;         // 10240 floats = 40 KB: U tile of one chunk [c][k][f]
-// The lane-ordered image (CLHIP_W16G_ADIRECT): per (k-tile, 4-channel chunk) 16 pieces of 1 KB,
+// The lane-ordered image, behind the LDS images of the whole layer (wino_conv16g_kernel and wino_conv16_kernel load their A operands
+// from it straight into registers): per (k-tile, 4-channel chunk) 16 pieces of 1 KB,
 //   [out-channel half wk][row tile r][frequency quad fq][lane = 16 * (channel of the quad) + (out channel & 15)][4 frequencies]
 // = what ONE buffer_load_dwordx4 of a wave of wino_conv16g_kernel wants as its A operands of 4 MFMAs: contiguous, whole lines.
 constexpr int WD_FLOATS = 4 * WKT * 16;           // 4096 floats = 16 KB per (k-tile, 4-channel chunk)
-#if CLHIP_W16G_ADIRECT
 constexpr int WU_FLOATS = W_FLOATS + 2 * WD_FLOATS;   // both images of an 8-channel chunk
-#else
-constexpr int WU_FLOATS = W_FLOATS;
-#endif
 
-// the four float4 of one (channel, out-channel) pair -> the LDS image (and the lane-ordered image behind it)
+// the four float4 of one (channel, out-channel) pair -> the LDS image and the lane-ordered image behind it
 __device__ __forceinline__ void wino_u_store(float* __restrict__ U, int kts, int n_chunks, int kt, int chunk, int c_l, int k_l,
                                              const float4 (&u)[4]) {
     float4* dst = reinterpret_cast<float4*>(U + (((size_t)(kt * n_chunks + chunk) * WCK + c_l) * WKT + k_l) * WFP);
 #pragma unroll
     for (int a = 0; a < 4; ++a) dst[a] = u[a];
     dst[4] = make_float4(0.f, 0.f, 0.f, 0.f);
-#if CLHIP_W16G_ADIRECT
     float* Ud = U + (size_t)kts * n_chunks * W_FLOATS;
     const int chunk4 = 2 * chunk + (c_l >> 2), q = c_l & 3, wk = k_l >> 5, r = (k_l >> 4) & 1, ti = k_l & 15;
     float4* dd = reinterpret_cast<float4*>(Ud + ((((size_t)(kt * 2 * n_chunks + chunk4) * 2 + wk) * 2 + r) * 4) * 256 + (q * 16 + ti) * 4);
 #pragma unroll
     for (int a = 0; a < 4; ++a) dd[a * 64] = u[a];
-#else
-    (void)kts;
-#endif
 }
 
 // Several (layer, mode) pairs in ONE launch: the plan executor transforms the weights of every Winograd layer of a pass at its start

@@ -19,12 +19,12 @@
 // rounding only (measured ~1e-6 of the output scale; north_star: 1e-3).
 //
 // Block = 4 waves = (2 halves of 64 out-channels) x (2 groups of 32 tiles); a wave holds 16 x 16 = 256 accumulator
-// registers (one wave per SIMD, like the weight-gradient kernel).  Tiles of a block: TCB x TRB tiles of NIMG images.
+// registers (one wave per SIMD, like the weight-gradient kernel).  Tiles of a block: 4 x 4 tiles of 4 images.
 //
 // Kernels of this file, in the order they were built (all share the U layout and the weight-transform launch):
 //   wino_weight_kernel / wino_weight_multi_kernel   U = G g G^T (one layer / every Winograd layer of a pass in one launch)
-//   wino_conv_kernel        forward / backward-data, 32-tile waves on 32x32x2 MFMAs, slot-pinned pipeline — the A/B reference
-//                           kept for the shapes the 16-tile kernel below does not take (odd maps wider than 8 tiles, maps narrower than 16 other than 8 x 8)
+//   wino_conv_kernel        forward / backward-data, 32-tile waves on 32x32x2 MFMAs, slot-pinned pipeline —
+//                           kept for the shapes the 16-tile kernel below does not take (even maps narrower than 16 other than 8 x 8)
 //   wino_wgrad_kernel       weight gradient, 64 x 64 (k, c) tiles, 256 accumulators, slot-pinned — layers with >= 8 stages per block
 //   wino_conv16_kernel      forward / backward-data of 8 x 8 maps with few units: one image per wave on 16x16x4 MFMAs
 //   wino_conv16g_kernel     forward / backward-data, 16-tile waves on 16x16x4 MFMAs, two blocks per CU — the DEFAULT path
@@ -36,38 +36,11 @@
 
 namespace {
 
-#ifndef CLHIP_W16G_ABL
-#define CLHIP_W16G_ABL 0     // TIMING-ONLY ablations of wino_conv16g_kernel's loop (wrong results; tools/gpu_r04_k.sh): bit 0 no input
-#endif                       // transform, 1 A operand read once, 2 no barrier, 3 no LDS stores, 4 no global loads, 5 no MFMAs
-#ifndef CLHIP_W16G_PRIO
-#define CLHIP_W16G_PRIO 2    // MFMA burst of a chunk fenced off and run at raised wave priority, see compute() in wino_conv16g_kernel
-#endif                       // (0: off — the A/B reference; 1: priority ramps up through the burst; 3: raised during staging instead)
-#ifndef CLHIP_W16_ADIRECT
-#define CLHIP_W16_ADIRECT 1  // wino_conv16_kernel (8 x 8 maps with few units): its A operands from the lane-ordered image too, except the
-#endif                       // instance that would spill (un-pooling, 32-channel waves).  0: through LDS (the A/B reference;
-                             // profiles/r04_w16_adirect.txt: 21.1 -> 19.8, 24.9 -> 20.9, 32.6 -> 30.4 us on small_VGG9's 8 x 8 launches)
-#ifndef CLHIP_W16G_PRIO_UNPOOL
-#define CLHIP_W16G_PRIO_UNPOOL 0   // the same switch for the instances that rebuild the un-pooled gradient while staging (measured slower with 2)
-#endif
-#ifndef CLHIP_WGPS_FENCE
-#ifndef CLHIP_WGPS_PITCH
-#define CLHIP_WGPS_PITCH 0   // wino_wgrad_ps_kernel: 1 = LDS row pitches of 4 mod 64 floats (no bank conflict on the operand reads).  Measured
-#endif                       // in round 6 (profiles/r06_j_wgps_pitch_ab.txt): 99.8 / 37.5 / 39.2 us against 97.7 / 36.7 / 38.7 with the old pitches —
-                             // the conflicts (0.38 of the LDS cycles) are not what the kernel waits for; not adopted.
-#define CLHIP_WGPS_FENCE 1   // wino_wgrad_ps_kernel: MFMAs of a step fenced off behind both dy transforms (0: the A/B reference)
-#endif
-#ifndef CLHIP_W16G_BURST
-#define CLHIP_W16G_BURST 0   // 1: no VALU between the MFMAs of a chunk (A/B experiment, see compute() in wino_conv16g_kernel)
-#endif
-#ifndef CLHIP_W16G_PF
-#define CLHIP_W16G_PF 2      // staging pipeline of wino_conv16g_kernel, see there
-#endif
-// (CLHIP_W16G_ADIRECT, the U layout constants, wino_u_store and the job table of the weight images: weight_images.hpp)
+// (the U layout constants, wino_u_store and the job table of the weight images: weight_images.hpp)
 
-
-template <int TCB, int TRB, int NIMG>
+// geometry of a block of wino_conv_kernel: 64 tiles = TCB x TRB tiles of NIMG images
 struct WGeoW {
-    static_assert(TCB * TRB * NIMG == 64, "64 tiles per block");
+    static constexpr int TCB = 4, TRB = 4, NIMG = 4;
     static constexpr int PW = 2 * TCB + 2;                 // halo plane row length (even)
     static constexpr int PR = 2 * TRB + 2;                 // halo plane rows per image
     static constexpr int PLANE = NIMG * PR * PW;           // floats per channel
@@ -119,16 +92,15 @@ __global__ __launch_bounds__(256) void wino_weight_multi_kernel(WtJobs J) {
 // MODE 0: forward   — out = [relu](conv(in, w) + bias), optionally 2x2-max-pooled with arg-max codes (pool_idx != NULL)
 // MODE 1: backward-data — in = dy (Cin = the layer's out channels), out = dx (* (mask_src > 0) when mask_src != NULL);
 //         UNPOOL: `in` is the gradient w.r.t. the POOLED output + the forward's arg-max codes (fused max_pool2d backward)
-//         ROWPACK (TRB = 1): the block's NIMG "images" are NIMG consecutive TILE ROWS of the (image, tile row) list — odd maps
-//         (AlexNet's 13 x 13: 7 x 7 tiles) fill 49 of 56 tile slots instead of 49 of 64; odd H / W: the last tile row / column
-//         is half outside (its inputs read 0, its outputs are not stored; 4-byte stores, rows of odd length are not 8-byte aligned)
-template <int TCB, int TRB, int NIMG, int MODE, bool UNPOOL, bool ROWPACK = false>
+// (odd H / W, the last tile row / column half outside: its inputs read 0, its outputs are not stored; 4-byte stores, rows of odd
+// length are not 8-byte aligned.  launch_wino sends every odd map to the 16-tile kernel's row-packed geometry below.)
+template <int MODE, bool UNPOOL>
 __global__ __launch_bounds__(256, 1) void wino_conv_kernel(
     const float* __restrict__ in, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ mask_src, float* __restrict__ out, uint8_t* __restrict__ pool_idx,
     int N, int Cin, int Cout, int H, int W, int relu, int tiles_w, int tiles_h, int n_pix_blocks) {
-    using G = WGeoW<TCB, TRB, NIMG>;
-    static_assert(!ROWPACK || (TRB == 1 && !UNPOOL), "row packing: one tile row per entity, no fused un-pooling");
+    using G = WGeoW;
+    constexpr int TCB = G::TCB, TRB = G::TRB, NIMG = G::NIMG;
     __shared__ __attribute__((aligned(16))) float lds[2 * G::BUF];
     __shared__ float bias_s[WKT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -137,9 +109,7 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(
 
     const int kt = blockIdx.x / n_pix_blocks, pb = blockIdx.x - kt * n_pix_blocks;
     const int bw = pb % tiles_w, bh = (pb / tiles_w) % tiles_h, ng = pb / (tiles_w * tiles_h);
-    // ROWPACK: tiles_h = tile rows per image, entity v = v0 + nb = (image v / tiles_h, tile row v % tiles_h); offsets relative to image n0
-    const int v0 = ROWPACK ? pb * NIMG : 0;
-    const int n0 = ROWPACK ? v0 / tiles_h : ng * NIMG, h0 = ROWPACK ? 0 : bh * 2 * TRB, w0 = ROWPACK ? 0 : bw * 2 * TCB;
+    const int n0 = ng * NIMG, h0 = bh * 2 * TRB, w0 = bw * 2 * TCB;
     const int ko0 = kt * WKT;
     const int n_chunks = (Cin + WCK - 1) / WCK;
     if (MODE == 0 && tid < WKT) bias_s[tid] = (bias && ko0 + tid < Cout) ? bias[ko0 + tid] : 0.f;
@@ -171,9 +141,7 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(
             const int cl = e / G::PLANE, rem = e - cl * G::PLANE;
             const int col = rem % G::PW, rr = rem / G::PW;
             const int row = rr % G::PR, nb = rr / G::PR;
-            int n = n0 + nb, h = h0 - 1 + row;
-            const int w = w0 - 1 + col;
-            if constexpr (ROWPACK) { const int v = v0 + nb; n = v / tiles_h; h = 2 * (v - n * tiles_h) - 1 + row; }
+            const int n = n0 + nb, h = h0 - 1 + row, w = w0 - 1 + col;
             const int nr = n - n0;                                       // image relative to the block's base pointer
             if (n < N && h >= 0 && h < H && w >= 0 && w < W) {
                 if constexpr (UNPOOL) {
@@ -318,9 +286,7 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(
     // register r of lane l = (out channel kb + rch(r), tile l) in every frequency accumulator
     const int kb = ko0 + wk * 32 + 4 * kk;
     auto rch = [](int r) { return (r & 3) + 8 * (r >> 2); };
-    int n = n0 + t_img, oh = h0 + 2 * t_row;
-    const int ow = w0 + 2 * t_col;
-    if constexpr (ROWPACK) { const int v = v0 + t_img; n = v / tiles_h; oh = 2 * (v - n * tiles_h); }
+    const int n = n0 + t_img, oh = h0 + 2 * t_row, ow = w0 + 2 * t_col;
     const bool tile_ok = n < N && oh < H && ow < W;                 // H, W even: a tile is inside or outside as a whole
     const bool odd = (H | W) & 1;                                   // uniform; the last tile row / column may be half outside
     const bool row1 = oh + 1 < H, col1 = ow + 1 < W;
@@ -402,29 +368,29 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(
 // of the SAME format, so the fixed-order slab reduction (wgrad_reduce_multi) serves both.
 // Signs: A dY A^T has rows / columns 3 negated (A = [[1,0],[1,1],[1,-1],[0,-1]]); the kernel accumulates with the un-negated
 // values and flips M_f for f in row 3 xor column 3 inside the output transform.
-template <int TCS, int TRS, int NIS>
+template <int TCS, int TRS>
 struct WGeoG {
-    static constexpr int TILES = TCS * TRS * NIS;          // 16 tiles per stage
+    static constexpr int TILES = TCS * TRS;                // 16 tiles of one image per stage
     static_assert(TILES == 16, "16 tiles per stage");
-    static constexpr int DW = 2 * TCS, DR = 2 * TRS;       // dy tile of one image: DR rows x DW cols
-    static constexpr int DPIX = NIS * DR * DW;             // 64 pixels
+    static constexpr int DW = 2 * TCS, DR = 2 * TRS;       // dy tile of the stage: DR rows x DW cols
+    static constexpr int DPIX = DR * DW;                   // 64 pixels
     static constexpr int LDP = DPIX + 2;                   // dy row stride per out-channel (8-byte units odd => conflict-free b64)
     static constexpr int PW = DW + 2, PR = DR + 2;
-    static constexpr int PLANE = NIS * PR * PW;
+    static constexpr int PLANE = PR * PW;
     static constexpr int PLANEP = (PLANE % 4 == 2) ? PLANE : PLANE + 2;      // even, PLANEP / 2 odd
     static_assert((LDP / 2) % 2 == 1 && (PLANEP / 2) % 2 == 1, "lane strides must be odd in 8-byte units");
     static constexpr int DY_FLOATS = WKT * LDP, X_FLOATS = WKT * PLANEP;
     static constexpr int BUF = DY_FLOATS + X_FLOATS;
 };
 
-// VEC (one image per stage, maps of whole tiles in width, 16-byte-aligned tensors): the staging units are 16-byte pieces as in
+// VEC (maps of whole tiles in width, 16-byte-aligned tensors): the staging units are 16-byte pieces as in
 // wino_wgrad_ps_kernel below — interior float4s of the halo-plane rows + the two halo columns, dy rows as float4s: 15 - 16 units per
 // stage where the scalar form has 48 (27 - 28 against 48 when dy is the pooled gradient, which stays one element + code per unit).
-template <int TCS, int TRS, int NIS, bool UNPOOL, bool VEC>
+template <int TCS, int TRS, bool UNPOOL, bool VEC>
 __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part, const uint8_t* __restrict__ unpool_idx,
     int N, int C, int K, int H, int W, int tiles_w, int tiles_h, int total_stages, int splits, int c_tiles, size_t slab_stride) {
-    using G = WGeoG<TCS, TRS, NIS>;
+    using G = WGeoG<TCS, TRS>;
     __shared__ __attribute__((aligned(16))) float lds[2 * G::BUF];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wk = wave & 1, wc = wave >> 1;
@@ -446,7 +412,6 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(
     constexpr int CPT = 256 / G::PLANE;                               // channels staged per pass
     static_assert(CPT >= 1 && WKT % CPT == 0, "whole passes over the 64 in-channels");
     constexpr int X_IT = WKT / CPT;
-    static_assert(!VEC || NIS == 1, "16-byte staging: one image per stage");
     constexpr int RSEG = G::DW / 4;
     constexpr int XU = G::PR * RSEG, XCPT = 256 / XU, XV_IT = (WKT + XCPT - 1) / XCPT;              // 24, 10, 7  |  20, 12, 6
     constexpr int HU = G::PR * 2, HCPT = 256 / HU, XH_IT = (WKT + HCPT - 1) / HCPT;                 // 12, 21, 4  |  20, 12, 6
@@ -471,6 +436,9 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(
     const int dv_dst0 = dv_kl * G::LDP + dv_r * G::DW + 4 * dv_seg;                 // even: 8-byte aligned
     bool xv_ok = false, xh_ok = false, dv_ok = false;
     unsigned dyi[UNPOOL ? DY_IT : 1];
+    // (d_nb and x_nb below, the image of a pixel inside a stage of several images, are 0 for every thread now that a stage is one
+    // image.  The kernel sits at its register limit — it spills — and hipcc allocates its registers differently when the two are
+    // written out of the index arithmetic, so they stay until a change that re-times this kernel.)
     const int dq = tid & 63, dkl = tid >> 6;
     const int d_nb = dq / (G::DR * G::DW), d_r = (dq / G::DW) % G::DR, d_c = dq % G::DW;
     const int dy_e0 = UNPOOL ? ((d_nb * K + dkl) * plane_dy + (d_r >> 1) * Wd + (d_c >> 1)) : ((d_nb * K + dkl) * plane_dy + d_r * W + d_c);
@@ -481,15 +449,15 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(
     const int x_col = x_rem % G::PW, x_rr = x_rem / G::PW, x_row = x_rr % G::PR, x_nb = x_rr / G::PR;
     const int x_e0 = (x_nb * C + x_cl) * plane_hw + x_row * W + x_col;     // relative to the (image, halo origin) base
     const int x_dst0 = G::DY_FLOATS + x_cl * G::PLANEP + x_rem;
-    // stage -> (image group, tile-row block, tile-col block)
+    // stage -> (image, tile-row block, tile-col block)
     int ld_n0 = 0, ld_h0 = 0, ld_w0 = 0;
     bool dy_ok = false, x_ok = false;
     __amdgpu_buffer_rsrc_t rs_dy = clhip_rsrc(dy, 0), rs_x = clhip_rsrc(x, 0), rs_di = clhip_rsrc(x, 0);
     auto begin_stage = [&](int st) {
         const bool live = st < st_end;
         const int s = live ? st : st_begin;
-        const int bw = s % tiles_w, bh = (s / tiles_w) % tiles_h, ng = s / (tiles_w * tiles_h);
-        ld_n0 = ng * NIS; ld_h0 = bh * G::DR; ld_w0 = bw * G::DW;
+        const int bw = s % tiles_w, bh = (s / tiles_w) % tiles_h;
+        ld_n0 = s / (tiles_w * tiles_h); ld_h0 = bh * G::DR; ld_w0 = bw * G::DW;
         const int org_dy = UNPOOL ? (ld_h0 >> 1) * Wd + (ld_w0 >> 1) : ld_h0 * W + ld_w0;
         const float* dyb = dy + ((size_t)ld_n0 * K + k0) * plane_dy + org_dy;
         const long long dy_left = ((long long)(N - ld_n0) * K - k0) * plane_dy - org_dy;
@@ -585,9 +553,9 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(
     const int b_lane = G::DY_FLOATS + (wc * 32 + li) * G::PLANEP;
     auto tile_off = [&](int step, int& doff, int& xo) {
         const int t = 2 * step + kk;
-        const int ti = t / (TRS * TCS), tr = (t / TCS) % TRS, tc = t % TCS;
-        doff = (ti * G::DR + 2 * tr) * G::DW + 2 * tc;
-        xo = (ti * G::PR + 2 * tr) * G::PW + 2 * tc;
+        const int tr = t / TCS, tc = t % TCS;
+        doff = 2 * tr * G::DW + 2 * tc;
+        xo = 2 * tr * G::PW + 2 * tc;
     };
     int doffs[NSTEP], xoffs[NSTEP];
 #pragma unroll
@@ -728,9 +696,16 @@ typedef float floatx4v __attribute__((ext_vector_type(4)));
 //       1 -> block = 1 image x 64 out-channels (wave = channel quarter): twice the waves for layers with few out-channels
 // (LDS floats of a block: the two chunk buffers + the 64 bias values; body = device function over (LDS base, block index), as
 // wino_conv16g_body below: the kernel of its own and one half of wino_pair_kernel are the same code)
+// A operands straight from the lane-ordered image of U into registers (as wino_conv16g_kernel; LDS = halo planes, two blocks per CU
+// by registers, which keeps the operands out of the AGPR shuffle a 512-register budget invites), except the un-pooling instance with
+// 32-channel waves: it needs 256 + registers that way and reads them from the LDS image (measured 36.2 vs 37.4 us).  Through LDS for
+// all instances: profiles/r04_w16_adirect.txt, 19.8 -> 21.1, 20.9 -> 24.9, 30.4 -> 32.6 us on small_VGG9's 8 x 8 launches.
+template <bool UNPOOL, int KT2>
+constexpr bool wino16_adirect = !(UNPOOL && KT2 == 2);
+
 template <bool UNPOOL, int KT2>
 __host__ __device__ constexpr int wino16_lds_floats() {
-    return 2 * ((CLHIP_W16_ADIRECT != 0 && !(UNPOOL && KT2 == 2) ? 0 : W_FLOATS) + WCK * KT2 * 100) + WKT;
+    return 2 * ((wino16_adirect<UNPOOL, KT2> ? 0 : W_FLOATS) + WCK * KT2 * 100) + WKT;
 }
 
 template <int MODE, bool UNPOOL, int KT2>
@@ -741,11 +716,7 @@ __device__ __forceinline__ void wino_conv16_body(
     int N, int Cin, int Cout, int relu) {
     constexpr int H = 8, W = 8, NIMG = KT2;
     constexpr int PW = 10, PR = 10, PLANE = NIMG * PR * PW;           // halo planes of the block's two images, per channel
-    // CLHIP_W16_ADIRECT: A operands from the lane-ordered image of U straight into registers (as wino_conv16g_kernel); LDS = halo planes
-    // (two blocks per CU by registers then, which keeps the operands out of the AGPR shuffle a 512-register budget invites; the
-    // un-pooling instance with 32-channel waves needs 256 + registers that way and stays on the LDS path: measured 36.2 vs 37.4 us)
-    constexpr bool ADIRECT = CLHIP_W16_ADIRECT != 0 && !(UNPOOL && KT2 == 2);
-    static_assert(!ADIRECT || CLHIP_W16G_ADIRECT != 0, "the lane-ordered image of U is written only with CLHIP_W16G_ADIRECT");
+    constexpr bool ADIRECT = wino16_adirect<UNPOOL, KT2>;
     constexpr int WOFF = ADIRECT ? 0 : W_FLOATS;
     constexpr int X_FLOATS = WCK * PLANE, BUF = WOFF + X_FLOATS;
     static_assert(wino16_lds_floats<UNPOOL, KT2>() == 2 * BUF + WKT, "LDS size of the wrappers");
@@ -981,7 +952,7 @@ __device__ __forceinline__ void wino_conv16_body(
 }
 
 template <int MODE, bool UNPOOL, int KT2>
-__global__ __launch_bounds__(256, (CLHIP_W16_ADIRECT && !(UNPOOL && KT2 == 2)) ? 2 : 1) void wino_conv16_kernel(
+__global__ __launch_bounds__(256, (wino16_adirect<UNPOOL, KT2> ? 2 : 1)) void wino_conv16_kernel(
     const float* __restrict__ in, const float* __restrict__ U, const float* __restrict__ bias,
     const float* __restrict__ mask_src, float* __restrict__ out, uint8_t* __restrict__ pool_idx,
     int N, int Cin, int Cout, int relu) {
@@ -995,9 +966,12 @@ __global__ __launch_bounds__(256, (CLHIP_W16_ADIRECT && !(UNPOOL && KT2 == 2)) ?
 // global loads), its barriers and its epilogue (output transform, bias / ReLU / pool, stores): on a 64-channel layer (8 chunks)
 // those are about a third of a unit's time.  This kernel has the 16x16x4-MFMA wave of wino_conv16_kernel on ANY even map: a wave
 // is TC x TR = 16 tiles x 32 out-channels (128 accumulators), a block 64 out-channels x (TC x 2 TR) tiles of one image, LDS
-// holds 4-channel chunks (23 KB, double-buffered) and the kernel stays under 256 registers — two blocks share a CU, each
+// holds 4-channel chunks (double-buffered) and the kernel stays under 256 registers — two blocks share a CU, each
 // SIMD has two waves, one issues MFMAs while the other waits, transforms or stores.  No hand-placed slots: the work of a
 // chunk is read operands -> transform -> 32 MFMAs, the compiler orders it, the second wave fills the gaps.
+// The A operands (transformed weights) come from L2 straight into registers, from the second, lane-ordered image of U behind the LDS
+// image (weight_images.hpp); LDS holds the halo planes only.  (Through LDS, round 4, profiles/r04_w16g_adirect.txt: conv time of a
+// pass +1.4 / +2.4 / +3.6 % on small / base / wide_VGG9, the instances that un-pool while staging +7 .. +13 %.)
 // Geometry: the block's TC x 2 TR tiles are 2 TR / EROWS ENTITIES of EROWS tile rows each, every entity with its own halo band
 // of 2 EROWS + 2 rows; entities are numbered over (image, row group of the image):
 //   EROWS = 2 TR      one entity = a (TC x 2 TR)-tile region of one image                     (even maps >= 16 wide: <8, 2, 4>)
@@ -1009,7 +983,7 @@ __global__ __launch_bounds__(256, (CLHIP_W16_ADIRECT && !(UNPOOL && KT2 == 2)) ?
 // below): the __global__ wrappers own the LDS array.
 template <int TC, int TR, int EROWS>
 __host__ __device__ constexpr int wino16g_lds_floats() {
-    return 2 * ((CLHIP_W16G_ADIRECT != 0 ? 0 : 4 * WKT * WFP) + 4 * (2 * TR / EROWS) * (2 * EROWS + 2) * (2 * TC + 2)) + WKT;
+    return 2 * 4 * (2 * TR / EROWS) * (2 * EROWS + 2) * (2 * TC + 2) + WKT;
 }
 
 template <int TC, int TR, int EROWS, int MODE, bool UNPOOL>
@@ -1023,10 +997,7 @@ __device__ __forceinline__ void wino_conv16g_body(
     constexpr int NE = 2 * TR / EROWS;                                // entities per block
     static_assert(NE * EROWS == 2 * TR && (NE == 1 || !UNPOOL || EROWS == 4), "whole entities");
     constexpr int PW = 2 * TC + 2, PRE = 2 * EROWS + 2, PLANE = NE * PRE * PW;
-    constexpr int WQ_FLOATS = CQ * WKT * WFP;                         // 5120 floats: half of a U chunk (channels are its outer index)
-    constexpr bool ADIRECT = CLHIP_W16G_ADIRECT != 0;                 // A operands from L2 straight into registers: LDS holds the halo planes only
-    constexpr int WOFF = ADIRECT ? 0 : WQ_FLOATS;
-    constexpr int X_FLOATS = CQ * PLANE, BUF = WOFF + X_FLOATS;
+    constexpr int X_FLOATS = CQ * PLANE, BUF = X_FLOATS;             // a chunk buffer = the halo planes of 4 channels
     static_assert(wino16g_lds_floats<TC, TR, EROWS>() == 2 * BUF + WKT, "LDS size of the wrappers");
     float* const bias_s = lds + 2 * BUF;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1046,16 +1017,14 @@ __device__ __forceinline__ void wino_conv16g_body(
     const __amdgpu_buffer_rsrc_t rs_x = clhip_rsrc(in_img, (size_t)(N - nb0) * Cin * plane_in * sizeof(float));
     const __amdgpu_buffer_rsrc_t rs_i = clhip_rsrc(UNPOOL ? pool_idx + (size_t)nb0 * Cin * plane_in : pool_idx,
                                                    UNPOOL ? (size_t)(N - nb0) * Cin * plane_in : 0);
-    // LDS image of this k-tile's chunks, or (ADIRECT) its lane-ordered image behind the LDS images of the whole layer
-    const __amdgpu_buffer_rsrc_t rs_u = ADIRECT
-        ? clhip_rsrc(U + (size_t)((Cout + WKT - 1) / WKT) * (Cin / WCK) * W_FLOATS + (size_t)kt * n_chunks * WD_FLOATS,
-                     (size_t)n_chunks * WD_FLOATS * sizeof(float))
-        : clhip_rsrc(U + (size_t)kt * n_chunks * WQ_FLOATS, (size_t)n_chunks * WQ_FLOATS * sizeof(float));
+    // this k-tile's lane-ordered image, behind the LDS images of the whole layer
+    const __amdgpu_buffer_rsrc_t rs_u =
+        clhip_rsrc(U + (size_t)((Cout + WKT - 1) / WKT) * (Cin / WCK) * W_FLOATS + (size_t)kt * n_chunks * WD_FLOATS,
+                   (size_t)n_chunks * WD_FLOATS * sizeof(float));
 
-    constexpr int W_IT = ADIRECT ? 1 : WQ_FLOATS / 4 / 256;           // 5 (ADIRECT: unused)
     constexpr int X_IT = (X_FLOATS + 255) / 256;
-    struct Stage {                                                    // one chunk on its way from global memory to LDS
-        float4 wv[W_IT];
+    struct Stage {                                                    // the halo planes of one chunk on their way from global memory to LDS
+        float4 wv[1];                                                 // unused: see `ab` in compute()
         float xr[X_IT];
         unsigned xi[UNPOOL ? X_IT : 1];
     };
@@ -1082,10 +1051,6 @@ __device__ __forceinline__ void wino_conv16g_body(
     }
     auto load_chunk = [&](int chunk, Stage& st) {
         const int cw = chunk < n_chunks ? chunk : n_chunks - 1;
-        if constexpr (!ADIRECT) {
-#pragma unroll
-            for (int u = 0; u < W_IT; ++u) st.wv[u] = clhip_buf_load4(rs_u, (tid + 256 * u) * 16, cw * WQ_FLOATS * 4);
-        }
         const int xb = cw * CQ * plane_in;
 #pragma unroll
         for (int j = 0; j < X_IT; ++j) {
@@ -1098,12 +1063,7 @@ __device__ __forceinline__ void wino_conv16g_body(
         }
     };
     auto store_chunk = [&](int bo, const Stage& st) {
-        if constexpr (!ADIRECT) {
-#pragma unroll
-            for (int u = 0; u < W_IT; ++u)
-                *reinterpret_cast<floatx4*>(lds + bo + 4 * (tid + 256 * u)) = floatx4{st.wv[u].x, st.wv[u].y, st.wv[u].z, st.wv[u].w};
-        }
-        float* xs = lds + bo + WOFF;
+        float* xs = lds + bo;
 #pragma unroll
         for (int j = 0; j < X_IT; ++j)
             if (256 * (j + 1) <= X_FLOATS || tid + 256 * j < X_FLOATS) {
@@ -1114,8 +1074,8 @@ __device__ __forceinline__ void wino_conv16g_body(
 
     const int t_rowb = wp * TR + ti / TC, t_col = ti % TC;           // this lane's tile inside the block's TC x 2 TR tiles
     const int t_ent = t_rowb / EROWS, t_row = t_rowb % EROWS;        // its entity and its row inside the entity
-    const int d_off = WOFF + q * PLANE + (t_ent * PRE + 2 * t_row) * PW + 2 * t_col;           // even: 8-byte aligned
-    const int a_off = (q * WKT + wk * 32 + ti) * WFP;
+    const int d_off = q * PLANE + (t_ent * PRE + 2 * t_row) * PW + 2 * t_col;                  // even: 8-byte aligned
+    const int a_off = (q * WKT + wk * 32 + ti) * WFP;                                          // unused: see `ab` in compute()
 
     floatx4v acc[2][16];
 #pragma unroll
@@ -1124,15 +1084,7 @@ __device__ __forceinline__ void wino_conv16g_body(
         for (int f = 0; f < 16; ++f) acc[k2][f] = floatx4v{0.f, 0.f, 0.f, 0.f};
 
     typedef float f2 __attribute__((ext_vector_type(2)));
-#if CLHIP_W16G_ABL & 2
-    floatx4 abl_a0[4], abl_a1[4];
-#pragma unroll
-    for (int fq = 0; fq < 4; ++fq) {
-        abl_a0[fq] = floatx4{0.5f + fq, 0.25f, -0.5f, 1.f} * (float)(lane + 1);
-        abl_a1[fq] = floatx4{0.75f, 0.5f + fq, 1.5f, -1.f} * (float)(lane + 2);
-    }
-#endif
-    // ADIRECT: the A operands of a chunk = 8 x 1 KB pieces of the lane-ordered image (this wave's out-channel half: 2 row tiles x 4
+    // the A operands of a chunk = 8 x 1 KB pieces of the lane-ordered image (this wave's out-channel half: 2 row tiles x 4
     // frequency quads), each ONE coalesced buffer_load_dwordx4; issued a whole chunk ahead into the register set the previous
     // burst has just released, so that L2 latency (~200-500 cycles) lies under the other set's chunk.
     struct AReg { floatx4 a0[4], a1[4]; };
@@ -1147,29 +1099,19 @@ __device__ __forceinline__ void wino_conv16g_body(
             A.a1[fq] = floatx4{__uint_as_float(v1.x), __uint_as_float(v1.y), __uint_as_float(v1.z), __uint_as_float(v1.w)};
         }
     };
-    // one chunk from LDS buffer `bo`: operands, input transform, 32 MFMAs
-    auto compute = [&](int bo, const AReg* areg) {
-        const float* ab = lds + bo + a_off;
+    // one chunk: window from LDS buffer `bo`, A operands from `A`, input transform, 32 MFMAs
+    auto compute = [&](int bo, const AReg& A) {
+        // LEFTOVER of the removed path that read the A operands from an LDS image: `ab`, a_off and Stage::wv are read by nothing.  Without
+        // them hipcc 7.2 emits the same instructions for the 8 instances of this body and the 4 of wino_pair_kernel that hold it, but
+        // swaps the operands of a few integer adds and the names of two registers, so the assembly is no longer the text that was
+        // measured.  They go with the next change that re-times these kernels anyway.
+        const float* ab = lds + bo + a_off; (void)ab;
         const float* db = lds + bo + d_off;
         f2 dlo[4], dhi[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             dlo[r] = *reinterpret_cast<const f2*>(db + r * PW);
             dhi[r] = *reinterpret_cast<const f2*>(db + r * PW + 2);
-        }
-        floatx4 a0[4], a1[4];
-#pragma unroll
-        for (int fq = 0; fq < 4; ++fq) {
-#if CLHIP_W16G_ABL & 2
-            a0[fq] = abl_a0[fq]; a1[fq] = abl_a1[fq];
-#else
-            if constexpr (ADIRECT) {
-                a0[fq] = areg->a0[fq]; a1[fq] = areg->a1[fq];
-            } else {
-                a0[fq] = *reinterpret_cast<const floatx4*>(ab + 4 * fq);
-                a1[fq] = *reinterpret_cast<const floatx4*>(ab + 16 * WFP + 4 * fq);
-            }
-#endif
         }
         // V = B^T d B
         f2 tlo[4], thi[4];
@@ -1178,11 +1120,6 @@ __device__ __forceinline__ void wino_conv16g_body(
         tlo[2] = dlo[2] - dlo[1]; thi[2] = dhi[2] - dhi[1];
         tlo[3] = dlo[1] - dlo[3]; thi[3] = dhi[1] - dhi[3];
         float vv[16];
-#if CLHIP_W16G_ABL & 1
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { vv[4 * i] = dlo[i].x; vv[4 * i + 1] = dlo[i].y; vv[4 * i + 2] = dhi[i].x; vv[4 * i + 3] = dhi[i].y; }
-        (void)tlo; (void)thi;
-#else
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const f2 o = tlo[i] - thi[i];
@@ -1191,123 +1128,59 @@ __device__ __forceinline__ void wino_conv16g_body(
             vv[4 * i + 1] = tlo[i].y + thi[i].x;
             vv[4 * i + 2] = thi[i].x - tlo[i].y;
         }
-#endif
-#if CLHIP_W16G_BURST
-        __builtin_amdgcn_sched_barrier(0);      // A/B: all 16 transformed values in their own registers first, then 32 MFMAs back to back
-#endif
-        // Round 4, measured per instance (profiles/r04_w16g_priority_variants.txt): fencing the 32 MFMAs of a chunk off from the
-        // operand reads / transform in front of them and running them at raised wave priority is 4 - 13 % FASTER on every instance
-        // that stages plain activations (forward, backward-data without a fused un-pool: wide_VGG9 359 -> 311, 188 -> 166 us) and
-        // 4 - 5 % SLOWER on the instances that rebuild the un-pooled gradient while staging (more VALU in front of the burst) —
-        // so it is on for the former only.  The three priority patterns tried (ramp, high in the burst, high while staging) time
-        // alike: what matters is the fence, the s_setprio pair costs nothing.
-        constexpr int PRIO = UNPOOL ? CLHIP_W16G_PRIO_UNPOOL : CLHIP_W16G_PRIO;
-        if constexpr (PRIO == 2) {
+        // The 32 MFMAs of a chunk are fenced off from the operand reads / transform in front of them and run at raised wave priority:
+        // 4 - 13 % FASTER on every instance that stages plain activations (forward, backward-data without a fused un-pool: wide_VGG9
+        // 359 -> 311, 188 -> 166 us) and 4 - 5 % SLOWER on the instances that rebuild the un-pooled gradient while staging (more VALU in
+        // front of the burst), so those run without it (round 4, per instance: profiles/r04_w16g_priority_variants.txt; what matters is
+        // the fence, the s_setprio pair costs nothing).
+        constexpr bool FENCED = !UNPOOL;
+        if constexpr (FENCED) {
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(3);
-            __builtin_amdgcn_sched_barrier(0);
-        } else if constexpr (PRIO == 3) {
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int f = 0; f < 16; ++f) {
-            if constexpr (PRIO == 1)
-            if ((f & 3) == 0) {                   // the further a wave is into its burst, the higher its claim on the matrix pipe
-                __builtin_amdgcn_sched_barrier(0);
-                if (f == 0) __builtin_amdgcn_s_setprio(0);
-                else if (f == 4) __builtin_amdgcn_s_setprio(1);
-                else if (f == 8) __builtin_amdgcn_s_setprio(2);
-                else __builtin_amdgcn_s_setprio(3);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#if CLHIP_W16G_ABL & 32
-            acc[0][f][0] += a0[f >> 2][f & 3] * vv[f];          // (one VALU op instead of the MFMA: keeps operands alive)
-            acc[1][f][0] += a1[f >> 2][f & 3] * vv[f];
-#else
-            acc[0][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[f >> 2][f & 3], vv[f], acc[0][f], 0, 0, 0);
-            acc[1][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[f >> 2][f & 3], vv[f], acc[1][f], 0, 0, 0);
-#endif
+            acc[0][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(A.a0[f >> 2][f & 3], vv[f], acc[0][f], 0, 0, 0);
+            acc[1][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(A.a1[f >> 2][f & 3], vv[f], acc[1][f], 0, 0, 0);
         }
-#if CLHIP_W16G_BURST
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-        if constexpr (PRIO == 1 || PRIO == 2) {
+        if constexpr (FENCED) {
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
-        } else if constexpr (PRIO == 3) {
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(3);        // staging of the next chunk (LDS writes, global loads, operand reads) goes first
-            __builtin_amdgcn_sched_barrier(0);
         }
     };
-#if CLHIP_W16G_ABL & 4
-#define W16G_SYNC() __builtin_amdgcn_wave_barrier()
-#else
-#define W16G_SYNC() __syncthreads()
-#endif
-#if CLHIP_W16G_ABL & 8
-#define W16G_STORE(bo, st) ((void)0)
-#else
-#define W16G_STORE(bo, st) store_chunk(bo, st)
-#endif
-#if CLHIP_W16G_ABL & 16
-#define W16G_LOAD(c, st) ((void)0)
-#else
-#define W16G_LOAD(c, st) load_chunk(c, st)
-#endif
     // Staging pipeline.  The loads of a later chunk must be ISSUED before this chunk's MFMAs and WAITED FOR after them.
     // Left to itself the scheduler (it minimises register pressure, 180 of the 256 registers two waves per SIMD allow) sinks
     // the loads below the MFMAs — issued right before the barrier, waited for right after it: every chunk then pays the whole
     // L2 / HBM latency with nothing of its own wave in flight (the loop ran at 0.42-0.55 of the matrix pipe on every layer
-    // width, round 3).  __builtin_amdgcn_sched_barrier(0) behind the issue pins the order.
-    //   CLHIP_W16G_PF = 0  the round-3 schedule (A/B reference)
-    //                   1  one register set: chunk + 2 is issued at the top of chunk's iteration, stored at the top of the next
-    //                   2  two register sets: chunk + 3 issued at the top of chunk's iteration (two iterations in flight)
-#if CLHIP_W16G_PF == 2
+    // width, round 3).  __builtin_amdgcn_sched_barrier(0) behind the issue pins the order.  Two register sets: chunk + 3 is issued at
+    // the top of chunk's iteration, two iterations in flight (round 4, against one set: profiles/r04_w16g_prefetch_variants.txt).
     Stage sa, sb;
-    AReg ra, rb;                                                       // (ADIRECT) A operands of the even / odd chunks
+    AReg ra, rb;                                                       // A operands of the even / odd chunks
     load_chunk(0, sa);
     store_chunk(0, sa);
     load_chunk(1, sa);
     load_chunk(2, sb);
-    if constexpr (ADIRECT) { load_a(0, ra); load_a(1, rb); }
+    load_a(0, ra);
+    load_a(1, rb);
     __syncthreads();
     for (int chunk = 0; chunk < n_chunks; chunk += 2) {               // n_chunks is even (Cin is a multiple of 8)
-        W16G_STORE(BUF, sa);                                           // chunk + 1 -> buffer 1 (read last in iteration chunk - 1)
-        W16G_LOAD(chunk + 3, sa);
+        store_chunk(BUF, sa);                                          // chunk + 1 -> buffer 1 (read last in iteration chunk - 1)
+        load_chunk(chunk + 3, sa);
         __builtin_amdgcn_sched_barrier(0);
-        compute(0, &ra);
-        if constexpr (ADIRECT) { load_a(chunk + 2, ra); __builtin_amdgcn_sched_barrier(0); }     // behind the burst that read `ra`
-        W16G_SYNC();
-        W16G_STORE(0, sb);                                             // chunk + 2 -> buffer 0
-        W16G_LOAD(chunk + 4, sb);
+        compute(0, ra);
+        load_a(chunk + 2, ra);                                         // behind the burst that read `ra`
         __builtin_amdgcn_sched_barrier(0);
-        compute(BUF, &rb);
-        if constexpr (ADIRECT) { load_a(chunk + 3, rb); __builtin_amdgcn_sched_barrier(0); }
-        W16G_SYNC();
-    }
-#else
-    static_assert(!ADIRECT, "CLHIP_W16G_ADIRECT needs the two-set pipeline (CLHIP_W16G_PF = 2)");
-    Stage sa;
-    load_chunk(0, sa);
-    store_chunk(0, sa);
-    load_chunk(1, sa);
-    __syncthreads();
-    for (int chunk = 0; chunk < n_chunks; ++chunk) {
-        const int bo = (chunk & 1) * BUF;
-        // chunk + 1 (in registers since the previous iteration) -> the other buffer (its readers finished before the last barrier)
-        store_chunk(BUF - bo, sa);
-        load_chunk(chunk + 2, sa);
-#if CLHIP_W16G_PF == 1
+        __syncthreads();
+        store_chunk(0, sb);                                            // chunk + 2 -> buffer 0
+        load_chunk(chunk + 4, sb);
         __builtin_amdgcn_sched_barrier(0);
-#endif
-        compute(bo, nullptr);
+        compute(BUF, rb);
+        load_a(chunk + 3, rb);
+        __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
     }
-#endif
 
     // ---- epilogue: register r of acc[k2][f] = (out channel ko0 + 32 wk + 16 k2 + 4 q + r, this lane's tile)
     const int tv = v0 + t_ent, n = tv / tiles_h;
@@ -1396,7 +1269,6 @@ __global__ __launch_bounds__(256, 2) void wino_conv16g_kernel(
 
 // (measured against the 32-tile kernel on even maps >= 16 wide in round 3: N = 200: 64->64 @32x32 forward 126 -> 109 us,
 // backward-data 136 -> 110; 256->256 @16x16 357 -> 317 = 190 TFLOP/s algorithmic)
-static bool wino16g_on() { return true; }
 
 // units of the 32-tile kernel a layer has; below this the 8 x 8 variant takes 8 x 8 maps
 #ifndef CLHIP_WINO16_BELOW_UNITS
@@ -1423,20 +1295,13 @@ struct WGeoP {
     static constexpr int DPIX = DR * DW;                   // 64 pixels
     static constexpr int PW = DW + 2, PR = DR + 2;
     static constexpr int PLANE = PR * PW;
-#if CLHIP_WGPS_PITCH
-    // The operand reads of a step are ds_read_b64 whose 32 lanes of a group are 16 channels (lane stride = the row pitch) x 2
-    // neighbouring tiles (2 floats apart); ds_read_b64 banks are (float index) mod 64, so the group is conflict-free when the pitch
-    // is 4 mod 64 floats: slot (8 bytes) = 2 * channel + tile, all 32 distinct.  (Round 5's pitches, 66 and PLANE | 2, were odd in
-    // 8-byte units — conflict-free over the channels alone, two-way between (channel, tile + 1) and (channel + k, tile): 0.38 of
-    // the kernel's LDS cycles were bank conflicts, profiles/r05_i_pmc_summary.txt.)
-    static constexpr int LDP = (DPIX + 63 - 4) / 64 * 64 + 4;          // 68
-    static constexpr int PLANEP = (PLANE + 63 - 4) / 64 * 64 + 4;      // 132
-    static_assert(LDP >= DPIX && PLANEP >= PLANE && LDP % 64 == 4 && PLANEP % 64 == 4, "row pitches of 4 mod 64 floats");
-#else
+    // Row pitches odd in 8-byte units: the ds_read_b64 operand reads are conflict-free over the channels, two-way between (channel,
+    // tile + 1) and (channel + k, tile) — 0.38 of the kernel's LDS cycles (profiles/r05_i_pmc_summary.txt), but not what it waits for:
+    // pitches of 4 mod 64 floats (no conflicts) measured 99.8 / 37.5 / 39.2 us against 97.7 / 36.7 / 38.7 (round 6,
+    // profiles/r06_j_wgps_pitch_ab.txt) and were not adopted.
     static constexpr int LDP = DPIX + 2;
     static constexpr int PLANEP = (PLANE % 4 == 2) ? PLANE : PLANE + 2;
     static_assert((LDP / 2) % 2 == 1 && (PLANEP / 2) % 2 == 1, "lane strides must be odd in 8-byte units");
-#endif
     static constexpr int DY_FLOATS = KB * LDP, X_FLOATS = CB * PLANEP;
     static constexpr int BUF = DY_FLOATS + X_FLOATS;
     static constexpr int XCH = 4 * 65 * 64;                // exchange area: per wave 64 accumulators + 1 bias sum, 64 lanes
@@ -1659,7 +1524,6 @@ __device__ __forceinline__ void wino_wgrad_ps_body(
                 vv[4 * i + 1] = tlo[i].y + thi[i].x;
                 vv[4 * i + 2] = thi[i].x - tlo[i].y;
             }
-#if CLHIP_WGPS_FENCE
             // round 4: both transformed dy tiles first, then the 32 MFMAs of the step fenced off at raised priority (-3 % on the
             // un-pooling instances, neutral on the others: profiles/r04_w16g_priority_variants.txt)
             float av0[16], av1[16];
@@ -1675,15 +1539,6 @@ __device__ __forceinline__ void wino_wgrad_ps_body(
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
-#else
-            float av[16];
-            dy_tf(cur + a_lane + doff, av, bsum[0]);
-#pragma unroll
-            for (int f = 0; f < 16; ++f) acc[0][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[f], vv[f], acc[0][f], 0, 0, 0);
-            dy_tf(cur + a_lane + 16 * G::LDP + doff, av, bsum[1]);
-#pragma unroll
-            for (int f = 0; f < 16; ++f) acc[1][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[f], vv[f], acc[1][f], 0, 0, 0);
-#endif
         }
         __syncthreads();
     }
@@ -1756,8 +1611,6 @@ __global__ __launch_bounds__(256, 2) void wino_wgrad_ps_kernel(
                                               total_stages, splits, c_tiles, slab_stride);
 }
 
-static bool wgrad_ps_on() { return true; }       // (small layers: the pixel-split Winograd weight gradient, wino_wgrad_ps_kernel)
-
 // ------------------------------------------------------------------------------------------------ backward of a small layer as ONE grid
 // The deep layers of the VGG9s (16 x 16 and 8 x 8 maps at N = 200) give every launch of their backward pass 200 - 512 blocks: ONE
 // round of blocks on 256 CUs x 2, all of them in the same phase at the same time — every block loads its first operands together,
@@ -1816,37 +1669,31 @@ int launch_wino(const float* in, const float* U, const float* bias, const float*
         CLHIP_LAUNCH_CHECK();
         return 0;
     }
-    if (wino16g_on()) {
-        // 16-tile waves, two blocks per CU (wino_conv16g_kernel): every shape of this path except 8 x 8 maps with so few units
-        // that the one-image waves of wino_conv16_kernel (above) spread better
+    // 16-tile waves, two blocks per CU (wino_conv16g_kernel): every shape of this path except 8 x 8 maps with so few units
+    // that the one-image waves of wino_conv16_kernel (above) spread better
 #define WINO_16G(TC_, TR_, ER_, UNP_)                                                                                          \
-        do {                                                                                                                   \
-            const int tiles_w = ((W + 1) / 2 + TC_ - 1) / TC_, groups = ((H + 1) / 2 + ER_ - 1) / ER_;                          \
-            constexpr int NE_ = 2 * TR_ / ER_;                                                                                  \
-            const long long npb = (((long long)N * groups + NE_ - 1) / NE_) * tiles_w, blocks = npb * kts;                      \
-            if (blocks <= 0 || blocks > 0x7fffffffLL) return CLHIP_EINVAL;                                                      \
-            hipLaunchKernelGGL((wino_conv16g_kernel<TC_, TR_, ER_, MODE, UNP_>), dim3((unsigned)blocks), dim3(256), 0, s, in, U, \
-                               bias, mask_src, out, pool_idx, N, Cin, Cout, H, W, relu, tiles_w, groups, (int)npb);             \
-            CLHIP_LAUNCH_CHECK();                                                                                               \
-            return 0;                                                                                                           \
-        } while (0)
-        if ((H | W) & 1) { if (W <= 16) WINO_16G(8, 2, 1, false); }
-        else if (W >= 16) WINO_16G(8, 2, 4, UNPOOL);
-        else if (H == 8 && W == 8) WINO_16G(4, 4, 4, UNPOOL);
-#undef WINO_16G
-    }
-#define WINO_GEO(TCB_, TRB_, NIMG_)                                                                                          \
-    do {                                                                                                                      \
-        const int tiles_w = ((W + 1) / 2 + TCB_ - 1) / TCB_, tiles_h = ((H + 1) / 2 + TRB_ - 1) / TRB_, ngrp = (N + NIMG_ - 1) / NIMG_; \
-        const long long npb = (long long)tiles_w * tiles_h * ngrp, blocks = npb * kts;                                        \
-        if (blocks <= 0 || blocks > 0x7fffffffLL) return CLHIP_EINVAL;                                                        \
-        hipLaunchKernelGGL((wino_conv_kernel<TCB_, TRB_, NIMG_, MODE, UNPOOL>), dim3((unsigned)blocks), dim3(256), 0, s, in, U, \
-                           bias, mask_src, out, pool_idx, N, Cin, Cout, H, W, relu, tiles_w, tiles_h, (int)npb);              \
+    do {                                                                                                                       \
+        const int tiles_w = ((W + 1) / 2 + TC_ - 1) / TC_, groups = ((H + 1) / 2 + ER_ - 1) / ER_;                              \
+        constexpr int NE_ = 2 * TR_ / ER_;                                                                                      \
+        const long long npb = (((long long)N * groups + NE_ - 1) / NE_) * tiles_w, blocks = npb * kts;                          \
+        if (blocks <= 0 || blocks > 0x7fffffffLL) return CLHIP_EINVAL;                                                          \
+        hipLaunchKernelGGL((wino_conv16g_kernel<TC_, TR_, ER_, MODE, UNP_>), dim3((unsigned)blocks), dim3(256), 0, s, in, U,    \
+                           bias, mask_src, out, pool_idx, N, Cin, Cout, H, W, relu, tiles_w, groups, (int)npb);                 \
+        CLHIP_LAUNCH_CHECK();                                                                                                   \
+        return 0;                                                                                                               \
     } while (0)
-    // what is left for the 32-tile kernel: even maps narrower than 16 other than 8 x 8 (the 16-tile kernel above took every other shape
-    // of clhip_internal_wino_ok: even maps >= 16 wide, 8 x 8 maps, odd maps up to 16 wide)
-    WINO_GEO(4, 4, 4);
-#undef WINO_GEO
+    if ((H | W) & 1) { if (W <= 16) WINO_16G(8, 2, 1, false); }
+    else if (W >= 16) WINO_16G(8, 2, 4, UNPOOL);
+    else if (H == 8 && W == 8) WINO_16G(4, 4, 4, UNPOOL);
+#undef WINO_16G
+    // what still reaches the 32-tile kernel: even maps narrower than 16 other than 8 x 8 (the 16-tile kernel above took every other
+    // shape of clhip_internal_wino_ok: even maps >= 16 wide, 8 x 8 maps, odd maps up to 16 wide)
+    using G = WGeoW;
+    const int tiles_w = ((W + 1) / 2 + G::TCB - 1) / G::TCB, tiles_h = ((H + 1) / 2 + G::TRB - 1) / G::TRB, ngrp = (N + G::NIMG - 1) / G::NIMG;
+    const long long npb = (long long)tiles_w * tiles_h * ngrp, blocks = npb * kts;
+    if (blocks <= 0 || blocks > 0x7fffffffLL) return CLHIP_EINVAL;
+    hipLaunchKernelGGL((wino_conv_kernel<MODE, UNPOOL>), dim3((unsigned)blocks), dim3(256), 0, s, in, U, bias, mask_src, out, pool_idx,
+                       N, Cin, Cout, H, W, relu, tiles_w, tiles_h, (int)npb);
     CLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -1854,7 +1701,7 @@ int launch_wino(const float* in, const float* U, const float* bias, const float*
 }  // namespace
 
 // shapes this path takes: channel counts in whole chunks; even H, W (2x2 output tiles, 8-byte stores), or odd maps 9..16 wide
-// through the row-packed geometry (no fused pooling there: callers pass pool_idx / unpool only for even maps)
+// through the 16-tile kernel's row-packed geometry (no fused pooling there: callers pass pool_idx / unpool only for even maps)
 bool clhip_internal_wino_ok(int Cin, int Cout, int H, int W) {
     if (Cin % WCK || Cin < 16 || Cout % 32 || H < 4 || W < 8) return false;
     if (((H | W) & 1) == 0) return true;
@@ -1977,7 +1824,7 @@ static int wino_wgrad_geo(const float* x, const float* dy, const uint8_t* unpool
     // whole tiles in width and 16-byte-aligned tensors: stages staged in 16-byte pieces (VEC; other shapes: the scalar form)
     g->vec = W % (2 * TCS) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0;
     g->kc32 = (K / 32) * (C / 32);
-    g->ps = wgrad_ps_on() && g->total < 16 * splits;      // (measured: layer 2 of the bench model, 12.5 stages per block, 99 -> 92 us; 50 stages: slower)
+    g->ps = g->total < 16 * splits;      // (measured: layer 2 of the bench model, 12.5 stages per block, 99 -> 92 us; 50 stages: slower)
     if (g->ps) {
         // fewer than 16 stages per 64 x 64 tile block: 32 x 32 tiles, a quarter of the splits, two blocks per CU (wino_wgrad_ps_kernel)
         // blocks of the launch = (k, c) tiles x pixel splits: two per CU; one per CU on 8 x 8 maps with few (k, c) tiles, where a block
@@ -2027,9 +1874,9 @@ int clhip_internal_wino_wgrad_partial(const float* x, const float* dy, const uin
     const bool vecg = g.vec;
 #define WG(TCS_, TRS_, UNP_)                                                                                                         \
     do {                                                                                                                            \
-        if (vecg) hipLaunchKernelGGL((wino_wgrad_kernel<TCS_, TRS_, 1, UNP_, true>), dim3(grid), dim3(256), 0, s, x, dy, part,       \
+        if (vecg) hipLaunchKernelGGL((wino_wgrad_kernel<TCS_, TRS_, UNP_, true>), dim3(grid), dim3(256), 0, s, x, dy, part,       \
                                      unpool_idx, N, C, K, H, W, tiles_w, tiles_h, (int)total, (int)splits, C / WKT, slab);           \
-        else hipLaunchKernelGGL((wino_wgrad_kernel<TCS_, TRS_, 1, UNP_, false>), dim3(grid), dim3(256), 0, s, x, dy, part,           \
+        else hipLaunchKernelGGL((wino_wgrad_kernel<TCS_, TRS_, UNP_, false>), dim3(grid), dim3(256), 0, s, x, dy, part,           \
                                 unpool_idx, N, C, K, H, W, tiles_w, tiles_h, (int)total, (int)splits, C / WKT, slab);                \
     } while (0)
     if (wide) { if (unpool_idx) WG(8, 2, true); else WG(8, 2, false); }

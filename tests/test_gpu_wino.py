@@ -23,6 +23,8 @@ SHAPES = [  # N, C, K, H, W
     (200, 64, 128, 32, 32), (200, 128, 256, 16, 16), (200, 256, 256, 16, 16), (200, 256, 512, 8, 8), (200, 512, 512, 8, 8),
     # odd maps (AlexNet's 13 x 13 layers, models/net.py:96-125): row-packed geometry, half-outside last tile row / column
     (4, 32, 64, 13, 13), (3, 64, 32, 13, 13), (2, 16, 32, 9, 15), (5, 64, 64, 11, 13), (3, 32, 32, 13, 16), (37, 192, 384, 13, 13),
+    # even maps narrower than 16 other than 8 x 8: the 32-tile kernel (partial tiles, the smallest map, an image count that is no multiple of 4)
+    (3, 32, 64, 12, 12), (5, 32, 32, 4, 8), (2, 64, 64, 14, 14),
 ]
 
 
@@ -100,7 +102,8 @@ WG_SHAPES = [(3, 64, 64, 32, 32), (5, 64, 64, 16, 16), (6, 64, 128, 8, 8), (4, 1
              (3, 128, 256, 16, 16), (200, 64, 64, 32, 32), (200, 64, 64, 16, 16), (200, 128, 128, 8, 8),
              (200, 64, 128, 16, 16), (200, 128, 128, 16, 16), (200, 128, 256, 8, 8), (200, 256, 256, 8, 8),      # base_VGG9 at the bench batch
              (200, 64, 128, 32, 32), (200, 128, 256, 16, 16), (200, 256, 256, 16, 16), (200, 256, 512, 8, 8), (200, 512, 512, 8, 8),   # wide_VGG9
-             (6, 64, 64, 13, 13), (3, 128, 64, 9, 11), (4, 64, 128, 15, 16), (40, 192, 384, 13, 13)]
+             (6, 64, 64, 13, 13), (3, 128, 64, 9, 11), (4, 64, 128, 15, 16), (40, 192, 384, 13, 13),
+             (3, 64, 64, 12, 12)]             # a narrow map that is no whole number of tiles wide: scalar staging
 
 
 @pytest.mark.parametrize("shape", WG_SHAPES)
@@ -155,8 +158,7 @@ def test_wino_weight_images_agree(C, K):
     want[:K, :C] = np.einsum("ar,kcrs,bs->kcab", G, w.double().numpy(), G).reshape(K, C, 16)
     got = lds[..., :16].transpose(0, 3, 1, 2, 4).reshape(kts * 64, nch * 8, 16)          # [k][c][f]
     assert np.abs(got - want).max() <= 1e-6 * max(1.0, np.abs(want).max())
-    if U.size < n_lds + kts * nch * 2 * 4096:
-        pytest.skip("library built with CLHIP_W16G_ADIRECT=0: no lane-ordered image")
+    assert U.size >= n_lds + kts * nch * 2 * 4096, "the workspace holds the lane-ordered image behind the LDS image"
     direct = U[n_lds:n_lds + kts * nch * 2 * 4096].reshape(kts, 2 * nch, 2, 2, 4, 4, 16, 4)      # kt, chunk4, wk, r, fq, q, ti, j
     # the same elements out of the LDS image: channel = 8 chunk8 + 4 half + q, out channel = 32 wk + 16 r + ti, frequency = 4 fq + j
     e = lds[..., :16].reshape(kts, nch, 2, 4, 2, 2, 16, 4, 4)                                  # kt, chunk8, half, q, wk, r, ti, fq, j
