@@ -42,10 +42,15 @@ class GemNet(SharedRowDropout, ExemplarNet):
     """gem.Net (gem.py:83-387).  The pickle carries the wrapped net, the exemplar tensors (memory_x / memory_labels, whole)
     and the counters.  Dropout: one shared mask row per layer (gem.py:166-196), reset at every observe."""
 
-    _TRANSIENT_EXTRA = ("G", "_gram_ws", "_gram", "_v", "_info", "_qp_bad", "host_qp")
+    _TRANSIENT_EXTRA = ("G", "_gram_ws", "_qp_ws", "_gram", "_v", "_info", "_qp_bad", "host_qp")
+    NARROW_ROWS = 16                 # rows of a Gram matrix the register-resident kernels of csrc/gem.hip take
+    MAX_TASKS = 64                   # CLHIP_GEM_WIDE_MAX: 63 memory rows + the current gradient (csrc/gem_wide.hip)
 
     def __init__(self, model, n_outputs, n_tasks, nc_per_task, n_memories, lr, weight_decay=0.0, memory_strength=1.0,
                  batch_size=200, in_shape=(3, 64, 64), device="cuda", exemplar_transform=None, frame_shape=None, frame_norm=None):
+        if n_tasks > self.MAX_TASKS:
+            raise ValueError("GEM: n_tasks = %d, the Gram / QP / projection kernels take at most %d tasks (CLHIP_GEM_WIDE_MAX)"
+                             % (n_tasks, self.MAX_TASKS))
         self.net = model.to(device)
         self.device = torch.device(device)
         self.n_outputs, self.n_tasks, self.n_memories = n_outputs, n_tasks, n_memories
@@ -65,9 +70,17 @@ class GemNet(SharedRowDropout, ExemplarNet):
         super()._bind(mix=False)
         self.G = torch.zeros((self.n_tasks, self.A.numel), dtype=torch.float32, device=self.device)   # gem.py:131
         L = _lib.lib()
-        self._gram_ws = torch.zeros(L.clhip_gem_gram_ws(16), dtype=torch.uint8, device=self.device)
-        self._gram = torch.zeros(16 * 16, dtype=torch.float64, device=self.device)
-        self._v = torch.zeros(16, dtype=torch.float64, device=self.device)          # QP solution, stays on the device
+        # a Gram matrix has at most n_tasks rows (the memory rows of the earlier tasks + the current gradient); sequences of up
+        # to 16 tasks use the register-resident kernels only, longer ones the wide entries once more than 16 rows are live
+        rows = max(self.NARROW_ROWS, self.n_tasks)
+        ws = L.clhip_gem_gram_ws(self.NARROW_ROWS)
+        if rows > self.NARROW_ROWS:
+            ws = max(ws, L.clhip_gem_gram_wide_ws(rows))
+        self._gram_ws = torch.zeros(ws, dtype=torch.uint8, device=self.device)
+        self._qp_ws = torch.zeros(max(L.clhip_gem_qp_wide_ws(rows) if rows > self.NARROW_ROWS else 0, 16), dtype=torch.uint8,
+                                  device=self.device)
+        self._gram = torch.zeros(rows * rows, dtype=torch.float64, device=self.device)
+        self._v = torch.zeros(rows, dtype=torch.float64, device=self.device)        # QP solution, stays on the device
         self._info = torch.zeros(2, dtype=torch.int32, device=self.device)          # {violated constraints, status}
         self._qp_bad = torch.zeros(1, dtype=torch.int32, device=self.device)        # sticky: solves that did not report 'ok'
         self.host_qp = None          # tests only: a host solver f(gram, t, rows, margin) -> v replaces the device QP
@@ -128,8 +141,10 @@ class GemNet(SharedRowDropout, ExemplarNet):
     def gram(self, rows, to_host=True):
         m = len(rows)
         idx = (C.c_int * m)(*rows)
-        check(_lib.lib().clhip_gem_gram(self.G.data_ptr(), self.G.shape[1], idx, m, self.A.numel, self._gram.data_ptr(),
-                                        self._gram_ws.data_ptr(), self._gram_ws.numel(), _stream()), "clhip_gem_gram")
+        L = _lib.lib()
+        name = "clhip_gem_gram" if m <= self.NARROW_ROWS else "clhip_gem_gram_wide"
+        check(getattr(L, name)(self.G.data_ptr(), self.G.shape[1], idx, m, self.A.numel, self._gram.data_ptr(),
+                               self._gram_ws.data_ptr(), self._gram_ws.numel(), _stream()), name)
         return self._gram[:m * m].cpu().numpy().reshape(m, m) if to_host else self._gram
 
     def project_on_device(self, rows, t, eps=1e-3):
@@ -139,12 +154,20 @@ class GemNet(SharedRowDropout, ExemplarNet):
         m = len(rows) + 1
         self.gram(list(rows) + [t], to_host=False)
         L = _lib.lib()
-        check(L.clhip_gem_qp(self._gram.data_ptr(), m, float(self.margin), float(eps), self._v.data_ptr(), self._info.data_ptr(),
-                             _stream()), "clhip_gem_qp")
         idx = (C.c_int * (m - 1))(*rows)
-        check(L.clhip_gem_project_dev(self.G.data_ptr(), self.G.shape[1], idx, self._v.data_ptr(), self._info.data_ptr(), m - 1,
-                                      self.G[t].data_ptr(), self.A.grad.data_ptr(), self.A.numel, _stream()),
-              "clhip_gem_project_dev")
+        if m <= self.NARROW_ROWS:
+            check(L.clhip_gem_qp(self._gram.data_ptr(), m, float(self.margin), float(eps), self._v.data_ptr(), self._info.data_ptr(),
+                                 _stream()), "clhip_gem_qp")
+            check(L.clhip_gem_project_dev(self.G.data_ptr(), self.G.shape[1], idx, self._v.data_ptr(), self._info.data_ptr(), m - 1,
+                                          self.G[t].data_ptr(), self.A.grad.data_ptr(), self.A.numel, _stream()),
+                  "clhip_gem_project_dev")
+        else:                                    # more than 16 rows: the workgroup QP and the 63-row projection
+            check(L.clhip_gem_qp_wide(self._gram.data_ptr(), m, float(self.margin), float(eps), self._v.data_ptr(),
+                                      self._info.data_ptr(), self._qp_ws.data_ptr(), self._qp_ws.numel(), _stream()),
+                  "clhip_gem_qp_wide")
+            check(L.clhip_gem_project_dev_wide(self.G.data_ptr(), self.G.shape[1], idx, self._v.data_ptr(), self._info.data_ptr(),
+                                               m - 1, self.G[t].data_ptr(), self.A.grad.data_ptr(), self.A.numel, _stream()),
+                  "clhip_gem_project_dev_wide")
         self._qp_bad += self._info[1:2]          # status 1 (iteration limit) / 2 (infeasible) must not pass silently
         return self._info[0].clone()
 
@@ -160,8 +183,9 @@ class GemNet(SharedRowDropout, ExemplarNet):
         m = len(rows)
         idx = (C.c_int * m)(*rows)
         vv = (C.c_float * m)(*[float(a) for a in v])
-        check(_lib.lib().clhip_gem_project(self.G.data_ptr(), self.G.shape[1], idx, vv, m, self.G[t].data_ptr(),
-                                           self.A.grad.data_ptr(), self.A.numel, _stream()), "clhip_gem_project")
+        name = "clhip_gem_project" if m <= self.NARROW_ROWS else "clhip_gem_project_wide"
+        check(getattr(_lib.lib(), name)(self.G.data_ptr(), self.G.shape[1], idx, vv, m, self.G[t].data_ptr(),
+                                        self.A.grad.data_ptr(), self.A.numel, _stream()), name)
 
     # ------------------------------------------------------------------ gem.py:206-287
     def observe(self, x, t, y, source=None):

@@ -162,6 +162,9 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         raise NotImplementedError("rehearsal method %r (iCaRL has its own entry: methods.icarl_main.main)" % args.method)
     assert args.n_outputs == sum(args.nc_per_task)
     assert args.n_tasks == len(nc_per_task)
+    if not baseline and args.n_tasks > G.GemNet.MAX_TASKS:           # at construction, not in the first observe of task 65
+        raise ValueError("gem: n_tasks = %d, the Gram / QP / projection kernels take at most %d tasks (CLHIP_GEM_WIDE_MAX)"
+                         % (args.n_tasks, G.GemNet.MAX_TASKS))
     if args.task_count == 1 and not baseline:
         assert "SI" in args.prev_model_path, "FIRST TASK NOT STARTING FROM SCRATCH, BUT FROM SI: ONLY STORING WRAPPER " \
                                              "WITH EXEMPLARS, path = {}".format(args.prev_model_path)

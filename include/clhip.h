@@ -523,6 +523,29 @@ int clhip_gem_project(const float* G, size_t ld, const int* row_idx_host, const 
 int clhip_gem_qp(const double* gram_f64, int m, double margin, double eps, double* v_out_f64, int* info_i32, void* stream);
 int clhip_gem_project_dev(const float* G, size_t ld, const int* row_idx_host, const double* v_dev_f64, const int* info_dev,
                           int m, const float* g, float* out, size_t n, void* stream);
+/* The same four operations for task sequences of more than 16 tasks (GEM's own paper runs 20): up to CLHIP_GEM_WIDE_MAX rows
+ * of a Gram matrix = 63 memory rows + the current gradient = CLHIP_MAX_TASKS tasks.  Semantics are those of the entries
+ * above at every m in range, m <= 16 included (the Gram sums are added in another order there, so the two agree to the
+ * f64 summation bound, not bit for bit); the entries above stay what a sequence of <= 16 tasks calls.
+ *   gem_gram_wide    1 <= m <= 64.  The rows are cut into 16-row panels, every panel pair is one f64 matrix-core tile; f64
+ *                    accumulation only, per-block tiles in ws (clhip_gem_gram_wide_ws(m) bytes, 0 for an m out of range), a
+ *                    grid that depends on n alone and fixed-order sums: bitwise symmetric, and the same bits in every run.
+ *                    Rows that are not selected and columns n .. ld-1 are never read.
+ *   gem_qp_wide      2 <= m <= 64 (m - 1 <= 63 unknowns): the Goldfarb-Idnani steps and decisions of gem_qp on ONE workgroup,
+ *                    matrices in LDS.  Same v_out_f64[m - 1] / info_i32[2] contract.  clhip_gem_qp_wide_ws(m) is 0 in this
+ *                    build and ws may then be NULL; ws_bytes below what it reports is refused.
+ *   gem_project_wide / gem_project_dev_wide    1 <= m <= 63 memory rows, the arithmetic of gem_project / gem_project_dev.   */
+#define CLHIP_GEM_WIDE_MAX 64
+size_t clhip_gem_gram_wide_ws(int m);
+int clhip_gem_gram_wide(const float* G, size_t ld, const int* row_idx_host, int m, size_t n, double* out_f64, void* ws,
+                        size_t ws_bytes, void* stream);
+size_t clhip_gem_qp_wide_ws(int m);
+int clhip_gem_qp_wide(const double* gram_f64, int m, double margin, double eps, double* v_out_f64, int* info_i32, void* ws,
+                      size_t ws_bytes, void* stream);
+int clhip_gem_project_wide(const float* G, size_t ld, const int* row_idx_host, const float* v_host, int m, const float* g,
+                           float* out, size_t n, void* stream);
+int clhip_gem_project_dev_wide(const float* G, size_t ld, const int* row_idx_host, const double* v_dev_f64, const int* info_dev,
+                               int m, const float* g, float* out, size_t n, void* stream);
 
 /* ------------------------------------------------------------------ rehearsal baselines
  * rehearsal/model/baseline_rehearsal_partial_mem.py:125-253 (observe_FT; full_mem.py is the same class): the reference runs
