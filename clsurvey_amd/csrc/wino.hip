@@ -1770,6 +1770,8 @@ int clhip_internal_wino_conv(int mode, const float* in, const float* w, const fl
                              size_t ws_bytes, hipStream_t s) {
     if (!in || !w || !out || !ws || !clhip_internal_wino_ok(Cin, Cout, H, W) || ws_bytes < clhip_internal_wino_ws(Cin, Cout))
         return CLHIP_EINVAL;
+    // (clhip_internal_wino_conv_u's refusal, ahead of the weight transform: a refused call launches nothing and leaves ws as it was)
+    if (((H | W) & 1) && (pool_idx || unpool)) return CLHIP_ENOTSUP;
     float* U = static_cast<float*>(ws);
     const int n_chunks = (Cin + WCK - 1) / WCK;
     const int total = ((Cout + WKT - 1) / WKT) * n_chunks * WCK * WKT;
@@ -1780,7 +1782,9 @@ int clhip_internal_wino_conv(int mode, const float* in, const float* w, const fl
 
 // ---- weight gradient through the Winograd path: slabs only, in the format of conv3x3_wgrad.hip (see wino_wgrad_kernel)
 bool clhip_internal_wino_wgrad_ok(int C, int K, int H, int W) {
-    return C % WKT == 0 && K % WKT == 0 && H >= 4 && W >= 8;      // odd H / W: half-outside tiles stage zeros (no fused un-pooling there)
+    // odd H / W: half-outside tiles stage zeros (no fused un-pooling there).  (C, K > 0: no (k, c) tiles otherwise, and the slab counts
+    // of clhip_internal_wino_wgrad_ws and wino_wgrad_geo divide by their number)
+    return C > 0 && K > 0 && C % WKT == 0 && K % WKT == 0 && H >= 4 && W >= 8;
 }
 
 // slabs the launch below wants (it takes fewer when the workspace is smaller)

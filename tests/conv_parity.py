@@ -1,4 +1,4 @@
-"""What test_gpu_conv2d_kernels.py and test_gpu_conv5x5_bs_kernels.py share (test infrastructure): operands of a convolution
+"""What test_gpu_conv2d_kernels.py, test_gpu_conv5x5_bs_kernels.py and test_gpu_wino_kernels.py share (test infrastructure): operands of a convolution
 layer, one raw-pointer call of an entry point on a fresh kernel_parity.Arena, and the per-element accuracy rule.
 
 Arena layout of a call: every operand lies directly between two runs of GUARD floats that hold a NaN bit pattern (a read of even
@@ -10,11 +10,12 @@ import types
 import pytest
 import torch
 
-from kernel_parity import Arena, ConvRef, all_bits, bit_pattern, bitwise_equal, ulp_distance
+from kernel_parity import Arena, ByteArena, ConvRef, all_bits, bit_pattern, bitwise_equal, ulp_distance
 
 WS_BITS = 0x7FC0BEEF          # workspace before a call: a quiet NaN, payload 0xBEEF
 OUT_BITS = 0x7FC00A11         # outputs before a call
 GUARD_BITS = 0x7FC0D00D       # guard items on both sides of every operand
+BYTE_OUT = 0xEE               # uint8 outputs before a call (the arg-max codes are 0..4; ByteArena's gap bytes are 0xA5)
 GUARD = 80                    # NaN floats directly in front of and behind every operand (a multiple of 4)
 WS_SLACK = 64                 # floats of workspace handed over beyond what a call needs
 U = 2.0 ** -24                # unit roundoff of float32
@@ -129,12 +130,14 @@ def ref_of(kind, ref):
     return {"fwd": (ref.y64, ref.y32, ref.s_y), "bwd_data": (ref.dx64, ref.dx32, ref.s_dx), "bwd_weight": (ref.dw64, ref.dw32, ref.s_dw)}[kind]
 
 
-def run_call(call, ins, outs, ws_floats=0, ws_bytes=None, mis=None, mis_by=1):
+def run_call(call, ins, outs, ws_floats=0, ws_bytes=None, mis=None, mis_by=1, bins=(), bouts=()):
     """One call on a fresh arena.  ins: [(name, tensor or None)], outs: [(name, floats or None)] (None: the pointer is NULL);
     call(ptr, ws_ptr, ws_bytes, stream) -> rc with ptr a dict name -> address (or None).  mis: the name of the one tensor that
     sits mis_by floats past a 16-byte boundary.  Every input is ONE arena item [GUARD NaNs | tensor | GUARD NaNs]: the float in
-    front of an operand and the float behind it are NaN.  Returns rc, the outputs, the workspace and whether everything else
-    (gaps, guards, inputs) is untouched."""
+    front of an operand and the float behind it are NaN.  bins: [(name, uint8 tensor or None)], bouts: [(name, bytes or None)]:
+    uint8 operands and outputs (arg-max codes) in a kernel_parity.ByteArena of their own, each at an odd address between at least
+    16 sentinel bytes on either side, outputs pre-filled with BYTE_OUT; their addresses join `ptr`, their outputs `out`.  Returns
+    rc, the outputs, the workspace and whether everything else (gaps, guards, inputs, of both arenas) is untouched."""
     assert GUARD % 4 == 0
     guard = bit_pattern(GUARD, GUARD_BITS)
     ar = Arena()
@@ -149,6 +152,20 @@ def run_call(call, ins, outs, ws_floats=0, ws_bytes=None, mis=None, mis_by=1):
     kws = ar.add(max(ws_floats, 4), fill=WS_BITS)
     ar.upload(dev())
     ptr = {name: (ar.ptr(keys[name]) + 4 * start[name] if name in keys else None) for name, _ in list(ins) + list(outs)}
+    bar, bkeys, bgiven = None, {}, {}
+    if any(t is not None for _, t in list(bins) + list(bouts)):
+        bar = ByteArena()
+        for name, t in bins:
+            if t is not None:
+                bgiven[name] = t.detach().cpu().contiguous().reshape(-1)
+                bkeys[name] = bar.add(bgiven[name])
+        for name, n in bouts:
+            if n is not None:
+                bkeys[name] = bar.add(n, fill=BYTE_OUT)
+        bar.upload(dev())
+    for name, _ in list(bins) + list(bouts):
+        assert name not in ptr
+        ptr[name] = bar.ptr(bkeys[name]) if name in bkeys else None
     if mis is not None:
         assert ptr[mis] % 16 == 4 * mis_by
     rc = call(ptr, ar.ptr(kws), 4 * ws_floats if ws_bytes is None else ws_bytes, torch.cuda.current_stream().cuda_stream)
@@ -160,4 +177,8 @@ def run_call(call, ins, outs, ws_floats=0, ws_bytes=None, mis=None, mis_by=1):
     r = types.SimpleNamespace(rc=rc, ws=ar.get(kws).clone())
     r.out = {name: ar.get(keys[name]).clone() for name, n in outs if n is not None}
     r.clean = ar.gaps_untouched() and all(bitwise_equal(ar.get(keys[name]), padded[name]) for name in padded)      # guards and inputs
+    if bar is not None:
+        bar.download()
+        r.out.update({name: bar.get(bkeys[name]).clone() for name, n in bouts if n is not None})
+        r.clean = r.clean and bar.gaps_untouched() and all(torch.equal(bar.get(bkeys[name]), bgiven[name]) for name in bgiven)
     return r

@@ -1,7 +1,7 @@
 """Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py,
 test_gpu_gemm_kernels.py, test_gpu_pool_kernels.py, test_gpu_bn_kernels.py, test_gpu_packnet_kernels.py,
 test_gpu_elementwise_kernels.py, test_gpu_gem_kernels.py, test_gpu_fc_chain_kernels.py, test_gpu_conv2d_kernels.py,
-test_gpu_conv5x5_bs_kernels.py) — test infrastructure.
+test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py) — test infrastructure.
 
 The fp32-chain rule is the one of assert_fp32_parity in test_gpu_parity.py with the bounds these two files use: the device
 result's distance from an fp64 evaluation of the same formula on the same float32 inputs, relative to the tensor's largest
@@ -86,6 +86,50 @@ class ConvRef:
         self.dw32 = conv2d_weight(x, w.shape, dy, stride, pad)
         self.db64 = dyd.sum((0, 2, 3))
         self.s_db = dyd.abs().sum((0, 2, 3))
+
+
+# Winograd F(2x2, 3x3) (Lavin & Gray): Y = A^T [ (G g G^T) .* (B^T d B) ] A.  The transforms add and cancel, so the direct product of
+# absolute values (ConvRef.s_y) is no bound for the terms a Winograd kernel rounds; the two functions below evaluate the same
+# formulas with every matrix and operand replaced by its absolute value, in fp64: what a rounding analysis of csrc/wino.hip is measured in.
+WINO_BT = [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]]
+WINO_G = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]]
+WINO_AT = [[1, 1, 1, 0], [0, 1, -1, -1]]
+
+
+def _wino_windows(t, win):
+    """[N][C][H][W] -> [N][C][TH][TW][win][win]: the 4x4 input windows (win = 4, one zero ring around the map) or the 2x2 output
+    tiles (win = 2) of the ceil(H/2) x ceil(W/2) tiles; what lies outside the map (tiles half outside an odd map) is zero."""
+    N, C, H, W = t.shape
+    TH, TW = (H + 1) // 2, (W + 1) // 2
+    lead = 1 if win == 4 else 0
+    p = torch.zeros((N, C, 2 * TH + 2 * lead, 2 * TW + 2 * lead), dtype=torch.float64)
+    p[:, :, lead:lead + H, lead:lead + W] = t.double()
+    return p.unfold(2, win, 2).unfold(3, win, 2)
+
+
+def wino_magnitude(inp, g):
+    """S_w[n][k][h][w] = |A^T| [ sum_c (|G| |g| |G^T|) .* (|B^T| |d| |B|) ] |A| for inp [N][Cin][H][W], g [Cout][Cin][3][3] as the
+    KERNEL sees them (backward-data: inp = dy, g[c][k] = the 180-degree-rotated w[k][c]).  S_w >= conv(|inp|, |g|) element by element."""
+    N, Cin, H, W = inp.shape
+    Bt, G, At = (torch.tensor(m, dtype=torch.float64).abs() for m in (WINO_BT, WINO_G, WINO_AT))
+    d = _wino_windows(inp.abs(), 4)                                            # [N][Cin][TH][TW][4][4]
+    TH, TW = d.shape[2], d.shape[3]
+    V = torch.einsum("ai,nctuij,bj->abcntu", Bt, d, Bt).reshape(16, Cin, N * TH * TW)
+    Uw = torch.einsum("ar,kcrs,bs->abkc", G, g.double().abs(), G).reshape(16, g.shape[0], Cin)
+    M = torch.bmm(Uw, V).reshape(4, 4, g.shape[0], N, TH, TW)
+    Y = torch.einsum("ia,abkntu,jb->nktiuj", At, M, At).reshape(N, g.shape[0], 2 * TH, 2 * TW)
+    return Y[:, :, :H, :W].contiguous()
+
+
+def wino_wgrad_magnitude(x, dy):
+    """S_wg[k][c][r][s] = |G^T| [ sum over images and tiles (|A| |dY| |A^T|) .* (|B^T| |d| |B|) ] |G| for x [N][C][H][W], dy [N][K][H][W]."""
+    N, C, H, W = x.shape
+    K = dy.shape[1]
+    Bt, G, At = (torch.tensor(m, dtype=torch.float64).abs() for m in (WINO_BT, WINO_G, WINO_AT))
+    V = torch.einsum("ai,nctuij,bj->abcntu", Bt, _wino_windows(x.abs(), 4), Bt).reshape(16, C, -1)
+    D = torch.einsum("ia,nktuij,jb->abkntu", At, _wino_windows(dy.abs(), 2), At).reshape(16, K, -1)
+    M = torch.bmm(D, V.transpose(1, 2)).reshape(4, 4, K, C)
+    return torch.einsum("ar,abkc,bs->kcrs", G, M, G).contiguous()
 
 
 class Arena:
