@@ -696,6 +696,7 @@ int clhip_conv3x3_bs_fwd(const float* x, const float* w, const float* b, float* 
                          int W, int relu, void* ws, size_t ws_bytes, void* stream) {
     if (N <= 0 || !clhip_internal_bs_ok(C, K, H, W)) return CLHIP_ENOTSUP;
     if (!x || !w || !y || !ws || ws_bytes < clhip_internal_bs_ws(C, K)) return CLHIP_EINVAL;
+    if (((H | W) & 1) && idx_u8_or_null) return CLHIP_ENOTSUP;       // what clhip_internal_bs_conv_u refuses, ahead of the weight launch
     const clhip_wino_wt job{w, static_cast<float*>(ws), K, C, 0, 0};
     const int rc = clhip_internal_bs_weights(&job, 1, as_stream(stream));
     if (rc) return rc;
@@ -706,6 +707,7 @@ int clhip_conv3x3_bs_bwd_data(const float* dy, const uint8_t* idx_u8_or_null, co
                               int C, int K, int H, int W, void* ws, size_t ws_bytes, void* stream) {
     if (N <= 0 || !clhip_internal_bs_ok(K, C, H, W)) return CLHIP_ENOTSUP;
     if (!dy || !w || !dx || !ws || ws_bytes < clhip_internal_bs_ws(K, C)) return CLHIP_EINVAL;
+    if (((H | W) & 1) && idx_u8_or_null) return CLHIP_ENOTSUP;       // as above: nothing is launched for a refused call
     const clhip_wino_wt job{w, static_cast<float*>(ws), C, K, 1, 0};
     const int rc = clhip_internal_bs_weights(&job, 1, as_stream(stream));
     if (rc) return rc;

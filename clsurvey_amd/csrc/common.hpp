@@ -15,6 +15,22 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// What the 32-bit index arithmetic of the direct 3x3 kernels (conv3x3.hip, conv3x3_wgrad.hip) can carry.  They form byte offsets in
+// int relative to the first image of a block's tile (at most two images: Geo<8,8,2>), to the weight tensor, and — the weight
+// gradient's staging — to 64 channel planes of one image; tile and stage counts are int.  Whole tensors may exceed 2 GB (the image
+// base is a 64-bit pointer), so the limits are per image.  A partial last channel tile forms the offset of up to 63 channels past
+// the tensor's last before the lane is masked, so each channel count carries that margin:  2 * (C + 32) * H * W * 4,
+// 2 * (K + 32) * H * W * 4 and 9 * K * C * 4 below 2^31 (which leaves 64 * H * W * 4 below 2^31 too), N * H * W (an upper bound of
+// every tile count) below 2^31.
+static inline bool clhip_conv3x3_dims_ok(int N, int C, int K, int H, int W) {
+    if (N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return false;
+    const long long hw = (long long)H * W;
+    if (hw >= (1LL << 23)) return false;
+    if (hw * (C + 32LL) >= (1LL << 28) || hw * (K + 32LL) >= (1LL << 28)) return false;      // hw < 2^23, C < 2^31: no overflow of the product
+    if ((long long)K * C >= (1LL << 29) / 9) return false;
+    return hw * N <= 0x7fffffffLL;
+}
+
 // Grid for HBM-bound grid-stride kernels: enough blocks to fill 256 CUs x 8, capped.
 static inline int ew_grid(size_t work_items, int block) {
     size_t g = (work_items + block - 1) / block;

@@ -1237,7 +1237,7 @@ int clhip_debug_set_conv_trace(void* p) {
 
 int clhip_conv3x3_fwd(const float* x, const float* w, const float* b, float* y,
                       int N, int C, int K, int H, int W, int relu, void* stream) {
-    if (!x || !w || !y || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return CLHIP_EINVAL;
+    if (!x || !w || !y || !clhip_conv3x3_dims_ok(N, C, K, H, W)) return CLHIP_EINVAL;
     hipStream_t s = as_stream(stream);
     if (C <= 4) return launch_conv<4, 0, false>(x, w, b, nullptr, y, N, C, K, H, W, K, C, relu, s);
     if (vec_ok(x, w, C, H, W, C)) return launch_conv<8, 0, true>(x, w, b, nullptr, y, N, C, K, H, W, K, C, relu, s);
@@ -1246,11 +1246,11 @@ int clhip_conv3x3_fwd(const float* x, const float* w, const float* b, float* y,
 
 int clhip_conv3x3_relu_pool_fwd(const float* x, const float* w, const float* b, float* y_pool, uint8_t* idx_u8,
                                 int N, int C, int K, int H, int W, void* stream) {
-    if (!x || !w || !y_pool || !idx_u8 || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1))
-        return CLHIP_EINVAL;
+    if (!x || !w || !y_pool || !idx_u8 || !clhip_conv3x3_dims_ok(N, C, K, H, W) || (H & 1) || (W & 1)) return CLHIP_EINVAL;
     hipStream_t s = as_stream(stream);
     if (c3w64_shape(N, C, K, H, W)) return launch_c3w64_pool(x, w, b, y_pool, idx_u8, N, K, H, W, s);
-    if (C == 3 && W % C3_TW == 0) return launch_c3_pool(x, w, b, y_pool, idx_u8, N, K, H, W, s);
+    // (conv3x3_c3_relu_pool_kernel leaves through 16-byte stores of y_pool and the codes: other addresses take the chunked kernel)
+    if (C == 3 && W % C3_TW == 0 && aligned16(y_pool) && aligned16(idx_u8)) return launch_c3_pool(x, w, b, y_pool, idx_u8, N, K, H, W, s);
 
     if (C <= 4) return launch_conv<4, 0, false>(x, w, b, nullptr, y_pool, N, C, K, H, W, K, C, 1, s, idx_u8);
     if (vec_ok(x, w, C, H, W, C)) return launch_conv<8, 0, true>(x, w, b, nullptr, y_pool, N, C, K, H, W, K, C, 1, s, idx_u8);
@@ -1278,7 +1278,7 @@ extern "C" {
 
 int clhip_conv3x3_bwd_data(const float* dy, const float* w, const float* relu_src, float* dx,
                            int N, int C, int K, int H, int W, void* stream) {
-    if (!dy || !w || !dx || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return CLHIP_EINVAL;
+    if (!dy || !w || !dx || !clhip_conv3x3_dims_ok(N, C, K, H, W)) return CLHIP_EINVAL;
     // in = dy (K channels), out = dx (C channels)
     if (vec_ok(dy, w, K, H, W, C))
         return launch_conv<8, 1, true>(dy, w, nullptr, relu_src, dx, N, K, C, H, W, K, C, 0, as_stream(stream));
@@ -1290,7 +1290,7 @@ int clhip_conv3x3_bwd_data(const float* dy, const float* w, const float* relu_sr
 // staging path): CLHIP_ENOTSUP otherwise, callers then un-pool first.
 int clhip_conv3x3_bwd_data_unpool(const float* dy_pool, const uint8_t* idx_u8, const float* w, const float* relu_src, float* dx,
                                   int N, int C, int K, int H, int W, void* stream) {
-    if (!dy_pool || !idx_u8 || !w || !dx || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return CLHIP_EINVAL;
+    if (!dy_pool || !idx_u8 || !w || !dx || !clhip_conv3x3_dims_ok(N, C, K, H, W)) return CLHIP_EINVAL;
     if ((H & 1) || (W & 1) || !vec_ok(dy_pool, w, K, H, W, C) || (reinterpret_cast<uintptr_t>(idx_u8) & 1u)) return CLHIP_ENOTSUP;
     return launch_conv<8, 1, true, true>(dy_pool, w, nullptr, relu_src, dx, N, K, C, H, W, K, C, 0, as_stream(stream),
                                          const_cast<uint8_t*>(idx_u8));

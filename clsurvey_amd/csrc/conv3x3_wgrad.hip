@@ -9,8 +9,9 @@
 // The reduction dimension (N*H*W, up to 819 200) is split across blocks (about one block per
 // CU: the kernel is MFMA-bound and software-pipelined — the next 64-pixel stage is prefetched
 // into registers while the current one feeds the matrix pipe).  Every block writes a partial
-// [9][K][C](+[K]) slab into the caller's workspace; two small kernels then sum the slabs in a
-// fixed order (grouped, then across groups) => bitwise run-to-run deterministic, as the
+// [9][K][C](+[K]) slab into the caller's workspace; ONE small kernel (wgrad_reduce_kernel) then
+// sums the `splits` slabs in a fixed two-level order (16 contiguous ranges of slabs in f64, then
+// the 16 range sums in order) => bitwise run-to-run deterministic, as the
 // reference promises by seeding everything and setting cudnn.deterministic
 // (utilities/utils.py:52-58).
 //
@@ -807,7 +808,7 @@ constexpr int RED_THREADS = RED_EL / RED_V * RED_J;
 // against 22.7 us for the slabs of a small_VGG9 pass, profiles/r05_wgred_wide.txt: fewer splits in flight per element.)
 
 // One block: elements [e0, e0 + 64) of the (9KC + K)-element slab.  Thread (j, v) sums splits [j q, (j + 1) q) of the 4
-// consecutive elements v (16-byte loads when the slab rows are 16-byte aligned), then lane j = 0 adds the 16 partial
+// consecutive elements v (16-byte loads when every slab row is 16-byte aligned: total % 4 == 0 and `part` itself), then lane j = 0 adds the 16 partial
 // sums in order: the order per element does not depend on the vector width.
 template <int EL, int J>
 __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ part, float* __restrict__ dw, float* __restrict__ db,
@@ -818,7 +819,7 @@ __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ par
     const int q = (splits + J - 1) / J;
     const int s0 = j * q, s1 = min(splits, s0 + q);
     double s[RED_V] = {0.0, 0.0, 0.0, 0.0};
-    if ((total & 3) == 0 && e + RED_V <= total) {
+    if ((total & 3) == 0 && (reinterpret_cast<uintptr_t>(part) & 15u) == 0 && e + RED_V <= total) {
         // (four slabs in flight per thread; eight were measured SLOWER — 36.7 us against 24.5 for the slabs of a small_VGG9 pass)
 #pragma unroll 4
         for (int sp = s0; sp < s1; ++sp) {
@@ -917,7 +918,8 @@ WPlan make_plan(int N, int C, int K, int H, int W) {
     if ((size_t)splits > max_splits) splits = (int)max_splits;
     if (splits < 1) splits = 1;
     p.splits = splits;
-    // two-level reduction: groups of ~sqrt(splits)
+    // `groups` more slabs of ~sqrt(splits) are asked for (the intermediate sums of an earlier two-kernel reduction); nothing writes
+    // or reads them now — wgrad_reduce_kernel sums the `splits` slabs directly — but the size is part of the ABI callers planned with
     int group = 1;
     while (group * group < splits) ++group;
     p.group = group;
@@ -938,14 +940,14 @@ int clhip_debug_set_wgrad_trace(void* p) {
 #endif
 
 size_t clhip_conv3x3_bwd_weight_ws(int N, int C, int K, int H, int W) {
-    if (N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
+    if (!clhip_conv3x3_dims_ok(N, C, K, H, W)) return 0;       // what the entry points answer CLHIP_EINVAL to
     return make_plan(N, C, K, H, W).ws_floats * sizeof(float);
 }
 
 static int bwd_weight_impl(const float* x, const float* dy, const uint8_t* unpool_idx, float* dw, float* db,
                            int N, int C, int K, int H, int W, void* ws, size_t ws_bytes, void* stream,
                            clhip_wgrad_job* defer = nullptr) {
-    if (!x || !dy || !dw || !ws || N <= 0 || C <= 0 || K <= 0 || H <= 0 || W <= 0) return CLHIP_EINVAL;
+    if (!x || !dy || !dw || !ws || !clhip_conv3x3_dims_ok(N, C, K, H, W)) return CLHIP_EINVAL;
     if (unpool_idx && ((H & 1) || (W & 1))) return CLHIP_ENOTSUP;
     WPlan p = make_plan(N, C, K, H, W);
     if (ws_bytes < p.ws_floats * sizeof(float)) return CLHIP_ENOSPC;
@@ -995,7 +997,8 @@ int clhip_conv3x3_bwd_weight(const float* x, const float* dy, float* dw, float* 
 }
 
 // dy_pool[N][K][H/2][W/2] + idx: weight gradient of a conv whose ReLU output was 2x2-max-pooled, without
-// materialising the un-pooled gradient.  Supported for the first-layer kernel (C*9 <= 32); others: ENOTSUP.
+// materialising the un-pooled gradient.  First-layer kernels (C*9 <= 32): any even map, any alignment.  General kernel: its
+// 16-byte staging form only (W % 4 == 0, whole tiles along w, x and dy 16-byte aligned) and codes at an even address; ENOTSUP otherwise.
 int clhip_conv3x3_bwd_weight_unpool(const float* x, const float* dy_pool, const uint8_t* idx_u8, float* dw, float* db,
                                     int N, int C, int K, int H, int W, void* ws, size_t ws_bytes, void* stream) {
     if (!idx_u8) return CLHIP_EINVAL;

@@ -48,7 +48,10 @@ const char* clhip_arch(void);
 
 /* ------------------------------------------------------------------ convolution (MFMA fp32)
  * nn.Conv2d(C, K, 3, padding=1) (+ fused bias, ReLU) — models/VGGSlim.py:34-38.
- * y[N][K][H][W] = relu?(conv(x[N][C][H][W], w[K][C][3][3]) + b[K])                      */
+ * y[N][K][H][W] = relu?(conv(x[N][C][H][W], w[K][C][3][3]) + b[K])
+ * Size limits of every clhip_conv3x3_* entry point below up to clhip_conv3x3_bwd_weight_unpool (32-bit offsets inside one
+ * image; whole tensors may exceed 2 GB): (C+32)*H*W < 2^28, (K+32)*H*W < 2^28, 9*K*C < 2^29, N*H*W < 2^31.
+ * CLHIP_EINVAL beyond them, before any launch; clhip_conv3x3_bwd_weight_ws then reports 0.                */
 int clhip_conv3x3_fwd(const float* x, const float* w, const float* b, float* y,
                       int N, int C, int K, int H, int W, int relu, void* stream);
 

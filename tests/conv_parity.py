@@ -1,4 +1,4 @@
-"""What test_gpu_conv2d_kernels.py, test_gpu_conv5x5_bs_kernels.py and test_gpu_wino_kernels.py share (test infrastructure): operands of a convolution
+"""What test_gpu_conv2d_kernels.py, test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py and test_gpu_conv3x3_kernels.py share (test infrastructure): operands of a convolution
 layer, one raw-pointer call of an entry point on a fresh kernel_parity.Arena, and the per-element accuracy rule.
 
 Arena layout of a call: every operand lies directly between two runs of GUARD floats that hold a NaN bit pattern (a read of even
@@ -130,13 +130,14 @@ def ref_of(kind, ref):
     return {"fwd": (ref.y64, ref.y32, ref.s_y), "bwd_data": (ref.dx64, ref.dx32, ref.s_dx), "bwd_weight": (ref.dw64, ref.dw32, ref.s_dw)}[kind]
 
 
-def run_call(call, ins, outs, ws_floats=0, ws_bytes=None, mis=None, mis_by=1, bins=(), bouts=()):
+def run_call(call, ins, outs, ws_floats=0, ws_bytes=None, mis=None, mis_by=1, bins=(), bouts=(), bshift=None):
     """One call on a fresh arena.  ins: [(name, tensor or None)], outs: [(name, floats or None)] (None: the pointer is NULL);
     call(ptr, ws_ptr, ws_bytes, stream) -> rc with ptr a dict name -> address (or None).  mis: the name of the one tensor that
     sits mis_by floats past a 16-byte boundary.  Every input is ONE arena item [GUARD NaNs | tensor | GUARD NaNs]: the float in
     front of an operand and the float behind it are NaN.  bins: [(name, uint8 tensor or None)], bouts: [(name, bytes or None)]:
     uint8 operands and outputs (arg-max codes) in a kernel_parity.ByteArena of their own, each at an odd address between at least
-    16 sentinel bytes on either side, outputs pre-filled with BYTE_OUT; their addresses join `ptr`, their outputs `out`.  Returns
+    16 sentinel bytes on either side, outputs pre-filled with BYTE_OUT; their addresses join `ptr`, their outputs `out`.  bshift:
+    {name: bytes past a 16-byte boundary} for the byte operands that must not sit at the default odd address (0: 16-byte aligned, 2: even).  Returns
     rc, the outputs, the workspace and whether everything else (gaps, guards, inputs, of both arenas) is untouched."""
     assert GUARD % 4 == 0
     guard = bit_pattern(GUARD, GUARD_BITS)
@@ -158,10 +159,10 @@ def run_call(call, ins, outs, ws_floats=0, ws_bytes=None, mis=None, mis_by=1, bi
         for name, t in bins:
             if t is not None:
                 bgiven[name] = t.detach().cpu().contiguous().reshape(-1)
-                bkeys[name] = bar.add(bgiven[name])
+                bkeys[name] = bar.add(bgiven[name], shift=(bshift or {}).get(name))
         for name, n in bouts:
             if n is not None:
-                bkeys[name] = bar.add(n, fill=BYTE_OUT)
+                bkeys[name] = bar.add(n, fill=BYTE_OUT, shift=(bshift or {}).get(name))
         bar.upload(dev())
     for name, _ in list(bins) + list(bouts):
         assert name not in ptr

@@ -1,7 +1,7 @@
 """Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py,
 test_gpu_gemm_kernels.py, test_gpu_pool_kernels.py, test_gpu_bn_kernels.py, test_gpu_packnet_kernels.py,
 test_gpu_elementwise_kernels.py, test_gpu_gem_kernels.py, test_gpu_fc_chain_kernels.py, test_gpu_conv2d_kernels.py,
-test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py) — test infrastructure.
+test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py, test_gpu_conv3x3_kernels.py) — test infrastructure.
 
 The fp32-chain rule is the one of assert_fp32_parity in test_gpu_parity.py with the bounds these two files use: the device
 result's distance from an fp64 evaluation of the same formula on the same float32 inputs, relative to the tensor's largest
@@ -191,13 +191,14 @@ class ByteArena:
         self.items = []            # (offset, host tensor)
         self.size = 16
 
-    def add(self, t, odd=True, fill=None):
-        """t: a uint8 tensor, or with `fill` a number of bytes that all start as that value."""
+    def add(self, t, odd=True, fill=None, shift=None):
+        """t: a uint8 tensor, or with `fill` a number of bytes that all start as that value.  shift: bytes past a 16-byte
+        boundary (0..15), instead of what `odd` says."""
         if fill is not None:
             t = torch.full((int(t),), int(fill), dtype=torch.uint8)
         t = t.detach().contiguous().reshape(-1)
         assert t.dtype == torch.uint8
-        off = (self.size + 15) // 16 * 16 + 16 + (5 if odd else 0)
+        off = (self.size + 15) // 16 * 16 + 16 + ((5 if odd else 0) if shift is None else int(shift))
         self.items.append((off, t))
         self.size = off + t.numel()
         return len(self.items) - 1
