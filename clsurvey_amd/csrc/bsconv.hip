@@ -32,6 +32,10 @@
 //     contiguous bytes per channel instead of 64 scattered 8-byte pieces per store instruction.
 //   * the same kernel with 25 taps (KS = 5, halo 2) is AlexNet's second convolution.
 //
+// Non-finite operands.  A NaN reaches exactly the outputs whose window covers it.  So does an Inf, but as NaN: its leading piece is Inf and
+// the residual Inf - Inf is NaN, so every product of the pixel is non-finite and the sums that hold it are NaN where an f32 kernel gives
+// +-Inf.  What is promised (and tested, tests/test_gpu_bs3x3_kernels.py) is `non-finite`, never `Inf`.
+//
 // Algorithmic FLOPs 2 * 9 * Cin * Cout * H * W * N; issued on the matrix pipe: 6x that, against the 2.5 PFLOP/s dense bf16 peak.
 #include "common.hpp"
 #include "bs_weight.hpp"
@@ -300,7 +304,9 @@ __device__ __forceinline__ void bs_conv_body(
     // 2x2 windows, then reads rows back as float4s — so that a store instruction covers whole 32 .. 128-byte row pieces per channel
     // instead of 64 scattered 8-byte pieces (the scattered form took 24 us of a 102 us launch on its own, 77 us with the mask reads of
     // backward-data: profiles/r05_bs_v2_ablations.txt).  All staging buffers are free here (last barrier passed); each wave uses its own piece.
-    const bool fast = !odd && (W & 3) == 0 && (!pool || (OW & 3) == 0) && !(BS_ABL & 64);
+    // (the b128 / b64 / b32 code stores of the pooled fast path start at dword multiples of pool_idx: codes that do not lie on a 4-byte
+    // boundary take the general path, whose stores are single bytes)
+    const bool fast = !odd && (W & 3) == 0 && (!pool || ((OW & 3) == 0 && (reinterpret_cast<uintptr_t>(pool_idx) & 3u) == 0)) && !(BS_ABL & 64);
     if (fast) {
         // (output stores: buffer instructions with the output cache policy of common.hpp, descriptors at the wave's image)
         const size_t img_elems = (size_t)Cout * (pool ? (size_t)OH * OW : chw);
@@ -586,8 +592,24 @@ int bs_launch5(const float* in, const clhip_u32x4* wimg, const float* bias, cons
 
 // shapes this path takes: whole 32-channel k pairs on the input side, whole 64-channel groups on the output side; any H, W >= 4
 // (tiles past the edge stage zeros and store nothing); fused pooling / un-pooling only on even maps
+// (Cout >= 64: `Cout % 64 == 0` alone took 0 and negative multiples; every caller sees this — the entry points here, s2dconv.hip and
+// the *_preferred rules below — and none of them ever launched usefully with Cout <= 0)
 bool clhip_internal_bs_ok(int Cin, int Cout, int H, int W) {
-    return Cin >= 32 && Cin % 32 == 0 && Cout % 64 == 0 && H >= 4 && W >= 4;
+    return Cin >= 32 && Cin % 32 == 0 && Cout >= 64 && Cout % 64 == 0 && H >= 4 && W >= 4;
+}
+
+// ... and whose offsets the kernel can carry.  bs_conv_body re-bases its descriptors at the block's first image (size_t), so the batch
+// and the whole tensors are not limited; inside a block the byte offsets are int: xoff * 4 and cb + e * plane_in with so * 4 reach
+// NI * Cin * H * W * 4 (NI = 2 images per block where W <= 8), ((k * H + oh) * W + ow) * 4 reaches Cout * H * W * 4, and the weight-image
+// offset (nt * n_chunks * 3 * TAPS * 64 + lane) * 16 plus (c * 3 * TAPS + tap * 3 + s) * 1024 reaches the image's size, which is also what
+// clhip_rsrc can describe (2^31 - 1 bytes).  Stated on the un-pooled map for the pooled forms too.  ks: 3 or 5.
+// (clhip_internal_bs_preferred / _bs5_preferred do not consult this: a plan whose layer lies beyond these limits still chooses the path
+// and builds its weight image, and clhip_internal_bs_conv_u / _bs5_conv_u turn the layer down with CLHIP_EINVAL when the pass runs —
+// the plan executor relies on that run-time refusal.)
+bool clhip_internal_bs_index_ok(int Cin, int Cout, int H, int W, int ks) {
+    const long long px = (long long)H * W, ni = (ks == 3 && W <= 8) ? 2 : 1;
+    const long long img = (long long)((Cout + 31) / 32) * ((Cin + BS_CK - 1) / BS_CK) * 3 * ks * ks * 1024;
+    return ni * Cin * px < (1LL << 29) && Cout * px < (1LL << 29) && img <= 0x7fffffffLL;
 }
 
 // ... and where the plan executor prefers it to the Winograd f32 kernels (CLHIP_BS=0: nowhere; CLHIP_BS=2: wherever it can run).
@@ -643,7 +665,7 @@ int clhip_internal_bs_weights(const clhip_wino_wt* jobs, int n, hipStream_t s) {
 // clhip_internal_wino_conv_u (backward-data: Cin = the layer's OUT channels, Cout = its IN channels)
 int clhip_internal_bs_conv_u(int mode, const float* in, const void* wimg, const float* bias, const float* mask_src, float* out,
                              uint8_t* pool_idx, int unpool, int N, int Cin, int Cout, int H, int W, int relu, hipStream_t s) {
-    if (!in || !wimg || !out || N <= 0 || !clhip_internal_bs_ok(Cin, Cout, H, W)) return CLHIP_EINVAL;
+    if (!in || !wimg || !out || N <= 0 || !clhip_internal_bs_ok(Cin, Cout, H, W) || !clhip_internal_bs_index_ok(Cin, Cout, H, W, 3)) return CLHIP_EINVAL;
     if (((H | W) & 1) && (pool_idx || unpool)) return CLHIP_ENOTSUP;
     const clhip_u32x4* img = static_cast<const clhip_u32x4*>(wimg);
     if (mode == 0) return bs_launch<0, false>(in, img, bias, nullptr, out, pool_idx, N, Cin, Cout, H, W, relu, s);
@@ -654,7 +676,8 @@ int clhip_internal_bs_conv_u(int mode, const float* in, const void* wimg, const 
 // the same for 5 x 5 taps (image made by clhip_internal_bs_weights from a job with pad = 5)
 int clhip_internal_bs5_conv_u(int mode, const float* in, const void* wimg, const float* bias, const float* mask_src, float* out, int N,
                               int Cin, int Cout, int H, int W, int relu, hipStream_t s) {
-    if (!in || !wimg || !out || N <= 0 || !clhip_internal_bs_ok(Cin, Cout, H, W) || W <= 8) return CLHIP_EINVAL;
+    if (!in || !wimg || !out || N <= 0 || !clhip_internal_bs_ok(Cin, Cout, H, W) || W <= 8 || !clhip_internal_bs_index_ok(Cin, Cout, H, W, 5))
+        return CLHIP_EINVAL;
     const clhip_u32x4* img = static_cast<const clhip_u32x4*>(wimg);
     if (mode == 0) return bs_launch5<0>(in, img, bias, nullptr, out, N, Cin, Cout, H, W, relu, s);
     return bs_launch5<1>(in, img, nullptr, mask_src, out, N, Cin, Cout, H, W, 0, s);
@@ -671,6 +694,7 @@ int clhip_conv5x5_bs_fwd(const float* x, const float* w, const float* b, float* 
                          size_t ws_bytes, void* stream) {
     if (N <= 0 || !clhip_internal_bs_ok(C, K, H, W) || W <= 8) return CLHIP_ENOTSUP;
     if (!x || !w || !y || !ws || ws_bytes < clhip_internal_bs5_ws(C, K)) return CLHIP_EINVAL;
+    if (!clhip_internal_bs_index_ok(C, K, H, W, 5)) return CLHIP_EINVAL;      // 32-bit offsets inside one image (clhip.h), ahead of the weight launch
     const clhip_wino_wt job{w, static_cast<float*>(ws), K, C, 0, 5};
     const int rc = clhip_internal_bs_weights(&job, 1, as_stream(stream));
     if (rc) return rc;
@@ -681,6 +705,7 @@ int clhip_conv5x5_bs_bwd_data(const float* dy, const float* w, const float* relu
                               void* ws, size_t ws_bytes, void* stream) {
     if (N <= 0 || !clhip_internal_bs_ok(K, C, H, W) || W <= 8) return CLHIP_ENOTSUP;
     if (!dy || !w || !dx || !ws || ws_bytes < clhip_internal_bs5_ws(K, C)) return CLHIP_EINVAL;
+    if (!clhip_internal_bs_index_ok(K, C, H, W, 5)) return CLHIP_EINVAL;
     const clhip_wino_wt job{w, static_cast<float*>(ws), C, K, 1, 5};
     const int rc = clhip_internal_bs_weights(&job, 1, as_stream(stream));
     if (rc) return rc;
@@ -696,6 +721,7 @@ int clhip_conv3x3_bs_fwd(const float* x, const float* w, const float* b, float* 
                          int W, int relu, void* ws, size_t ws_bytes, void* stream) {
     if (N <= 0 || !clhip_internal_bs_ok(C, K, H, W)) return CLHIP_ENOTSUP;
     if (!x || !w || !y || !ws || ws_bytes < clhip_internal_bs_ws(C, K)) return CLHIP_EINVAL;
+    if (!clhip_internal_bs_index_ok(C, K, H, W, 3)) return CLHIP_EINVAL;      // 32-bit offsets inside one image (clhip.h), ahead of the weight launch
     if (((H | W) & 1) && idx_u8_or_null) return CLHIP_ENOTSUP;       // what clhip_internal_bs_conv_u refuses, ahead of the weight launch
     const clhip_wino_wt job{w, static_cast<float*>(ws), K, C, 0, 0};
     const int rc = clhip_internal_bs_weights(&job, 1, as_stream(stream));
@@ -707,6 +733,7 @@ int clhip_conv3x3_bs_bwd_data(const float* dy, const uint8_t* idx_u8_or_null, co
                               int C, int K, int H, int W, void* ws, size_t ws_bytes, void* stream) {
     if (N <= 0 || !clhip_internal_bs_ok(K, C, H, W)) return CLHIP_ENOTSUP;
     if (!dy || !w || !dx || !ws || ws_bytes < clhip_internal_bs_ws(K, C)) return CLHIP_EINVAL;
+    if (!clhip_internal_bs_index_ok(K, C, H, W, 3)) return CLHIP_EINVAL;
     if (((H | W) & 1) && idx_u8_or_null) return CLHIP_ENOTSUP;       // as above: nothing is launched for a refused call
     const clhip_wino_wt job{w, static_cast<float*>(ws), C, K, 1, 0};
     const int rc = clhip_internal_bs_weights(&job, 1, as_stream(stream));

@@ -83,7 +83,9 @@ struct BwRawD { float4 lo, hi; unsigned codes; };
 #define BW_SCHED 1      // 1: the splits of the next rows are interleaved into the MFMA stream of an interior step (sched_group_barrier)
 #endif
 
-template <bool UNPOOL>
+// CODE_BYTES (UNPOOL only): the four codes of a lane are loaded as four bytes instead of one dword — for codes that do not lie on a 4-byte
+// boundary (the dword load starts at a dword multiple of idx); same values, same arithmetic.
+template <bool UNPOOL, bool CODE_BYTES = false>
 __global__ __launch_bounds__(256, 1) void bs_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           const uint8_t* __restrict__ idx, float* __restrict__ part, int N, int C, int K,
                                                           int H, int W, int splits, long long rows_total, size_t slab_stride) {
@@ -140,7 +142,13 @@ __global__ __launch_bounds__(256, 1) void bs_wgrad_kernel(const float* __restric
                 const int so = ok ? (y >> 1) * Wd : 0;
                 r.lo = clhip_buf_load4(rs_d, ok ? dox : CLHIP_OOB, so * 4);
                 r.hi = r.lo;
-                r.codes = __builtin_amdgcn_raw_buffer_load_b32(rs_i, ok ? dio : CLHIP_OOB, so, 0);
+                if constexpr (CODE_BYTES) {
+                    r.codes = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) r.codes |= clhip_buf_load_u8(rs_i, ok ? dio + j : CLHIP_OOB, so) << (8 * j);
+                } else {
+                    r.codes = __builtin_amdgcn_raw_buffer_load_b32(rs_i, ok ? dio : CLHIP_OOB, so, 0);
+                }
             } else {
                 const int so = (ok ? y : 0) * W * 4;
                 r.lo = clhip_buf_load4(rs_d, ok ? dox : CLHIP_OOB, so);
@@ -330,7 +338,9 @@ int clhip_internal_bs_wgrad_partial(const float* x, const float* dy, const uint8
     const size_t slab = (size_t)9 * K * C + K;
     const int blocks = (K / 64) * (C / 64) * splits;
     float* part = static_cast<float*>(ws);
-    if (unpool_idx) hipLaunchKernelGGL(bs_wgrad_kernel<true>, dim3(blocks), dim3(256), 0, s, x, dy, unpool_idx, part, N, C, K, H, W, splits, units, slab);
+    if (unpool_idx && (reinterpret_cast<uintptr_t>(unpool_idx) & 3u))
+        hipLaunchKernelGGL((bs_wgrad_kernel<true, true>), dim3(blocks), dim3(256), 0, s, x, dy, unpool_idx, part, N, C, K, H, W, splits, units, slab);
+    else if (unpool_idx) hipLaunchKernelGGL(bs_wgrad_kernel<true>, dim3(blocks), dim3(256), 0, s, x, dy, unpool_idx, part, N, C, K, H, W, splits, units, slab);
     else hipLaunchKernelGGL(bs_wgrad_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, unpool_idx, part, N, C, K, H, W, splits, units, slab);
     CLHIP_LAUNCH_CHECK();
     *job = clhip_wgrad_job{part, dw, db, K, C, splits};

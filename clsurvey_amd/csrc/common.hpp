@@ -205,6 +205,7 @@ bool clhip_internal_wino_ok(int Cin, int Cout, int H, int W);
 size_t clhip_internal_wino_ws(int Cin, int Cout);
 // bsconv.hip: the same operators on the bf16 matrix cores with fp32 operands split into three bf16 pieces (weight image in `wimg`)
 bool clhip_internal_bs_ok(int Cin, int Cout, int H, int W);
+bool clhip_internal_bs_index_ok(int Cin, int Cout, int H, int W, int ks);      // the kernel's 32-bit offsets inside one image (ks: 3 or 5)
 bool clhip_internal_bs_preferred(int Cin, int Cout, int H, int W);
 bool clhip_internal_bs5_preferred(int Cin, int Cout, int H, int W);
 size_t clhip_internal_bs5_ws(int Cin, int Cout);

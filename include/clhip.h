@@ -141,7 +141,11 @@ int clhip_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* d
  * the operator of clhip_conv3x3_wino_bwd_weight (same arguments; idx_u8 != NULL: dy is the pooled gradient [N][K][H/2][W/2] + the
  * forward pass's arg-max codes), for C % 64 == 0, K % 64 == 0, W % 16 == 0; other maps from 8 pixels wide (13 x 13!) with C % 32 == 0,
  * K % 32 == 0 and a plain dy run on the tap-split kernel of csrc/bswgrad5.hip (CLHIP_ENOTSUP otherwise).  ws:
- * clhip_conv3x3_bs_bwd_weight_ws(N, C, K, H, W) bytes of slabs, reduced in a fixed order (bitwise deterministic). */
+ * clhip_conv3x3_bs_bwd_weight_ws(N, C, K, H, W) bytes of slabs, reduced in a fixed order (bitwise deterministic); 0 for a shape
+ * neither kernel takes.  Order of the answers: N <= 0, a shape neither kernel takes, codes on an odd map or with a shape the 16-pixel
+ * kernel does not take -> CLHIP_ENOTSUP; a NULL x / dy / dw / ws -> CLHIP_EINVAL; ws_bytes too small -> CLHIP_ENOSPC.  Per-image
+ * limits: C*H*W*4 and K*H*W*4 < 2^31 - 1 on the 16-pixel kernel, N*C*H*W*4 and N*K*H*W*4 < 2^31 - 1 on the tap-split one.  Codes may
+ * lie at any byte address. */
 size_t clhip_conv3x3_bs_bwd_weight_ws(int N, int C, int K, int H, int W);
 int clhip_conv3x3_bs_bwd_weight(const float* x, const float* dy, const uint8_t* idx_u8_or_null, float* dw, float* db, int N, int C, int K,
                                 int H, int W, void* ws, size_t ws_bytes, void* stream);
@@ -300,7 +304,15 @@ int clhip_conv3x3_wino_bwd(const float* x, const float* dy, const uint8_t* idx_u
  * Inf + NaN residuals, so such an output is NaN where the f32 kernels give +-Inf; either way the loss is non-finite and the trainers
  * stop the attempt (train_EWC.py:204-205).
  * Shapes: C % 32 == 0, K % 64 == 0 on the forward (K % 32, C % 64 on backward-data), H, W >= 4; fused pooling on even maps only;
- * CLHIP_ENOTSUP otherwise.  ws: clhip_conv3x3_bs_ws(C, K) bytes (the weight image of this call).                            */
+ * CLHIP_ENOTSUP otherwise.  ws: clhip_conv3x3_bs_ws(C, K) bytes (the weight image of this call).
+ * Order of the answers: N <= 0 or a shape outside the domain -> CLHIP_ENOTSUP; a NULL x / w / y (dy / w / dx) or ws, or ws_bytes below
+ * the weight image -> CLHIP_EINVAL (these entry points have no CLHIP_ENOSPC); a size beyond the limits below -> CLHIP_EINVAL; arg-max
+ * codes on an odd map -> CLHIP_ENOTSUP; all of it before anything is launched.
+ * Size limits (32-bit offsets inside the images of one block; the batch and whole tensors may exceed 2 GB), with Cin / Cout the
+ * channels as the kernel sees them (C, K forward; K, C backward-data) and stated on the un-pooled H x W map: Cin*H*W < 2^29
+ * (< 2^28 for the 3x3 entry points where W <= 8: two images per block), Cout*H*W < 2^29, and a weight image
+ * (clhip_conv3x3_bs_ws / clhip_conv5x5_bs_ws of this direction) under 2^31 bytes.  The 5x5 pair below has the same limits.
+ * Arg-max codes may lie at any byte address (off a 4-byte boundary the pooled forward stores them byte by byte).              */
 size_t clhip_conv3x3_bs_ws(int C, int K);
 int clhip_conv3x3_bs_fwd(const float* x, const float* w, const float* b, float* y, uint8_t* idx_u8_or_null, int N, int C, int K,
                          int H, int W, int relu, void* ws, size_t ws_bytes, void* stream);

@@ -1,4 +1,4 @@
-"""What test_gpu_conv2d_kernels.py, test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py and test_gpu_conv3x3_kernels.py share (test infrastructure): operands of a convolution
+"""What test_gpu_conv2d_kernels.py, test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py, test_gpu_conv3x3_kernels.py and test_gpu_bs3x3_kernels.py share (test infrastructure): operands of a convolution
 layer, one raw-pointer call of an entry point on a fresh kernel_parity.Arena, and the per-element accuracy rule.
 
 Arena layout of a call: every operand lies directly between two runs of GUARD floats that hold a NaN bit pattern (a read of even
