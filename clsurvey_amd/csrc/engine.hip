@@ -1,33 +1,59 @@
 // Static-plan executor for the reference's feature-extractor / classifier nets:
 //   [conv (any square kernel / stride / pad) (+BatchNorm2d) (+ReLU) (+max-pool)]* -> [(Dropout) Linear (+ReLU)]*
 // i.e. VGGSlim and its _BN / _DROP variants (models/VGGSlim.py:27-76) and torchvision's AlexNet (models/net.py:96-125).
-// 3x3 stride-1 pad-1 layers take the conv3x3.hip fast path (fused ReLU + 2x2 pool forward, fused un-pool first-layer
-// weight gradient, one deferred reduction launch for all weight-gradient slabs); everything else runs through the
-// general kernels (conv2d.hip, pool.hip, bn.hip).  Side inputs per layer: dropout mask rows, an extra gradient for
-// side branches (EBLL's code layers), BatchNorm running buffers.
+// 3x3 stride-1 pad-1 layers take the conv3x3.hip fast path (fused ReLU + 2x2 pool forward, fused un-pool first-layer weight gradient, one
+// deferred reduction launch for all weight-gradient slabs); everything else runs through the general kernels (conv2d.hip, pool.hip,
+// bn.hip).  Side inputs per layer: dropout mask rows, an extra gradient for side branches (EBLL's code layers), BatchNorm running buffers.
 //
-// The reference trains through nn.Sequential + autograd, one Python dispatch per op per batch
-// (EWC/train_EWC.py:181-189).  At N=200 a small_VGG9 step is < 1 ms of MFMA work, so the op
-// sequence is planned once and every forward / loss / backward pass is ONE call that enqueues
-// ~35 kernels on the caller's stream with all ReLU backward passes fused into the producing
-// backward-data kernels.  The plan holds only shapes and offsets; parameters, gradients and
-// the activation workspace are caller-owned device memory (torch allocations).
+// The reference trains through nn.Sequential + autograd, one Python dispatch per op per batch (EWC/train_EWC.py:181-189).  At N=200 a
+// small_VGG9 step is < 1.5 ms of MFMA work, so the op sequence is planned once and every forward / loss / backward pass is ONE call that
+// enqueues its launches (17 for a small_VGG9 loss step) on the caller's stream with all ReLU backward passes fused into the
+// producing backward-data kernels.  The plan holds only shapes and offsets; parameters, gradients and the activation workspace are
+// caller-owned device memory (torch allocations).  clhip_net_create decides ONCE what every layer runs (choose_paths); the passes
+// launch from one place per kind of launch (launch_conv_fwd, launch_conv_bwd_data, launch_wgrad, conv_layer's one_grid).
 #include <vector>
 #include <cstdlib>
+#include <memory>
 #include <new>
 #include "common.hpp"
 
 namespace {
 
+// the kernel of a conv layer's forward or backward-data launch
+enum class Conv : unsigned char {
+    None,       // no launch (backward-data of layer 0)
+    Direct3,    // direct f32 3x3 (conv3x3.hip)
+    Wino,       // Winograd F(2x2,3x3) (wino.hip), weights transformed per pass
+    Bs3,        // 3x3 on the bf16 matrix cores with split fp32 operands (bsconv.hip), weight image built per pass
+    Bs5,        // 5x5 / stride 1 / padding 2 on the same (bsconv.hip)
+    S2d,        // strided first layer through space-to-depth + the dense 3x3 kernels (s2dconv.hip); forward only
+    Gemm,       // general gather-GEMM (conv2d.hip)
+};
+// weights prepared once per pass for one direction of a layer (wino_prepare / the first layer's merged grid)
+enum class Img : unsigned char { None, WinoU, Bs3, Bs5 };
+struct WeightImage { Img kind; size_t off; };       // off: bytes into the plan's image region (off_wino)
+// weight-gradient candidates of a conv layer, tried in this order (launch_wgrad); a kernel may decline a call at run time
+enum : unsigned {
+    WG_BS = 1,      // bf16-split slabs (bswgrad.hip), deferred reduction
+    WG_WINO = 2,    // Winograd slabs (wino.hip), deferred reduction
+    WG_3X3 = 4,     // direct 3x3 kernel: slabs under the deferred reduction, else reduced right away (without it: the gather-GEMM)
+    WG_BS5 = 8,     // 5x5 bf16-split (bswgrad5.hip; slabs in the plan's scratch)
+    WG_S2D = 16,    // space-to-depth frames of the forward pass (s2dconv.hip)
+};
+
 struct LayerPlan {
-    int type;              // 0 conv3x3, 1 fc
+    int type;              // 0 conv, 1 fc
     int cin, cout, relu, pool;
     long w_off, b_off;     // float offsets into the parameter / gradient arenas
     int h, w;              // conv: input spatial size
-    int ks, st, pd;        // conv kernel / stride / pad (3,1,1 = the conv3x3.hip fast path)
+    int ks, st, pd;        // conv kernel / stride / pad
     int oh, ow;            // conv output size
-    int pk, ps;            // pool window / stride (2,2 = pool.hip's 2-bit fast path)
+    int pk, ps;            // pool window / stride
     int ph, pw;            // pooled size
+    bool vgg;              // 3x3 / stride 1 / pad 1: the conv3x3.hip / wino.hip / bsconv.hip fast paths
+    bool pool22;           // pooled with a 2x2 stride-2 window (pool.hip's 2-bit fast path, the fused un-pooling kernels)
+    bool fused_pool;       // conv + ReLU + 2x2 pool go out as ONE forward launch that marks dead windows in the arg-max bytes: the
+                           // next layer's backward-data needs no ReLU mask (CLHIP_POOL_DEAD, common.hpp)
     size_t in_elems, out_elems, pool_elems;   // per image
     size_t act_off;        // float offset of this layer's OUTPUT (post-ReLU, pre-pool) in ws
     size_t pool_off;       // float offset of pooled output
@@ -37,17 +63,12 @@ struct LayerPlan {
     size_t z_off;          // bn: float offset of the convolution output (pre-BatchNorm) in ws
     size_t stat_off;       // bn: float offset of save_mean[cout], save_invstd[cout]
     float* rmean; float* rvar; float bn_momentum, bn_eps;
-    size_t wino_uf, wino_ud;     // byte offsets of this layer's transformed weights (forward / backward-data) in the plan's Winograd region
-    int wino_f, wino_d, wino_w;  // forward / backward-data / weight gradient through Winograd F(2x2,3x3) (wino.hip) instead of the direct kernels
-    int bs5_f, bs5_d;            // 5 x 5 layers: forward / backward-data on the bf16-split kernel (image offsets in wino_uf / wino_ud)
-    int bs5_w;                   // ... and their weight gradient (bswgrad5.hip; slabs in the plan's scratch)
-    int bs_f, bs_d;              // ... forward / backward-data on the bf16 matrix cores with split fp32 operands (bsconv.hip): wino_f / wino_d
-                                 // are set as well (the layer takes the prepared-weights path) and wino_uf / wino_ud hold its weight IMAGE
-    int bs_w;                  // weight gradient on the bf16-split kernel (bswgrad.hip) instead of the Winograd / direct f32 kernels
-    int s2d;                   // strided first layer through space-to-depth + the dense 3x3 kernels (s2dconv.hip); frames at s2d_off
-    size_t s2d_off, s2d_bytes;
-    int wg3;                   // weight gradient on the 3x3 kernel (else the general gather-GEMM)
-    size_t wg_off, wg_bytes;   // this layer's own weight-gradient slabs (3x3 layers; reduced for all layers at once)
+    Conv fwd, bwd;               // forward / backward-data kernel
+    WeightImage img_f, img_d;    // ... and the prepared weights it reads
+    unsigned wg;                 // WG_* candidates of the weight gradient
+    size_t wg_off, wg_bytes;     // this layer's own weight-gradient slabs (WG_BS / WG_WINO / WG_3X3; reduced for all layers at once)
+    size_t s2d_off, s2d_bytes;   // Conv::S2d: this layer's frames in the plan's space-to-depth region
+    size_t scratch_need;         // the most any of this layer's launches asks of the plan's shared scratch
     const float* extra_grad;   // added to the gradient w.r.t. this layer's input (side branches: clhip_net_set_input_grad)
     const float* drop;     // dropout mask applied to this layer's INPUT (NULL = none); see clhip_net_set_dropout
     long drop_stride;      // floats between the mask rows of consecutive samples (0 = one row shared by the batch)
@@ -57,14 +78,6 @@ struct LayerPlan {
 
 constexpr long long WINO_MIN_UNITS = 640;
 constexpr long long WINO16_MIN_UNITS = 384;      // waves of the 8 x 8 variant (wino.hip, wino_conv16_kernel)
-// CLHIP_WINO=0 keeps every layer on the direct kernels (A/B measurements, triage)
-static bool wino_small_wgrad() { return true; }      // (layers with few stages per block: wino_wgrad_ps_kernel, wino.hip)
-
-static bool wino_enabled() {
-    const char* e = std::getenv("CLHIP_WINO");
-    return !(e && e[0] == '0');
-}
-
 constexpr unsigned PROBE_RING = 64;
 #ifndef CLHIP_EDGE_GRIDS_DEFAULT
 #define CLHIP_EDGE_GRIDS_DEFAULT 1
@@ -73,46 +86,57 @@ constexpr unsigned PROBE_RING = 64;
 #define CLHIP_OVERLAP_DEFAULT 0
 #endif
 
+// The environment switches of the executor, all read while a plan is created.
+bool env_starts(const char* name, char c) { const char* e = std::getenv(name); return e && e[0] == c; }
+bool wino_enabled() { return !env_starts("CLHIP_WINO", '0'); }           // =0: every layer off the Winograd kernels (A/B measurements, triage)
+bool bs5_wgrad_enabled() { return !env_starts("CLHIP_BS_WGRAD", '0'); }  // =0: no bf16-split weight gradient on the 5x5 layers
+bool s2d_enabled() { return env_starts("CLHIP_S2D", '1'); }              // =1: a strided first layer over phase planes (choose_paths)
+bool fc_tail_enabled() { return !env_starts("CLHIP_FC_TAIL", '0'); }     // =0: per-layer classifier launches (the bitwise reference of the fused tail)
+// CLHIP_WGRAD_OVERLAP=1 / 2 (make_resources), CLHIP_EDGE_GRIDS=0 / 1 / 2 (NetPlan::edge_grids)
+int overlap_mode() { return env_starts("CLHIP_WGRAD_OVERLAP", '1') ? 1 : env_starts("CLHIP_WGRAD_OVERLAP", '2') ? 2 : CLHIP_OVERLAP_DEFAULT; }
+int edge_grids_mode() {
+    const char* e = std::getenv("CLHIP_EDGE_GRIDS");
+    return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : CLHIP_EDGE_GRIDS_DEFAULT;
+}
+
 struct NetPlan {
     std::vector<LayerPlan> layers;
     int max_batch, in_c, in_h, in_w, n_classes;
     size_t in_elems;
-    size_t acts_floats;      // saved activations
-    size_t idx_bytes;
-    size_t grad_floats;      // one ping-pong gradient buffer
     size_t scratch_bytes;    // wgrad / fc split-K scratch
-    size_t wino_bytes;       // transformed weights of the layer in flight (Winograd path)
+    size_t wino_bytes;       // prepared weights (Winograd U, bf16-split images) of every layer: one region, filled once per pass
     size_t off_wino;
-    size_t off_s2d;          // frames of the space-to-depth first layer (its own region: the phase planes of the forward pass feed the
+    size_t off_s2d;         // frames of the space-to-depth first layer (its own region: the phase planes of the forward pass feed the
     int s2d_fresh_n;         // weight gradient of the same pass; s2d_fresh_n = the batch they were made for, 0 = stale)
     size_t total_bytes;
     // derived offsets (bytes) inside ws
     size_t off_acts, off_idx, off_g0, off_g1, off_scratch, off_dlogits, off_loss, off_fcdz, off_wg;
-    int training;            // BatchNorm: batch statistics (1) or running statistics (0)
-    int n_wg;                // 3x3 conv layers with deferred slab reduction (0: every layer reduces right away)
+    int training = 1;        // BatchNorm: batch statistics (1) or running statistics (0)
+    int n_wg;                // conv layers with slabs of their own under the deferred reduction (0: every layer reduces right away)
     // classifier = trailing Linear layers [fc_first, end): fused into three launches when it fits fc_chain.hip
     int fc_first;
     bool fc_fused;
     clhip_fc_chain chain;
-    // layers fc_first+1 .. end forward + cross-entropy + backward-data down to dz(h1) in one launch (fc_tail_kernel); the
-    // arrival counter of its last-workgroup reduction is the plan's own 4 bytes of device memory (zero between launches),
-    // so a plan must not run on two streams at once (it never could: the activations live in one workspace)
+    size_t fcdz_floats;      // dz slots of the hidden Linear layers
     // measurement probe (clhip_net_probe): HIP events around the forward launch(es) of one layer, a ring of PROBE_RING
     // pairs so that recording never waits for the GPU
-    int probe_layer;
+    int probe_layer = -1;
     int probe_kind;          // 0 forward, 1 backward-data, 2 weight-gradient launch(es) of probe_layer
     unsigned probe_count;
     std::vector<hipEvent_t> probe_ev;
+    // layers fc_first+1 .. end forward + cross-entropy + backward-data down to dz(h1) in one launch (fc_tail_kernel); the
+    // arrival counter of its last-workgroup reduction is the plan's own 4 bytes of device memory (zero between launches),
+    // so a plan must not run on two streams at once (it never could: the activations live in one workspace)
     bool fc_tail, no_combo;
     unsigned* tail_counter;
     size_t off_rows;
-    // backward (optional, CLHIP_WGRAD_OVERLAP=1): the weight-gradient launches of the conv layers run on a side stream
-    // next to the backward-data launch of the same layer (both only read dy)
     // CLHIP_EDGE_GRIDS (default 1): the prepared-weights launch of a pass runs as blocks of the first layer's forward grid where that
     // layer is on conv3x3_c3w64_relu_pool_kernel (net_forward_impl).  0: the launch of its own (the bitwise A/B reference);
     // 1 / 2: weight blocks at the end / at the front of the merged grid (both measured, DESIGN 9: the end is the faster side)
     int edge_grids;
     unsigned edge_count;     // merged launches issued so far (clhip_net_edge_grid_count: tests tell the merged grid from its fallback)
+    // backward (optional, CLHIP_WGRAD_OVERLAP): the weight-gradient launches of the conv layers run on a side stream
+    // next to the backward-data launch of the same layer (both only read dy)
     bool overlap;
     int overlap_mode;        // 0 off, 1 every conv layer (CLHIP_WGRAD_OVERLAP=1), 2 only layers whose launches under-fill the chip
     hipStream_t side;
@@ -127,6 +151,7 @@ struct NetPlan {
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline size_t max_of(size_t a, size_t b) { return a > b ? a : b; }
 
 // h[n][f] *= mask[n * stride + f]: nn.Dropout in training mode with a caller-drawn mask (already divided by the
 // retain probability), or GEM's one-row-per-observe masks (stride 0).  HBM-bound, in place.
@@ -169,6 +194,720 @@ int drop_scale(float* h, const float* mask, long stride, size_t feat, int N, hip
     return 0;
 }
 
+// clhip_net_create in pieces: geometry, kernel choice, arena layout (with the classifier chain), runtime resources.
+// Shapes of every layer from the descriptors; CLHIP_EINVAL for a net the plan does not cover
+int plan_geometry(NetPlan& p, const clhip_layer_desc* descs, int n_layers) {
+    int c = p.in_c, h = p.in_h, w = p.in_w;
+    size_t feat = p.in_elems;
+    bool seen_fc = false;
+    for (int i = 0; i < n_layers; ++i) {
+        const clhip_layer_desc& d = descs[i];
+        LayerPlan L{};
+        L.type = d.type; L.cin = d.cin; L.cout = d.cout; L.relu = d.relu; L.pool = d.pool; L.w_off = d.w_off; L.b_off = d.b_off;
+        if (L.type == 0) {
+            if (seen_fc || L.cin != c) return CLHIP_EINVAL;
+            L.h = h; L.w = w;
+            L.ks = d.ksize > 0 ? d.ksize : 3;
+            L.st = d.ksize > 0 ? d.stride : 1;
+            L.pd = d.ksize > 0 ? d.pad : 1;
+            if (L.st < 1 || L.pd < 0) return CLHIP_EINVAL;
+            L.oh = (h + 2 * L.pd - L.ks) / L.st + 1; L.ow = (w + 2 * L.pd - L.ks) / L.st + 1;
+            if (L.oh <= 0 || L.ow <= 0) return CLHIP_EINVAL;
+            L.vgg = L.ks == 3 && L.st == 1 && L.pd == 1;
+            L.in_elems = (size_t)c * h * w;
+            L.out_elems = (size_t)L.cout * L.oh * L.ow;
+            L.bn = d.bn ? 1 : 0; L.bn_w_off = d.bn_w_off; L.bn_b_off = d.bn_b_off;
+            L.bn_momentum = 0.1f; L.bn_eps = 1e-5f;
+            h = L.oh; w = L.ow;
+            if (L.pool) {
+                L.pk = d.pool_k > 0 ? d.pool_k : 2;
+                L.ps = d.pool_k > 0 ? d.pool_s : 2;
+                L.pool22 = L.pk == 2 && L.ps == 2;
+                if (L.ps < 1 || h < L.pk || w < L.pk) return CLHIP_EINVAL;
+                if (L.pool22 && ((h & 1) || (w & 1))) return CLHIP_EINVAL;
+                L.ph = (h - L.pk) / L.ps + 1; L.pw = (w - L.pk) / L.ps + 1;
+                L.pool_elems = (size_t)L.cout * L.ph * L.pw;
+                h = L.ph; w = L.pw;
+            }
+            L.fused_pool = L.vgg && !L.bn && L.pool22 && L.relu;
+            c = L.cout;
+            feat = (size_t)c * h * w;
+        } else if (L.type == 1) {
+            seen_fc = true;
+            if ((size_t)L.cin != feat) return CLHIP_EINVAL;
+            L.in_elems = feat; L.out_elems = (size_t)L.cout;
+            L.scratch_need = clhip_fc_ws(p.max_batch, L.cin, L.cout);
+            feat = L.out_elems;
+        } else return CLHIP_EINVAL;
+        L.has_drop_buf = (d.has_drop && i > 0) ? 1 : 0;
+        p.layers.push_back(L);
+    }
+    p.n_classes = (int)feat;
+    return 0;
+}
+
+// What conv layer `layer` runs: the kernel of each direction, the weights prepared for it, the weight-gradient candidates and the
+// sizes of the regions they need.  This is the only place that decides; the passes read L.fwd / L.bwd / L.img_* / L.wg.
+void choose_paths(LayerPlan& L, const clhip_layer_desc& d, int layer, int max_batch) {
+    // 3x3 layers whose rows are not 16-byte aligned (AlexNet's 13x13 maps) would take the scalar-staging variant of
+    // the 3x3 weight-gradient kernel with 16x4-pixel tiles (169 of 256 slots): the dense gather-GEMM is 1.8x faster
+    // there (measured 83 vs 46 TFLOP/s)
+    const bool wg3 = L.vgg && (L.w % 4 == 0 || L.cin * 9 <= 32);
+    const size_t s = wg3 ? clhip_conv3x3_bwd_weight_ws(max_batch, L.cin, L.cout, L.h, L.w)
+                         : clhip_conv2d_bwd_weight_ws(max_batch, L.cin, L.h, L.w, L.cout, L.ks, L.ks, L.st, L.pd);
+    L.scratch_need = max_of(s, L.bn ? clhip_bn_ws(L.cout) : 0);
+    if (wg3) { L.wg = WG_3X3; L.wg_bytes = align_up(s, 256); }
+    L.fwd = L.vgg ? Conv::Direct3 : Conv::Gemm;
+    L.bwd = layer == 0 ? Conv::None : L.fwd;
+    if (L.vgg && !L.bn) {
+        // Winograd path: 2.25x fewer matrix instructions, but a wave's work unit is 32 channels x 32 TILES (128 pixels) with 256 accumulator
+        // registers, one wave per SIMD: it needs enough units to fill most of the 1024 SIMDs (measured at N = 200: 64->64 @16x16, 800 units,
+        // 1.26x the direct kernel; 128->128 @8x8, 400 units, 0.8x)
+        const long long tiles = (long long)max_batch * ((L.h + 1) / 2) * ((L.w + 1) / 2);
+        auto units = [&](int kout) { return ((tiles + 31) / 32) * ((kout + 31) / 32); };
+        // (8 x 8 maps: the 16x16x4-MFMA variant has 16-tile units, one image x 32 channels per wave)
+        auto enough = [&](int kout) {
+            if (units(kout) >= WINO_MIN_UNITS) return true;
+            return L.h == 8 && L.w == 8 && (long long)max_batch * ((kout + 31) / 32) >= WINO16_MIN_UNITS;
+        };
+        const bool wino = wino_enabled();
+        if (wino && clhip_internal_wino_ok(L.cin, L.cout, L.h, L.w) && enough(L.cout)) L.fwd = Conv::Wino;
+        if (wino && layer > 0 && clhip_internal_wino_ok(L.cout, L.cin, L.h, L.w) && enough(L.cin)) L.bwd = Conv::Wino;
+        // bf16 matrix cores with split fp32 operands (bsconv.hip) where that path is the faster one (large maps: see clhip_internal_bs_preferred;
+        // CLHIP_BS=0 turns it off, =2 takes it wherever it can run); fused 2x2 pooling only exists on even maps there
+        const bool even = ((L.h | L.w) & 1) == 0;
+        if (clhip_internal_bs_preferred(L.cin, L.cout, L.h, L.w) && (even || !L.pool)) L.fwd = Conv::Bs3;
+        if (layer > 0 && clhip_internal_bs_preferred(L.cout, L.cin, L.h, L.w) && (even || !L.pool)) L.bwd = Conv::Bs3;
+        // Winograd weight gradient (wino.hip picks the tile split by the stages per block itself); its slabs live in this layer's
+        // weight-gradient region (AlexNet's 13x13 layers get one for it: their direct path is the gather-GEMM, which has no slabs)
+        if (wino && clhip_internal_wino_wgrad_ok(L.cin, L.cout, L.h, L.w)) {
+            L.wg |= WG_WINO;
+            L.wg_bytes = max_of(L.wg_bytes, align_up(clhip_internal_wino_wgrad_ws(max_batch, L.cin, L.cout, L.h, L.w), 256));
+        }
+        // ... or on the bf16 matrix cores with split fp32 operands (bswgrad.hip) where that is the faster launch and the layer's
+        // backward is not one merged grid (BackwardPass::one_grid): its slabs live in the same region
+        const bool merged = L.bwd == Conv::Wino && (L.wg & WG_WINO) && L.wg_bytes &&
+                            clhip_internal_wino_pair_shape(max_batch, L.cin, L.cout, L.h, L.w, L.pool22 ? 1 : 0);
+        if (!merged && clhip_internal_bs_wgrad_preferred(L.cin, L.cout, L.h, L.w, L.pool22 ? 1 : 0)) {
+            const size_t bw = clhip_internal_bs_wgrad_ws(max_batch, L.cin, L.cout, L.h, L.w);
+            if (bw && wg3) { L.wg |= WG_BS; L.wg_bytes = max_of(L.wg_bytes, align_up(bw, 256)); }
+        }
+        L.img_f.kind = L.fwd == Conv::Wino ? Img::WinoU : L.fwd == Conv::Bs3 ? Img::Bs3 : Img::None;
+        L.img_d.kind = L.bwd == Conv::Wino ? Img::WinoU : L.bwd == Conv::Bs3 ? Img::Bs3 : Img::None;
+    }
+    // 5 x 5 / stride 1 / padding 2 layers (AlexNet's second convolution) on the bf16-split kernels
+    if (!L.vgg && !L.bn && L.ks == 5 && L.st == 1 && L.pd == 2) {
+        if (clhip_internal_bs5_preferred(L.cin, L.cout, L.h, L.w)) { L.fwd = Conv::Bs5; L.img_f.kind = Img::Bs5; }
+        if (layer > 0 && clhip_internal_bs5_preferred(L.cout, L.cin, L.h, L.w)) { L.bwd = Conv::Bs5; L.img_d.kind = Img::Bs5; }
+        // weight gradient: 372 us against the gather-GEMM's 589 at N = 128 (profiles/r06_x_bswgrad5.txt)
+        const size_t w5 = bs5_wgrad_enabled() ? clhip_internal_bs5_wgrad_ws(max_batch, L.cin, L.cout, L.h, L.w) : 0;
+        if (w5) { L.wg |= WG_BS5; L.scratch_need = max_of(L.scratch_need, w5); }
+    }
+    // AlexNet's 11 x 11 / stride-4 first layer as a dense 3x3 convolution over the 48 phase planes of the padded input
+    // (s2dconv.hip), CLHIP_S2D=1.  Off by default: measured at N = 128 (profiles/r06_l_alexnet_s2d.txt) the dense kernels take
+    // 159 (forward) and 192 us (weight gradient) but building the frames and cropping the output costs 64 + 62 + 45 us more —
+    // 285 / 237 us against the gather-GEMM's 257 / 217; the step 4.72 against 4.69 ms.  First layer only: no backward-data.
+    if (!L.vgg && !L.bn && layer == 0 && !d.has_drop) {
+        const size_t sb = s2d_enabled() ? clhip_conv2d_s2d_ws(max_batch, L.cin, L.h, L.w, L.cout, L.ks, L.st, L.pd) : 0;
+        if (sb) { L.fwd = Conv::S2d; L.wg |= WG_S2D; L.s2d_bytes = align_up(sb, 256); }
+    }
+}
+
+size_t image_bytes(Img kind, int cin, int cout) {
+    return kind == Img::WinoU ? clhip_internal_wino_ws(cin, cout) : kind == Img::Bs3 ? clhip_internal_bs_ws(cin, cout)
+         : kind == Img::Bs5 ? clhip_internal_bs5_ws(cin, cout) : 0;
+}
+
+// trailing Linear layers as one clhip_fc_chain (needs the layers' act_off); fc_fused when fc_chain.hip takes it
+void plan_classifier(NetPlan& p) {
+    const int n_layers = (int)p.layers.size();
+    p.fc_first = n_layers;
+    for (int i = 0; i < n_layers; ++i) if (p.layers[i].type == 1) { p.fc_first = i; break; }
+    const int nfc = n_layers - p.fc_first;
+    if (nfc < 1 || nfc > CLHIP_FC_MAX) return;
+    clhip_fc_chain& ch = p.chain;
+    ch.n = nfc;
+    size_t dzf = 0;
+    for (int l = 0; l < nfc; ++l) {
+        const LayerPlan& L = p.layers[p.fc_first + l];
+        ch.w_off[l] = L.w_off; ch.b_off[l] = L.b_off; ch.din[l] = L.cin; ch.dout[l] = L.cout; ch.relu[l] = L.relu;
+        ch.act_off[l] = L.act_off;
+        ch.dz_off[l] = dzf;
+        if (l < nfc - 1) dzf += (size_t)L.cout * p.max_batch;
+    }
+    p.fcdz_floats = dzf;
+    p.fc_fused = clhip_internal_fc_chain_ok(&ch) != 0;
+}
+
+// offsets of everything in the caller's workspace: per layer inside the regions (layer order), then the regions themselves
+void layout_arena(NetPlan& p) {
+    const size_t N = p.max_batch;
+    size_t acts = 0, idxb = 0, gmax = 0, scratch = 0, imgs = 0, wg_total = 0, s2d_total = 0;
+    for (LayerPlan& L : p.layers) {
+        if (L.bn) {
+            L.z_off = acts; acts += L.out_elems * N;
+            L.stat_off = acts; acts += align_up(2 * (size_t)L.cout, 4);
+        }
+        L.act_off = acts; acts += L.out_elems * N;
+        if (L.type == 0 && L.pool) {
+            L.pool_off = acts; acts += L.pool_elems * N;
+            L.idx_off = idxb; idxb += align_up(L.pool_elems * N, 256);
+        }
+        if (L.has_drop_buf) { L.drop_off = acts; acts += L.in_elems * N; }
+        // own slabs per layer so that ONE launch reduces them all at the end of backward (HBM is plentiful: 288 GB)
+        if (L.wg & (WG_3X3 | WG_WINO)) { L.wg_off = wg_total; wg_total += L.wg_bytes; ++p.n_wg; }
+        // every layer keeps its own prepared weights: ONE launch per pass fills them all
+        if (L.img_f.kind != Img::None) { L.img_f.off = imgs; imgs += align_up(image_bytes(L.img_f.kind, L.cin, L.cout), 256); }
+        if (L.img_d.kind != Img::None) { L.img_d.off = imgs; imgs += align_up(image_bytes(L.img_d.kind, L.cout, L.cin), 256); }
+        if (L.fwd == Conv::S2d) { L.s2d_off = s2d_total; s2d_total += L.s2d_bytes; }
+        scratch = max_of(scratch, L.scratch_need);
+        gmax = max_of(gmax, max_of(L.in_elems, L.out_elems));
+    }
+    p.scratch_bytes = scratch; p.wino_bytes = imgs;
+    plan_classifier(p);
+    size_t off = 0;
+    p.off_acts = off; off += align_up(acts * 4, 256);
+    p.off_idx = off; off += align_up(idxb, 256);
+    p.off_g0 = off; off += align_up(gmax * N * 4, 256);          // two ping-pong gradient buffers
+    p.off_g1 = off; off += align_up(gmax * N * 4, 256);
+    p.off_scratch = off; off += align_up(scratch, 256);
+    p.off_wino = off; off += align_up(imgs, 256);
+    p.off_dlogits = off; off += align_up(N * p.n_classes * 4, 256);
+    p.off_loss = off; off += 256;
+    p.off_fcdz = off;
+    if (p.fc_fused) {
+        off += align_up(p.fcdz_floats * 4 + 256, 256);
+        p.off_rows = off;                        // per-row loss / hit of the fused classifier tail
+        off += align_up(N * 8, 256);
+    }
+    p.off_wg = off;
+    if (p.n_wg < 2 || p.n_wg > CLHIP_WGRAD_JOBS_MAX) p.n_wg = 0;
+    if (p.n_wg) off += align_up(wg_total, 256);
+    p.off_s2d = off; off += s2d_total;
+    p.total_bytes = off;
+}
+
+// side stream and events of the weight-gradient overlap, arrival counter of the fused classifier tail: both need a device, and
+// plans made on a host without one (shape tests) simply stay single-stream / keep the per-layer launches
+void make_resources(NetPlan& p) {
+    // Measured on small_VGG9 (N = 200): 2.59 ms per bench step with the overlap against 2.45 ms without (the two MFMA-bound kernels only
+    // take slots from each other); AlexNet N = 128: 9.65 vs 9.76 ms.  Hence off unless CLHIP_WGRAD_OVERLAP=1; results are identical either
+    // way (same kernels, same order per stream).  Round 2 tried the side stream for the DEEP layers only (planes of 16x16 and smaller at
+    // batch 200: ~400 blocks, 1.5 per CU, SIMD time left unused) with the slab reductions still deferred: 2.125 against 2.076 ms per step —
+    // the event hand-offs and the two launches taking each other's slots cost more than the idle time they fill.  So: off by default;
+    // CLHIP_WGRAD_OVERLAP=1 every conv layer, =2 the deep layers only.
+    const size_t n_layers = p.layers.size();
+    bool any_bn = false;
+    for (const LayerPlan& L : p.layers) any_bn = any_bn || L.bn;
+    p.overlap_mode = overlap_mode();
+    if (p.overlap_mode && !any_bn) {         // BatchNorm backward shares `scratch` with the weight-gradient launches
+        if (hipStreamCreateWithFlags(&p.side, hipStreamNonBlocking) == hipSuccess) {
+            p.overlap = true;
+            p.ev_dy.resize(n_layers); p.ev_wg.resize(n_layers);
+            for (size_t i = 0; i < n_layers && p.overlap; ++i)
+                if (hipEventCreateWithFlags(&p.ev_dy[i], hipEventDisableTiming) != hipSuccess ||
+                    hipEventCreateWithFlags(&p.ev_wg[i], hipEventDisableTiming) != hipSuccess) p.overlap = false;
+        } else { (void)hipGetLastError(); p.side = nullptr; }
+    }
+    p.edge_grids = edge_grids_mode();
+    const bool tail = fc_tail_enabled();
+    p.no_combo = !tail;
+    if (p.fc_fused && tail && clhip_internal_fc_tail_ok(&p.chain) && p.max_batch <= 1024) {
+        if (hipMalloc(reinterpret_cast<void**>(&p.tail_counter), 256) == hipSuccess &&
+            hipMemset(p.tail_counter, 0, 256) == hipSuccess) {
+            p.fc_tail = true;
+        } else {
+            (void)hipGetLastError();
+            if (p.tail_counter) { (void)hipFree(p.tail_counter); p.tail_counter = nullptr; }
+        }
+    }
+}
+
+static bool tail_usable(const NetPlan* p, const float* params, const void* ws, int N) {
+    if (!p->fc_tail) return false;
+    for (size_t i = p->fc_first + 1; i < p->layers.size(); ++i)
+        if (p->layers[i].drop || p->layers[i].extra_grad) return false;
+    const float* acts = reinterpret_cast<const float*>(static_cast<const char*>(ws) + p->off_acts);
+    return aligned16(params + p->chain.w_off[1]) && aligned16(params + p->chain.w_off[2]) && aligned16(acts + p->chain.act_off[0]) &&
+           aligned16(params + p->chain.b_off[0]) && (size_t)N * (p->n_classes | 1) <= 12288;        // the range in which the per-layer path uses softmax_ce_rows_lds_kernel
+}
+
+// what the launches of one pass share: the plan, the caller's buffers and stream, the regions of the workspace
+struct Pass {
+    NetPlan* p; const float* params; int N; void* stream; char* base; float* acts; uint8_t* idx; void* scratch;
+    Pass(NetPlan* plan, const float* prm, int n, void* ws, void* st)
+        : p(plan), params(prm), N(n), stream(st), base(static_cast<char*>(ws)), acts(reinterpret_cast<float*>(base + plan->off_acts)),
+          idx(reinterpret_cast<uint8_t*>(base + plan->off_idx)), scratch(base + plan->off_scratch) {}
+    hipStream_t s() const { return as_stream(stream); }
+    float* image(const WeightImage& im) const { return reinterpret_cast<float*>(base + p->off_wino + im.off); }
+};
+
+// the prepared-weights 3x3 convolution of a layer: Winograd (wino.hip) or bf16-split (bsconv.hip), same arguments
+static int plan_conv_u(Conv kind, int mode, const float* in, const float* U, const float* bias, const float* mask_src, float* out,
+                       uint8_t* pool_idx, int unpool, int N, int Cin, int Cout, int H, int W, int relu, hipStream_t s) {
+    return kind == Conv::Bs3 ? clhip_internal_bs_conv_u(mode, in, U, bias, mask_src, out, pool_idx, unpool, N, Cin, Cout, H, W, relu, s)
+                             : clhip_internal_wino_conv_u(mode, in, U, bias, mask_src, out, pool_idx, unpool, N, Cin, Cout, H, W, relu, s);
+}
+
+// Forward launch of a conv layer: out = conv(in) + bias (+ ReLU).  pool_idx (fused_pool layers): the launch pools 2x2 as well, `out`
+// is the pooled map and pool_idx receives the arg-max bytes; the pre-pool tensor is never materialised.
+static int launch_conv_fwd(const Pass& c, const LayerPlan& L, const float* in, float* out, uint8_t* pool_idx, int relu) {
+    const float* w = c.params + L.w_off; const float* b = c.params + L.b_off;
+    switch (L.fwd) {
+    case Conv::Wino: case Conv::Bs3:
+        return plan_conv_u(L.fwd, 0, in, c.image(L.img_f), b, nullptr, out, pool_idx, 0, c.N, L.cin, L.cout, L.h, L.w, relu, c.s());
+    case Conv::Direct3:
+        return pool_idx ? clhip_conv3x3_relu_pool_fwd(in, w, b, out, pool_idx, c.N, L.cin, L.cout, L.h, L.w, c.stream)
+                        : clhip_conv3x3_fwd(in, w, b, out, c.N, L.cin, L.cout, L.h, L.w, relu, c.stream);
+    case Conv::Bs5:
+        return clhip_internal_bs5_conv_u(0, in, c.image(L.img_f), b, nullptr, out, c.N, L.cin, L.cout, L.h, L.w, relu, c.s());
+    case Conv::S2d:
+        return clhip_conv2d_s2d_fwd(in, w, b, out, c.N, L.cin, L.h, L.w, L.cout, L.ks, L.st, L.pd, relu, c.base + c.p->off_s2d + L.s2d_off,
+                                    L.s2d_bytes, c.stream);
+    default:
+        return clhip_conv2d_fwd(in, w, b, out, c.N, L.cin, L.h, L.w, L.cout, L.ks, L.ks, L.st, L.pd, relu, c.stream);
+    }
+}
+
+// Backward-data launch of a conv layer (> 0): dx = conv^T(dy), masked with (xmask > 0) where xmask is given.  unpool_idx: dy is the
+// POOLED gradient of a 2x2 pool and the kernel rebuilds the un-pooled tile from it and the arg-max bytes while staging
+// (3x3 kernels only; they may decline a shape with CLHIP_ENOTSUP).
+static int launch_conv_bwd_data(const Pass& c, const LayerPlan& L, const float* dy, uint8_t* unpool_idx, const float* xmask, float* dx) {
+    const float* w = c.params + L.w_off;
+    switch (L.bwd) {
+    case Conv::Wino: case Conv::Bs3:
+        return plan_conv_u(L.bwd, 1, dy, c.image(L.img_d), nullptr, xmask, dx, unpool_idx, unpool_idx ? 1 : 0, c.N, L.cout, L.cin, L.h, L.w, 0,
+                           c.s());
+    case Conv::Direct3:
+        return unpool_idx ? clhip_conv3x3_bwd_data_unpool(dy, unpool_idx, w, xmask, dx, c.N, L.cin, L.cout, L.h, L.w, c.stream)
+                          : clhip_conv3x3_bwd_data(dy, w, xmask, dx, c.N, L.cin, L.cout, L.h, L.w, c.stream);
+    case Conv::Bs5:
+        return clhip_internal_bs5_conv_u(1, dy, c.image(L.img_d), nullptr, xmask, dx, c.N, L.cout, L.cin, L.h, L.w, 0, c.s());
+    default:
+        return clhip_conv2d_bwd_data(dy, w, xmask, dx, c.N, L.cin, L.h, L.w, L.cout, L.ks, L.ks, L.st, L.pd, c.stream);
+    }
+}
+
+// Weight gradient of a conv layer from dy on stream `st`, by the layer's candidates in order; a kernel that declines the call
+// (CLHIP_ENOTSUP, CLHIP_ENOSPC: alignment, 2^31 offsets, a fused un-pool on an odd map) hands over to the next.
+// unpool_idx != NULL is the POOLED site (dy is the pooled gradient, see launch_conv_bwd_data): only layers with WG_3X3 come here, the
+// last resort is the un-pooling direct kernel, and a CLHIP_ENOTSUP from the chain sends the caller to the un-pooled site.
+// defer: slabs go to the layer's own region and *slot describes them for the one reduction launch of the pass (*job set).
+static int launch_wgrad(const Pass& c, float* grads, const LayerPlan& L, const float* xin, const float* dy, const uint8_t* unpool_idx, void* st,
+                        bool defer, clhip_wgrad_job* slot, bool* job) {
+    NetPlan* p = c.p;
+    float* dw = grads + L.w_off; float* db = grads + L.b_off;
+    void* slabs = c.base + p->off_wg + L.wg_off;
+    int r;
+    auto declined = [&]() { return r == CLHIP_ENOTSUP || r == CLHIP_ENOSPC; };
+    auto slab_kernel = [&](auto partial) {        // bswgrad.hip / wino.hip: same arguments; false: it declined, the next candidate runs
+        r = partial(xin, dy, unpool_idx, dw, db, c.N, L.cin, L.cout, L.h, L.w, slabs, L.wg_bytes, as_stream(st), slot);
+        if (r == 0) *job = true;
+        return !declined();
+    };
+    // (the un-pooled site asks for a region; the pooled site does not: WG_3X3 layers always own one)
+    const bool region = defer && (unpool_idx || L.wg_bytes);
+    if (region && (L.wg & WG_BS) && slab_kernel(clhip_internal_bs_wgrad_partial)) return r;
+    if (region && (L.wg & WG_WINO) && slab_kernel(clhip_internal_wino_wgrad_partial)) return r;
+    if (defer && (L.wg & WG_3X3)) {
+        *job = true;
+        return clhip_internal_conv3x3_wgrad_partial(xin, dy, unpool_idx, dw, db, c.N, L.cin, L.cout, L.h, L.w, slabs, L.wg_bytes, st, slot);
+    }
+    if (unpool_idx)
+        return clhip_conv3x3_bwd_weight_unpool(xin, dy, unpool_idx, dw, db, c.N, L.cin, L.cout, L.h, L.w, c.scratch, p->scratch_bytes, st);
+    if (L.wg & WG_BS5) {
+        r = clhip_internal_bs5_wgrad(xin, dy, dw, db, c.N, L.cin, L.cout, L.h, L.w, c.scratch, p->scratch_bytes, as_stream(st));
+        if (!declined()) return r;
+    }
+    if (L.wg & WG_S2D) {                  // (the phase planes of this pass's forward are still in the layer's frames)
+        const bool fresh = p->s2d_fresh_n == c.N;
+        p->s2d_fresh_n = 0;
+        return clhip_conv2d_s2d_bwd_weight(fresh ? nullptr : xin, dy, dw, db, c.N, L.cin, L.h, L.w, L.cout, L.ks, L.st, L.pd,
+                                           c.base + p->off_s2d + L.s2d_off, L.s2d_bytes, st);
+    }
+    return (L.wg & WG_3X3) ? clhip_conv3x3_bwd_weight(xin, dy, dw, db, c.N, L.cin, L.cout, L.h, L.w, c.scratch, p->scratch_bytes, st)
+                           : clhip_conv2d_bwd_weight(xin, dy, dw, db, c.N, L.cin, L.h, L.w, L.cout, L.ks, L.ks, L.st, L.pd, c.scratch,
+                                                     p->scratch_bytes, st);
+}
+
+// prepared weights of every layer (forward set, backward-data set, or both): Winograd U images and bf16-split images
+static void wino_collect(const Pass& c, bool fwd, bool bwd, std::vector<clhip_wino_wt>& jobs, std::vector<clhip_wino_wt>& bsjobs) {
+    jobs.reserve(2 * c.p->layers.size());                  // (sized by the plan: a net of any depth gets every transform)
+    bsjobs.reserve(2 * c.p->layers.size());
+    for (const LayerPlan& L : c.p->layers) {
+        auto add = [&](const WeightImage& im, int ko, int ci, int mode) {
+            const float* w = c.params + L.w_off;
+            switch (im.kind) {
+            case Img::WinoU: jobs.push_back(clhip_wino_wt{w, c.image(im), ko, ci, mode, 0}); break;
+            case Img::Bs3: bsjobs.push_back(clhip_wino_wt{w, c.image(im), ko, ci, mode, 0}); break;
+            case Img::Bs5: bsjobs.push_back(clhip_wino_wt{w, c.image(im), ko, ci, mode, 5}); break;
+            case Img::None: break;
+            }
+        };
+        if (fwd) add(L.img_f, L.cout, L.cin, 0);
+        if (bwd) add(L.img_d, L.cin, L.cout, 1);
+    }
+}
+
+static int wino_prepare(const Pass& c, bool fwd, bool bwd) {
+    std::vector<clhip_wino_wt> jobs, bsjobs;
+    wino_collect(c, fwd, bwd, jobs, bsjobs);
+    // (ONE launch for the Winograd U images and the bf16-split images of the pass when they fit one job table: a boundary between two
+    // launches of 5 - 7 us each costs as much as either)
+    return clhip_internal_weight_images(jobs.data(), (int)jobs.size(), bsjobs.data(), (int)bsjobs.size(), c.s());
+}
+
+// Forward pass; activations are kept in ws for a following backward. logits_out (optional) receives a copy of the [N][classes] logits.
+// tail: 0 = every layer; 1 = stop behind the first Linear layer, the caller launches the fused tail itself (loss step);
+// 2 = stop there and finish with the fused tail, forward only.
+static int net_forward_impl(void* handle, const float* params, const float* x, int N, void* ws, float* logits_out,
+                            void* stream, int tail, int* slabs_live = nullptr, bool prep_bwd = false) {
+    NetPlan* p = static_cast<NetPlan*>(handle);
+    if (!p || !params || !x || !ws || N <= 0 || N > p->max_batch) return CLHIP_EINVAL;
+    const Pass c(p, params, N, ws, stream);
+    float* acts = c.acts;
+    // The weight images are first read by layer 1.  Where layer 0 is the fused conv + ReLU + pool launch of a 3-channel image (no
+    // dropout on the input, direct kernel) the jobs ride in that launch's grid (conv3x3.hip, c3w64_relu_pool_wt_kernel),
+    // which declines (CLHIP_ENOTSUP) unless the shape is conv3x3_c3w64_relu_pool_kernel's; every other plan: the launch of its own, here
+    std::vector<clhip_wino_wt> edge_jobs, edge_bsjobs;
+    bool edge = false;
+    if (p->wino_bytes) {
+        const LayerPlan& L0 = p->layers[0];
+        edge = p->edge_grids && L0.fused_pool && L0.fwd == Conv::Direct3 && !L0.drop && L0.cin == 3;
+        if (edge) wino_collect(c, true, prep_bwd, edge_jobs, edge_bsjobs);
+        else if (const int rcw = wino_prepare(c, true, prep_bwd)) return rcw;
+    }
+    const float* cur = x;
+    int rc;
+    const size_t n_run = tail ? (size_t)p->fc_first + 1 : p->layers.size();
+    int live = 0;            // split-K slabs of the first Linear layer left in `scratch` for the fused tail
+    for (size_t li = 0; li < n_run; ++li) {
+        const LayerPlan& L = p->layers[li];
+        float* y = acts + L.act_off;
+        const bool probed = (int)li == p->probe_layer && p->probe_kind == 0 && !p->probe_ev.empty();
+        if (probed) (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING)], c.s());
+        struct ProbeEnd {       // closes the pair when the layer's launches are issued (every exit of the loop body)
+            NetPlan* p; bool on; hipStream_t s;
+            ~ProbeEnd() { if (on) { (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING) + 1], s); ++p->probe_count; } }
+        } probe_end{p, probed, c.s()};
+        if (L.drop && L.has_drop_buf) {       // masked copy: backward reads it as this layer's input, cur stays intact
+            float* dropped = acts + L.drop_off;
+            rc = drop_copy(cur, dropped, L.drop, L.drop_stride, L.in_elems, N, c.s());
+            if (rc) return rc;
+            cur = dropped;
+        } else if (L.drop) {    // li > 0: cur is the previous layer's saved output; masked in place so that backward sees h * m
+            rc = drop_scale(const_cast<float*>(cur), L.drop, L.drop_stride, L.in_elems, N, c.s());
+            if (rc) return rc;
+        }
+        if (L.type == 0) {
+            // fused_pool layers: conv + bias + ReLU + 2x2 max-pool in one launch.  Every other conv layer (general geometry, BatchNorm,
+            // no ReLU, other pool windows): separate conv (+bias, ReLU), BatchNorm and pool kernels
+            float* pl = acts + L.pool_off;
+            uint8_t* pidx = c.idx + L.idx_off;
+            if (li == 0 && edge) {
+                // (a forward probe on layer 0 — clhip_net_probe_kind 0 — times the merged launch, weight blocks included; with
+                //  CLHIP_EDGE_GRIDS=0 the weight-image launch lies in front of the event pair: the layer-0 figure shifts by it)
+                rc = clhip_internal_c3w64_pool_weight_images(cur, params + L.w_off, params + L.b_off, pl, pidx, N, L.cin, L.cout,
+                                                             L.h, L.w, edge_jobs.data(), (int)edge_jobs.size(), edge_bsjobs.data(),
+                                                             (int)edge_bsjobs.size(), p->edge_grids == 2, c.s());
+                if (rc == 0) { ++p->edge_count; cur = pl; continue; }
+                if (rc != CLHIP_ENOTSUP) return rc;
+                rc = clhip_internal_weight_images(edge_jobs.data(), (int)edge_jobs.size(), edge_bsjobs.data(), (int)edge_bsjobs.size(), c.s());
+                if (rc) return rc;
+            }
+            float* zc = L.bn ? acts + L.z_off : L.fused_pool ? pl : y;
+            rc = launch_conv_fwd(c, L, cur, zc, L.fused_pool ? pidx : nullptr, L.bn ? 0 : L.relu);
+            if (rc) return rc;
+            if (L.fwd == Conv::S2d) p->s2d_fresh_n = N;
+            if (L.bn) {
+                float* st = acts + L.stat_off;
+                rc = clhip_bn_fwd(zc, params + L.bn_w_off, params + L.bn_b_off, L.rmean, L.rvar, y, st, st + L.cout, N, L.cout,
+                                  L.oh * L.ow, p->training, L.bn_momentum, L.bn_eps, L.relu, c.scratch, p->scratch_bytes, stream);
+                if (rc) return rc;
+            }
+            cur = L.fused_pool ? pl : y;
+            if (L.pool && !L.fused_pool) {
+                rc = L.pool22 ? clhip_maxpool2_fwd(y, pl, pidx, N * L.cout, L.oh, L.ow, stream)
+                              : clhip_maxpool_fwd(y, pl, pidx, N * L.cout, L.oh, L.ow, L.pk, L.ps, stream);
+                if (rc) return rc;
+                cur = pl;
+            }
+        } else {
+            if (tail && (int)li == p->fc_first) {
+                // the fused tail sums the split-K slabs of this layer itself (no reduction launch)
+                rc = clhip_internal_fc_fwd_partial(cur, params + L.w_off, N, L.cin, L.cout, c.scratch, p->scratch_bytes, &live, c.s());
+                if (rc) return rc;
+            }
+            if (!live) {
+                rc = clhip_fc_fwd(cur, params + L.w_off, params + L.b_off, y, N, L.cin, L.cout, L.relu, c.scratch, p->scratch_bytes, stream);
+                if (rc) return rc;
+            }
+            cur = y;
+        }
+    }
+    if (slabs_live) *slabs_live = live;
+    if (tail == 1) return 0;
+    if (tail == 2) {
+        rc = clhip_internal_fc_tail(&p->chain, params, acts, N, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                    c.base + p->off_rows, p->tail_counter, 0, 0, static_cast<const float*>(c.scratch), live, c.s());
+        if (rc) return rc;
+        cur = acts + p->layers.back().act_off;
+    }
+    if (logits_out) {
+        hipError_t e = hipMemcpyAsync(logits_out, cur, (size_t)N * p->n_classes * sizeof(float), hipMemcpyDeviceToDevice, c.s());
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+// State of one backward pass, layer by layer from the top: the gradient in flight and its ping-pong buffer, the side stream's
+// hand-offs, the slab jobs collected for the one reduction launch at the end.
+struct BackwardPass {
+    const Pass c;
+    NetPlan* const p;
+    float* const grads; const float* const dlogits;
+    float* const g[2]; float* const fcdz;      // the two ping-pong gradient buffers; dz slots of the fused classifier
+    const hipStream_t main_s;
+    const bool ov;           // every conv layer's weight gradient on the side stream: immediate reductions
+    const bool ov_small;     // only the under-filled deep layers; slabs stay deferred
+    const bool defer;        // weight-gradient slabs stay in the layers' regions until one launch reduces them all
+    const float* gin;        // gradient w.r.t. the current layer's output (already ReLU-masked)
+    int gin_buf = -1;        // which of g[0..1] holds gin (-1: dlogits / fcdz)
+    int flip = 0, taken = -1;
+    hipEvent_t last_side = nullptr;                  // last weight-gradient event of the side stream: the caller's stream joins it at the end
+    hipEvent_t pending[2] = {nullptr, nullptr};      // side-stream reader of g[b] that must finish before g[b] is rewritten
+    clhip_wgrad_job jobs[CLHIP_WGRAD_JOBS_MAX];
+    int n_jobs = 0;
+
+    BackwardPass(NetPlan* plan, const float* params, float* grads_, int N, void* ws, const float* dl, void* stream)
+        : c(plan, params, N, ws, stream), p(plan), grads(grads_), dlogits(dl),
+          g{reinterpret_cast<float*>(c.base + plan->off_g0), reinterpret_cast<float*>(c.base + plan->off_g1)},
+          fcdz(reinterpret_cast<float*>(c.base + plan->off_fcdz)), main_s(as_stream(stream)), ov(plan->overlap && plan->overlap_mode == 1),
+          ov_small(plan->overlap && plan->overlap_mode == 2), defer(plan->n_wg > 0 && !ov), gin(dl) {}
+
+    bool side_ok(int layer) const {
+        const LayerPlan& Ls = p->layers[layer];
+        return ov || (ov_small && Ls.type == 0 && (Ls.wg & WG_3X3) && Ls.h * Ls.w <= 256);
+    }
+    // layers whose backward-data and weight gradient can go out as one grid: 3x3 layers on the Winograd kernels with deferred
+    // slabs, a backward-data to compute and nothing to apply to it afterwards (clhip_internal_wino_pair decides on the shape)
+    bool pair_ok(const LayerPlan& L, int layer) const {
+        return defer && L.bwd == Conv::Wino && (L.wg & WG_WINO) && !(L.wg & WG_BS) && L.wg_bytes && !L.drop && !L.extra_grad && !side_ok(layer);
+    }
+    // next ping-pong buffer as an OUTPUT of a main-stream launch
+    float* take() {
+        const int bi = flip;
+        flip ^= 1;
+        if (pending[bi]) { (void)hipStreamWaitEvent(main_s, pending[bi], 0); pending[bi] = nullptr; }
+        taken = bi;
+        return g[bi];
+    }
+    // run `launch(stream)` (a weight-gradient launch reading dy = g[dy_buf]) on the side stream once main has produced dy
+    template <class F> int on_side(int layer, int dy_buf, F&& launch) {
+        if (!side_ok(layer)) return launch(c.stream);
+        hipError_t e = hipEventRecord(p->ev_dy[layer], main_s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(p->side, p->ev_dy[layer], 0);
+        if (e != hipSuccess) return (int)e;
+        const int r = launch((void*)p->side);
+        if (r) return r;
+        e = hipEventRecord(p->ev_wg[layer], p->side);
+        if (e != hipSuccess) return (int)e;
+        last_side = p->ev_wg[layer];
+        if (dy_buf >= 0) pending[dy_buf] = p->ev_wg[layer];
+        return 0;
+    }
+    // what a layer applies to the gradient w.r.t. its input once backward-data has written it: dropout mask, then the side branch
+    int finish_input_grad(const LayerPlan& L, float* gout) {
+        if (L.drop) {
+            const int rc = drop_scale(gout, L.drop, L.drop_stride, L.in_elems, c.N, main_s);
+            if (rc) return rc;
+        }
+        return L.extra_grad ? add_inplace(gout, L.extra_grad, L.in_elems * (size_t)c.N, main_s) : 0;
+    }
+    int fc_layer(int i, const float* xin);
+    int conv_layer(int i, const float* xin, const float* xmask);
+};
+
+int BackwardPass::fc_layer(int i, const float* xin) {
+    const LayerPlan& L = p->layers[i];
+    const int N = c.N;
+    int rc;
+    if (!p->fc_fused) {
+        rc = clhip_fc_bwd_weight(xin, gin, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, c.scratch, p->scratch_bytes, c.stream);
+        if (rc) return rc;
+    }
+    bool combo = false;
+    clhip_fc_chain ch;
+    if (p->fc_fused && i == p->fc_first) {
+        ch = p->chain;       // inputs of the hidden layers: their masked copies where a dropout is active
+        for (int l = 1; l < ch.n; ++l) {
+            const LayerPlan& Ll = p->layers[p->fc_first + l];
+            if (Ll.drop && Ll.has_drop_buf) ch.act_off[l - 1] = Ll.drop_off;
+        }
+    }
+    if (i > 0) {
+        // fused weight gradients (below) read the hidden layers' dz after the chain: keep them in their own slots
+        float* gout;
+        if (p->fc_fused && i > p->fc_first) { gout = fcdz + p->chain.dz_off[i - p->fc_first - 1]; gin_buf = -1; }
+        else { gout = take(); gin_buf = taken; }
+        // mask with (xin > 0): xin is a ReLU (or pooled ReLU) output
+        clhip_gemm_args ga;
+        const int gb = (p->fc_fused && i == p->fc_first && !p->no_combo)
+                           ? clhip_internal_fc_bwd_data_args(gin, c.params + L.w_off, xin, gout, N, L.cin, L.cout, &ga) : 0;
+        if (gb > 0) {
+            // backward-data of the first Linear layer and every Linear layer's dW / db in ONE launch
+            rc = clhip_internal_fc_bwd_combo(&ga, gb, &ch, grads, xin, N, c.acts, dlogits, fcdz, main_s);
+            combo = true;
+        } else {
+            rc = clhip_fc_bwd_data(gin, c.params + L.w_off, xin, gout, N, L.cin, L.cout, c.scratch, p->scratch_bytes, c.stream);
+        }
+        if (rc) return rc;
+        gin = gout;
+        rc = finish_input_grad(L, gout);
+        if (rc) return rc;
+    }
+    if (p->fc_fused && i == p->fc_first && !combo) {
+        // all dz_l are in place: dW_l, db_l of every Linear layer in one launch
+        rc = clhip_internal_fc_chain_wgrad(&ch, grads, xin, N, c.acts, dlogits, fcdz, main_s);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int BackwardPass::conv_layer(int i, const float* xin, const float* xmask) {
+    const LayerPlan& L = p->layers[i];
+    const int N = c.N;
+    uint8_t* const pidx = c.idx + L.idx_off;
+    const float* gy = gin; int gy_buf = gin_buf;       // gradient w.r.t. the conv (+ ReLU) output: gin itself, or its un-pooled form
+    bool wdone = false, ddone = false;
+    float* gout_d = nullptr; int gout_d_buf = -1;      // backward-data output, once taken
+    int rc;
+    // measurement probe around this layer's backward-data / weight-gradient launch(es) (clhip_net_probe_kind)
+    auto probe_on = [&](int kind) { return i == p->probe_layer && p->probe_kind == kind && !p->probe_ev.empty(); };
+    // (events go on the stream the launch is issued on: a weight-gradient launch may run on the side stream, on_side)
+    auto probe_stream = [&](int kind) { return (kind == 2 && side_ok(i)) ? p->side : main_s; };
+    auto probe_begin = [&](int kind) { if (probe_on(kind)) (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING)], probe_stream(kind)); };
+    auto probe_end = [&](int kind) {
+        if (probe_on(kind)) { (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING) + 1], probe_stream(kind)); ++p->probe_count; }
+    };
+    // backward-data and the weight-gradient slabs of this layer as ONE grid (wino.hip, wino_pair_kernel).  A declined shape is no
+    // error: gout_d stays taken and the backward-data launch below reuses it
+    auto one_grid = [&](const float* dy, uint8_t* idx_or_null) {
+        gout_d = take(); gout_d_buf = taken;
+        if (p->probe_kind) probe_begin(p->probe_kind);   // (kinds 1 and 2 both time the merged launch; a forward probe does not)
+        const int r = clhip_internal_wino_pair(dy, idx_or_null, c.image(L.img_d), xmask, gout_d, xin, grads + L.w_off, grads + L.b_off, N, L.cin,
+                                               L.cout, L.h, L.w, c.base + p->off_wg + L.wg_off, L.wg_bytes, main_s, &jobs[n_jobs]);
+        if (r == 0) { wdone = ddone = true; ++n_jobs; if (p->probe_kind) probe_end(p->probe_kind); }
+        return r == CLHIP_ENOTSUP ? 0 : r;
+    };
+    // the weight-gradient chain (launch_wgrad) on the stream of this layer; n_jobs advances when it left slabs for the deferred reduction
+    auto wgrad = [&](const float* dy, uint8_t* idx_or_null, int dy_buf) {
+        bool job = false;
+        probe_begin(2);
+        const int r = on_side(i, dy_buf, [&](void* st) { return launch_wgrad(c, grads, L, xin, dy, idx_or_null, st, defer, &jobs[n_jobs], &job); });
+        if (r == 0) { wdone = true; probe_end(2); if (job) ++n_jobs; }
+        return r;
+    };
+    if (L.vgg && L.pool22 && !L.bn && (L.wg & WG_3X3)) {
+        // fused max-pool backward: weight gradient and backward-data both rebuild the un-pooled gradient tile from
+        // the POOLED gradient + the arg-max codes while staging it, when their kernels support the shape (first
+        // layer: the small-C kernel; others: the 16-byte staging paths).  The 4x larger un-pooled tensor and the
+        // clhip_maxpool2_bwd launch disappear.
+        if (pair_ok(L, i)) {
+            rc = one_grid(gin, pidx);
+            if (rc) return rc;
+        }
+        if (!wdone) {
+            rc = wgrad(gin, pidx, gin_buf);
+            if (rc && rc != CLHIP_ENOTSUP) return rc;      // CLHIP_ENOTSUP: this layer goes the un-pooled way below
+        }
+        if (wdone && !ddone && i > 0 && !L.drop && !L.extra_grad) {
+            if (!gout_d) { gout_d = take(); gout_d_buf = taken; }
+            probe_begin(1);
+            rc = launch_conv_bwd_data(c, L, gin, pidx, xmask, gout_d);
+            if (rc == 0) { ddone = true; probe_end(1); }
+            else if (rc != CLHIP_ENOTSUP) return rc;
+        }
+    }
+    if (L.pool && !(wdone && (i == 0 || ddone))) {      // somebody still needs the un-pooled gradient
+        float* gout = gout_d;
+        if (gout) taken = gout_d_buf; else gout = take();
+        rc = L.pool22 ? clhip_maxpool2_bwd(gin, pidx, gout, N * L.cout, L.oh, L.ow, c.stream)
+                      : clhip_maxpool_bwd(gin, pidx, gout, N * L.cout, L.oh, L.ow, L.pk, L.ps, c.stream);
+        if (rc) return rc;
+        gy = gout; gy_buf = taken;
+        gout_d = nullptr;
+    }
+    if (L.bn) {
+        // dy (w.r.t. the ReLU output) -> dz (w.r.t. the convolution output), in place; dgamma, dbeta
+        const float* st = c.acts + L.stat_off;
+        float* dzb = const_cast<float*>(gy);
+        if (gy_buf < 0) return CLHIP_EINVAL;      // a conv layer's incoming gradient always lives in g[0..1]
+        rc = clhip_bn_bwd(gy, c.acts + L.act_off, c.acts + L.z_off, c.params + L.bn_w_off, st, st + L.cout, dzb, grads + L.bn_w_off,
+                          grads + L.bn_b_off, N, L.cout, L.oh * L.ow, p->training, L.relu, c.scratch, p->scratch_bytes, c.stream);
+        if (rc) return rc;
+    }
+    if (!wdone && !L.pool && !gout_d && pair_ok(L, i)) {
+        rc = one_grid(gy, nullptr);
+        if (rc) return rc;
+    }
+    if (!wdone) {
+        rc = wgrad(gy, nullptr, gy_buf);
+        if (rc) return rc;
+    }
+    if (ddone) { gin = gout_d; gin_buf = gout_d_buf; }
+    if (i == 0 || ddone) return 0;
+    float* gout = gout_d;             // (taken for a merged launch that declined the shape)
+    if (gout) taken = gout_d_buf; else gout = take();
+    probe_begin(1);
+    rc = launch_conv_bwd_data(c, L, gy, nullptr, xmask, gout);
+    if (rc) return rc;
+    probe_end(1);
+    gin = gout; gin_buf = taken;
+    return finish_input_grad(L, gout);
+}
+
+// Backward pass from dlogits[N][classes] (device) through the activations saved by the last clhip_net_forward on the same ws.
+// Writes every parameter gradient into `grads` (same offsets as params; overwritten, not accumulated).
+static int net_backward_impl(void* handle, const float* params, float* grads, const float* x, int N, void* ws,
+                             const float* dlogits, void* stream, bool tail_done, bool wino_ready = false) {
+    NetPlan* p = static_cast<NetPlan*>(handle);
+    if (!p || !params || !grads || !x || !ws || !dlogits || N <= 0 || N > p->max_batch) return CLHIP_EINVAL;
+    BackwardPass b(p, params, grads, N, ws, dlogits, stream);
+    int rc;
+    if (p->wino_bytes && !wino_ready) {           // a backward on its own: the forward of the same call did not transform for it
+        rc = wino_prepare(b.c, false, true);
+        if (rc) return rc;
+    }
+    for (int i = (int)p->layers.size() - 1; i >= 0; --i) {
+        const LayerPlan& L = p->layers[i];
+        // input of layer i = (pooled) output of layer i-1, or the image batch
+        const float* xin = x;
+        // ReLU mask of this layer's backward-data, (input > 0).  Not needed when the input is the pooled output of a fused
+        // conv + ReLU + pool launch: its arg-max bytes mark the windows without a positive maximum (CLHIP_POOL_DEAD) and
+        // the un-pooling consumers of the gradient drop them (common.hpp)
+        bool masked = true;
+        if (i > 0) {
+            const LayerPlan& P = p->layers[i - 1];
+            xin = b.c.acts + ((P.type == 0 && P.pool) ? P.pool_off : P.act_off);
+            if (L.drop && L.has_drop_buf) xin = b.c.acts + L.drop_off;
+            masked = !(L.type == 0 && !L.drop && P.fused_pool);
+        }
+        if (L.type == 1 && tail_done && i > p->fc_first) {
+            // the fused tail has already left dz of this layer's input in its fcdz slot
+            b.gin = b.fcdz + p->chain.dz_off[i - p->fc_first - 1]; b.gin_buf = -1;
+            continue;
+        }
+        rc = L.type == 1 ? b.fc_layer(i, xin) : b.conv_layer(i, xin, masked ? xin : nullptr);
+        if (rc) return rc;
+    }
+    if (b.last_side) {      // join: every slab / gradient of the side stream is complete on the caller's stream from here on
+        hipError_t e = hipStreamWaitEvent(b.main_s, b.last_side, 0);
+        if (e != hipSuccess) return (int)e;
+    }
+    return b.n_jobs ? clhip_internal_wgrad_reduce_multi(b.jobs, b.n_jobs, b.main_s) : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -176,254 +915,17 @@ extern "C" {
 int clhip_net_create(const clhip_layer_desc* descs, int n_layers, int max_batch, int in_c, int in_h, int in_w,
                      void** out_handle) {
     if (!descs || n_layers <= 0 || max_batch <= 0 || !out_handle) return CLHIP_EINVAL;
-    NetPlan* p = new (std::nothrow) NetPlan();
+    std::unique_ptr<NetPlan> p(new (std::nothrow) NetPlan());
     if (!p) return CLHIP_ENOSPC;
     p->max_batch = max_batch; p->in_c = in_c; p->in_h = in_h; p->in_w = in_w;
     p->in_elems = (size_t)in_c * in_h * in_w;
-    int c = in_c, h = in_h, w = in_w;
-    size_t feat = p->in_elems;
-    size_t acts = 0, idxb = 0, gmax = 0, scratch = 0, wg_total = 0, wino_ws = 0, s2d_total = 0;
-    int n_wg = 0;
-    bool seen_fc = false;
-    for (int i = 0; i < n_layers; ++i) {
-        LayerPlan L{};
-        L.type = descs[i].type; L.cin = descs[i].cin; L.cout = descs[i].cout;
-        L.relu = descs[i].relu; L.pool = descs[i].pool; L.w_off = descs[i].w_off; L.b_off = descs[i].b_off;
-        if (L.type == 0) {
-            if (seen_fc || L.cin != c) { delete p; return CLHIP_EINVAL; }
-            L.h = h; L.w = w;
-            L.ks = descs[i].ksize > 0 ? descs[i].ksize : 3;
-            L.st = descs[i].ksize > 0 ? descs[i].stride : 1;
-            L.pd = descs[i].ksize > 0 ? descs[i].pad : 1;
-            if (L.st < 1 || L.pd < 0) { delete p; return CLHIP_EINVAL; }
-            L.oh = (h + 2 * L.pd - L.ks) / L.st + 1; L.ow = (w + 2 * L.pd - L.ks) / L.st + 1;
-            if (L.oh <= 0 || L.ow <= 0) { delete p; return CLHIP_EINVAL; }
-            const bool vgg = L.ks == 3 && L.st == 1 && L.pd == 1;
-            L.in_elems = (size_t)c * h * w;
-            L.out_elems = (size_t)L.cout * L.oh * L.ow;
-            L.bn = descs[i].bn ? 1 : 0; L.bn_w_off = descs[i].bn_w_off; L.bn_b_off = descs[i].bn_b_off;
-            L.bn_momentum = 0.1f; L.bn_eps = 1e-5f;
-            if (L.bn) {
-                L.z_off = acts; acts += L.out_elems * max_batch;
-                L.stat_off = acts; acts += align_up(2 * (size_t)L.cout, 4);
-                const size_t bs = clhip_bn_ws(L.cout);
-                if (bs > scratch) scratch = bs;
-            }
-            L.act_off = acts; acts += L.out_elems * max_batch;
-            int oh = L.oh, ow = L.ow;
-            if (L.pool) {
-                L.pk = descs[i].pool_k > 0 ? descs[i].pool_k : 2;
-                L.ps = descs[i].pool_k > 0 ? descs[i].pool_s : 2;
-                if (L.ps < 1 || oh < L.pk || ow < L.pk) { delete p; return CLHIP_EINVAL; }
-                if (L.pk == 2 && L.ps == 2 && ((oh & 1) || (ow & 1))) { delete p; return CLHIP_EINVAL; }
-                L.ph = (oh - L.pk) / L.ps + 1; L.pw = (ow - L.pk) / L.ps + 1;
-                L.pool_elems = (size_t)L.cout * L.ph * L.pw;
-                L.pool_off = acts; acts += L.pool_elems * max_batch;
-                L.idx_off = idxb; idxb += align_up(L.pool_elems * max_batch, 256);
-                oh = L.ph; ow = L.pw;
-            }
-            // 3x3 layers whose rows are not 16-byte aligned (AlexNet's 13x13 maps) would take the scalar-staging variant of
-            // the 3x3 weight-gradient kernel with 16x4-pixel tiles (169 of 256 slots): the dense gather-GEMM is 1.8x faster
-            // there (measured 83 vs 46 TFLOP/s)
-            L.wg3 = (vgg && (L.w % 4 == 0 || L.cin * 9 <= 32)) ? 1 : 0;
-            size_t s = L.wg3 ? clhip_conv3x3_bwd_weight_ws(max_batch, L.cin, L.cout, L.h, L.w)
-                             : clhip_conv2d_bwd_weight_ws(max_batch, L.cin, L.h, L.w, L.cout, L.ks, L.ks, L.st, L.pd);
-            if (s > scratch) scratch = s;
-            if (L.wg3) { L.wg_off = wg_total; L.wg_bytes = align_up(s, 256); wg_total += L.wg_bytes; ++n_wg; }
-            // Winograd path: 2.25x fewer matrix instructions, but a wave's work unit is 32 channels x 32 TILES (128
-            // pixels) with 256 accumulator registers, one wave per SIMD: it needs enough units to fill most of the 1024 SIMDs
-            // (measured at N = 200: 64->64 @16x16, 800 units, 1.26x the direct kernel; 128->128 @8x8, 400 units, 0.8x)
-            if (vgg && !L.bn) {
-                const long long tiles = (long long)max_batch * ((L.h + 1) / 2) * ((L.w + 1) / 2);
-                auto units = [&](int kout) { return ((tiles + 31) / 32) * ((kout + 31) / 32); };
-                // (8 x 8 maps: the 16x16x4-MFMA variant has 16-tile units, one image x 32 channels per wave)
-                auto enough = [&](int kout) {
-                    if (units(kout) >= WINO_MIN_UNITS) return true;
-                    return L.h == 8 && L.w == 8 && (long long)max_batch * ((kout + 31) / 32) >= WINO16_MIN_UNITS;
-                };
-                const bool wino = wino_enabled();
-                L.wino_f = wino && clhip_internal_wino_ok(L.cin, L.cout, L.h, L.w) && enough(L.cout);
-                L.wino_d = wino && i > 0 && clhip_internal_wino_ok(L.cout, L.cin, L.h, L.w) && enough(L.cin);
-                // bf16 matrix cores with split fp32 operands (bsconv.hip) where that path is the faster one (large maps: see
-                // clhip_internal_bs_preferred; CLHIP_BS=0 turns it off, =2 takes it wherever it can run); fused 2x2 pooling only exists
-                // on even maps there
-                const bool even = ((L.h | L.w) & 1) == 0;
-                L.bs_f = clhip_internal_bs_preferred(L.cin, L.cout, L.h, L.w) && (even || !L.pool);
-                L.bs_d = i > 0 && clhip_internal_bs_preferred(L.cout, L.cin, L.h, L.w) && (even || !L.pool);
-                if (L.bs_f) L.wino_f = 1;
-                if (L.bs_d) L.wino_d = 1;
-                // weight gradient: the reduction (tiles) splits over ~256 blocks per 64x64 (k, c) tile; each block needs a
-                // few 16-tile stages to amortise its 256-accumulator epilogue (measured: 12.5 stages per block 1.44x, 3.1 0.6x)
-                if (wino && clhip_internal_wino_wgrad_ok(L.cin, L.cout, L.h, L.w)) {
-                    const int kc = (L.cin / 64) * (L.cout / 64), splits = (256 + kc - 1) / kc;
-                    const long long stages = (long long)max_batch * (((L.w + 1) / 2 + (L.w >= 16 ? 7 : 3)) / (L.w >= 16 ? 8 : 4)) *
-                                             (((L.h + 1) / 2 + (L.w >= 16 ? 1 : 3)) / (L.w >= 16 ? 2 : 4));
-                    // (fewer stages per block: wino_wgrad_ps_kernel — 32 x 32 tiles, a quarter of the splits — inside the same entry point;
-                    // measured faster than the direct pixel-split kernel on those layers in round 3)
-                    L.wino_w = stages >= 8LL * splits || wino_small_wgrad();
-                    if (L.wino_w) {                   // its slabs live in this layer's weight-gradient region
-                        const size_t ww = clhip_internal_wino_wgrad_ws(max_batch, L.cin, L.cout, L.h, L.w);
-                        if (L.wg3) {
-                            if (ww > L.wg_bytes) { wg_total += align_up(ww, 256) - L.wg_bytes; L.wg_bytes = align_up(ww, 256); }
-                        } else {                      // (AlexNet's 13x13 layers: the direct path is the gather-GEMM, which has no slabs)
-                            L.wg_off = wg_total; L.wg_bytes = align_up(ww, 256); wg_total += L.wg_bytes; ++n_wg;
-                        }
-                    }
-                }
-                // ... or on the bf16 matrix cores with split fp32 operands (bswgrad.hip) where that is the faster launch and the layer's
-                // backward is not one merged grid: its slabs live in the same region
-                {
-                    const bool pooled22 = L.pool && L.pk == 2 && L.ps == 2;
-                    const bool merged = i > 0 && L.wino_w && L.wino_d && !L.bs_d && L.wg_bytes &&
-                                        clhip_internal_wino_pair_shape(max_batch, L.cin, L.cout, L.h, L.w, pooled22 ? 1 : 0);
-                    if (!merged && clhip_internal_bs_wgrad_preferred(L.cin, L.cout, L.h, L.w, pooled22 ? 1 : 0)) {
-                        const size_t bw = clhip_internal_bs_wgrad_ws(max_batch, L.cin, L.cout, L.h, L.w);
-                        if (bw && L.wg3) {
-                            L.bs_w = 1;
-                            if (bw > L.wg_bytes) { wg_total += align_up(bw, 256) - L.wg_bytes; L.wg_bytes = align_up(bw, 256); }
-                        }
-                    }
-                }
-                // every Winograd layer keeps its own transformed weights: ONE transform launch per pass fills them all
-                if (L.wino_f) { L.wino_uf = wino_ws; wino_ws += align_up(L.bs_f ? clhip_internal_bs_ws(L.cin, L.cout) : clhip_internal_wino_ws(L.cin, L.cout), 256); }
-                if (L.wino_d) { L.wino_ud = wino_ws; wino_ws += align_up(L.bs_d ? clhip_internal_bs_ws(L.cout, L.cin) : clhip_internal_wino_ws(L.cout, L.cin), 256); }
-            }
-            // 5 x 5 / stride 1 / padding 2 layers (AlexNet's second convolution) on the bf16-split kernel: bs5_f / bs5_d, images in the
-            // same region
-            if (!vgg && !L.bn && L.ks == 5 && L.st == 1 && L.pd == 2) {
-                L.bs5_f = clhip_internal_bs5_preferred(L.cin, L.cout, L.h, L.w);
-                L.bs5_d = i > 0 && clhip_internal_bs5_preferred(L.cout, L.cin, L.h, L.w);
-                // weight gradient: 372 us against the gather-GEMM's 589 at N = 128 (profiles/r06_x_bswgrad5.txt); CLHIP_BS_WGRAD=0: off
-                {
-                    const char* e = std::getenv("CLHIP_BS_WGRAD");
-                    const size_t w5 = (e && e[0] == '0') ? 0 : clhip_internal_bs5_wgrad_ws(max_batch, L.cin, L.cout, L.h, L.w);
-                    if (w5) { L.bs5_w = 1; if (w5 > scratch) scratch = w5; }
-                }
-                if (L.bs5_f) { L.wino_uf = wino_ws; wino_ws += align_up(clhip_internal_bs5_ws(L.cin, L.cout), 256); }
-                if (L.bs5_d) { L.wino_ud = wino_ws; wino_ws += align_up(clhip_internal_bs5_ws(L.cout, L.cin), 256); }
-            }
-            // AlexNet's 11 x 11 / stride-4 first layer as a dense 3x3 convolution over the 48 phase planes of the padded input
-            // (s2dconv.hip), CLHIP_S2D=1.  Off by default: measured at N = 128 (profiles/r06_l_alexnet_s2d.txt) the dense kernels take
-            // 159 (forward) and 192 us (weight gradient) but building the frames and cropping the output costs 64 + 62 + 45 us more —
-            // 285 / 237 us against the gather-GEMM's 257 / 217; the step 4.72 against 4.69 ms.  First layer only: no backward-data.
-            if (!vgg && !L.bn && i == 0 && !descs[i].has_drop) {
-                const char* e = std::getenv("CLHIP_S2D");
-                const size_t sb = !(e && e[0] == '1') ? 0 : clhip_conv2d_s2d_ws(max_batch, L.cin, L.h, L.w, L.cout, L.ks, L.st, L.pd);
-                if (sb) { L.s2d = 1; L.s2d_off = s2d_total; L.s2d_bytes = align_up(sb, 256); s2d_total += L.s2d_bytes; }
-            }
-            if (L.out_elems > gmax) gmax = L.out_elems;
-            if (L.in_elems > gmax) gmax = L.in_elems;
-            h = oh; w = ow;
-            c = L.cout;
-            feat = (size_t)c * h * w;
-        } else if (L.type == 1) {
-            seen_fc = true;
-            if ((size_t)L.cin != feat) { delete p; return CLHIP_EINVAL; }
-            L.in_elems = feat; L.out_elems = (size_t)L.cout;
-            L.act_off = acts; acts += L.out_elems * max_batch;
-            size_t s = clhip_fc_ws(max_batch, L.cin, L.cout);
-            if (s > scratch) scratch = s;
-            if (L.in_elems > gmax) gmax = L.in_elems;
-            if (L.out_elems > gmax) gmax = L.out_elems;
-            feat = L.out_elems;
-        } else { delete p; return CLHIP_EINVAL; }
-        L.has_drop_buf = (descs[i].has_drop && i > 0) ? 1 : 0;
-        if (L.has_drop_buf) { L.drop_off = acts; acts += L.in_elems * max_batch; }
-        p->layers.push_back(L);
-    }
-    p->n_classes = (int)feat;
-    p->acts_floats = acts; p->idx_bytes = idxb; p->grad_floats = gmax * max_batch; p->scratch_bytes = scratch;
-    size_t off = 0;
-    p->off_acts = off; off += align_up(acts * 4, 256);
-    p->off_idx = off; off += align_up(idxb, 256);
-    p->off_g0 = off; off += align_up(p->grad_floats * 4, 256);
-    p->off_g1 = off; off += align_up(p->grad_floats * 4, 256);
-    p->off_scratch = off; off += align_up(scratch, 256);
-    p->wino_bytes = wino_ws;
-    p->off_wino = off; off += align_up(wino_ws, 256);
-    p->off_dlogits = off; off += align_up((size_t)max_batch * p->n_classes * 4, 256);
-    p->off_loss = off; off += 256;
-    // fused classifier
-    p->fc_first = n_layers;
-    for (int i = 0; i < n_layers; ++i) if (p->layers[i].type == 1) { p->fc_first = i; break; }
-    p->fc_fused = false;
-    p->off_fcdz = off;
-    const int nfc = n_layers - p->fc_first;
-    if (nfc >= 1 && nfc <= CLHIP_FC_MAX) {
-        clhip_fc_chain& ch = p->chain;
-        ch.n = nfc;
-        size_t dzf = 0;
-        for (int l = 0; l < nfc; ++l) {
-            const LayerPlan& L = p->layers[p->fc_first + l];
-            ch.w_off[l] = L.w_off; ch.b_off[l] = L.b_off; ch.din[l] = L.cin; ch.dout[l] = L.cout; ch.relu[l] = L.relu;
-            ch.act_off[l] = L.act_off;
-            ch.dz_off[l] = dzf;
-            if (l < nfc - 1) dzf += (size_t)L.cout * max_batch;
-        }
-        if (clhip_internal_fc_chain_ok(&ch)) {
-            p->fc_fused = true;
-            off += align_up(dzf * 4 + 256, 256);
-            p->off_rows = off;                       // per-row loss / hit of the fused classifier tail
-            off += align_up((size_t)max_batch * 8, 256);
-        }
-    }
-    // own slabs per 3x3 layer so that ONE launch reduces them all at the end of backward (HBM is plentiful: 288 GB)
-    p->off_wg = off;
-    p->n_wg = (n_wg >= 2 && n_wg <= CLHIP_WGRAD_JOBS_MAX) ? n_wg : 0;
-    if (p->n_wg) off += align_up(wg_total, 256);
-    p->off_s2d = off; off += s2d_total;
-    p->s2d_fresh_n = 0;
-    p->total_bytes = off;
-    p->training = 1;
-    p->overlap = false;
-    p->side = nullptr;
-    // Measured on small_VGG9 (N = 200): 2.59 ms per bench step with the overlap against 2.45 ms without (the two
-    // MFMA-bound kernels only take slots from each other); AlexNet N = 128: 9.65 vs 9.76 ms.  Hence off unless
-    // CLHIP_WGRAD_OVERLAP=1; results are identical either way (same kernels, same order per stream).
-    // Round 2 tried the side stream for the DEEP layers only (planes of 16x16 and smaller at batch 200: ~400 blocks, 1.5 per
-    // CU, SIMD time left unused) with the slab reductions still deferred: 2.125 against 2.076 ms per step — the event
-    // hand-offs and the two launches taking each other's slots cost more than the idle time they fill.  So: off by default;
-    // CLHIP_WGRAD_OVERLAP=1 every conv layer, =2 the deep layers only.
-    const char* ov = getenv("CLHIP_WGRAD_OVERLAP");
-    bool any_bn = false;
-    for (const LayerPlan& L : p->layers) any_bn = any_bn || L.bn;
-    p->overlap_mode = (ov && ov[0] == '1') ? 1 : (ov && ov[0] == '2') ? 2 : CLHIP_OVERLAP_DEFAULT;
-    if (p->overlap_mode && !any_bn) {         // BatchNorm backward shares `scratch` with the weight-gradient launches
-        // needs a device: plans made on a host without one (shape tests) simply stay single-stream
-        if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) == hipSuccess) {
-            p->overlap = true;
-            p->ev_dy.resize(n_layers); p->ev_wg.resize(n_layers);
-            for (int i = 0; i < n_layers && p->overlap; ++i)
-                if (hipEventCreateWithFlags(&p->ev_dy[i], hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&p->ev_wg[i], hipEventDisableTiming) != hipSuccess) p->overlap = false;
-        } else {
-            (void)hipGetLastError();
-            p->side = nullptr;
-        }
-    }
-    p->edge_count = 0;
-    const char* eg = getenv("CLHIP_EDGE_GRIDS");
-    p->edge_grids = (eg && eg[0] >= '0' && eg[0] <= '2' && !eg[1]) ? eg[0] - '0' : CLHIP_EDGE_GRIDS_DEFAULT;
-    p->probe_layer = -1;
-    p->probe_kind = 0;
-    p->probe_count = 0;
-    p->fc_tail = false;
-    p->no_combo = false;
-    p->tail_counter = nullptr;
-    const char* tl = getenv("CLHIP_FC_TAIL");      // CLHIP_FC_TAIL=0: per-layer launches (the bitwise reference of the fused tail)
-    if (tl && tl[0] == '0') p->no_combo = true;
-    if (p->fc_fused && !(tl && tl[0] == '0') && clhip_internal_fc_tail_ok(&p->chain) &&
-        max_batch <= 1024) {
-        // needs a device: plans made on a host without one (shape tests) keep the per-layer launches
-        if (hipMalloc(reinterpret_cast<void**>(&p->tail_counter), 256) == hipSuccess &&
-            hipMemset(p->tail_counter, 0, 256) == hipSuccess) {
-            p->fc_tail = true;
-        } else {
-            (void)hipGetLastError();
-            if (p->tail_counter) { (void)hipFree(p->tail_counter); p->tail_counter = nullptr; }
-        }
-    }
-    *out_handle = p;
+    const int rc = plan_geometry(*p, descs, n_layers);
+    if (rc) return rc;
+    for (int i = 0; i < n_layers; ++i)
+        if (p->layers[i].type == 0) choose_paths(p->layers[i], descs[i], i, max_batch);
+    layout_arena(*p);
+    make_resources(*p);
+    *out_handle = p.release();
     return 0;
 }
 
@@ -482,12 +984,6 @@ int clhip_net_layer_paths(void* handle, int layer) {
     NetPlan* p = static_cast<NetPlan*>(handle);
     if (!p || layer < 0 || layer >= (int)p->layers.size()) return CLHIP_EINVAL;
     const LayerPlan& L = p->layers[layer];
-    // (bit 2: the Winograd weight gradient runs only inside the deferred-reduction scheme, net_backward_impl's `defer`; and even
-    // then the kernel may hand single shapes back to the direct path — odd maps with a fused un-pool, > 2^31-byte offsets)
-    const bool defer_capable = p->n_wg > 0 && !(p->overlap && p->overlap_mode == 1);
-    // bits 3 / 4: the forward / backward-data launch is the bf16-split kernel (bsconv.hip), not Winograd (bits 0 / 1 then say
-    // "prepared-weights path")
-    // bit 5: the weight gradient is the bf16-split kernel (bswgrad.hip)
     if (L.type == 1) {
         // Linear layers.  bit 6: the layer's forward and backward-data run inside fc_tail_kernel (the layers behind the first
         // Linear layer of a plan that takes the tail, while none of them has a dropout mask or an extra input gradient set:
@@ -498,8 +994,14 @@ int clhip_net_layer_paths(void* handle, int layer) {
             if (p->layers[i].drop || p->layers[i].extra_grad) tail = false;
         return (tail ? 64 : 0) | ((p->fc_fused && layer >= p->fc_first) ? 128 : 0);
     }
-    return (L.wino_f ? 1 : 0) | (L.wino_d ? 2 : 0) | ((L.wino_w && defer_capable) ? 4 : 0) | ((L.bs_f || L.bs5_f) ? 8 : 0) |
-           ((L.bs_d || L.bs5_d) ? 16 : 0) | ((L.bs_w && defer_capable) ? 32 : 0);
+    // bits 0 / 1: the forward / backward-data launch reads prepared weights of the 3x3 paths (Winograd or bf16-split);
+    // bits 3 / 4: it is a bf16-split kernel (bsconv.hip, 3x3 or 5x5), not Winograd
+    auto dir = [](Conv k) { return (k == Conv::Wino || k == Conv::Bs3 ? 1 : 0) | (k == Conv::Bs3 || k == Conv::Bs5 ? 8 : 0); };
+    // bits 2 / 5: the weight gradient is the Winograd / the bf16-split kernel (bswgrad.hip).  Both run only inside the
+    // deferred-reduction scheme (BackwardPass::defer), and even then the kernel may hand single shapes back to the direct path —
+    // odd maps with a fused un-pool, > 2^31-byte offsets
+    const bool defer_capable = p->n_wg > 0 && !(p->overlap && p->overlap_mode == 1);
+    return dir(L.fwd) | dir(L.bwd) << 1 | (((L.wg & WG_WINO) && defer_capable) ? 4 : 0) | (((L.wg & WG_BS) && defer_capable) ? 32 : 0);
 }
 
 int clhip_net_set_input_grad(void* handle, int layer, const float* extra) {
@@ -572,515 +1074,11 @@ void clhip_net_destroy(void* handle) { delete static_cast<NetPlan*>(handle); }
 size_t clhip_net_workspace_bytes(void* handle) { return handle ? static_cast<NetPlan*>(handle)->total_bytes : 0; }
 int clhip_net_num_classes(void* handle) { return handle ? static_cast<NetPlan*>(handle)->n_classes : 0; }
 
-// Forward pass; activations are kept in ws for a following backward. logits_out (optional) receives
-// a copy of the [N][classes] logits.
-// tail: 0 = every layer; 1 = stop behind the first Linear layer, the caller launches the fused tail itself (loss step);
-// 2 = stop there and finish with the fused tail, forward only.
-static bool tail_usable(const NetPlan* p, const float* params, const void* ws, int N) {
-    if (!p->fc_tail) return false;
-    for (size_t i = p->fc_first + 1; i < p->layers.size(); ++i)
-        if (p->layers[i].drop || p->layers[i].extra_grad) return false;
-    const float* acts = reinterpret_cast<const float*>(static_cast<const char*>(ws) + p->off_acts);
-    return aligned16(params + p->chain.w_off[1]) && aligned16(params + p->chain.w_off[2]) && aligned16(acts + p->chain.act_off[0]) &&
-           aligned16(params + p->chain.b_off[0]) &&
-           (size_t)N * (p->n_classes | 1) <= 12288;        // the range in which the per-layer path uses softmax_ce_rows_lds_kernel
-}
-
-// the prepared-weights convolution of a layer: Winograd (wino.hip) or bf16-split (bsconv.hip), same arguments
-static int plan_conv_u(int bs, int mode, const float* in, const float* U, const float* bias, const float* mask_src, float* out,
-                       uint8_t* pool_idx, int unpool, int N, int Cin, int Cout, int H, int W, int relu, hipStream_t s) {
-    return bs ? clhip_internal_bs_conv_u(mode, in, U, bias, mask_src, out, pool_idx, unpool, N, Cin, Cout, H, W, relu, s)
-              : clhip_internal_wino_conv_u(mode, in, U, bias, mask_src, out, pool_idx, unpool, N, Cin, Cout, H, W, relu, s);
-}
-
-// transformed weights of every Winograd / bf16-split layer (forward set, backward-data set, or both) in one launch each
-static void wino_collect(const NetPlan* p, const float* params, char* base, bool fwd, bool bwd, std::vector<clhip_wino_wt>& jobs,
-                         std::vector<clhip_wino_wt>& bsjobs) {
-    jobs.reserve(2 * p->layers.size());                  // (sized by the plan: a net of any depth gets every transform)
-    bsjobs.reserve(2 * p->layers.size());
-    for (const LayerPlan& L : p->layers) {
-        if (L.type != 0) continue;
-        if (fwd && L.wino_f)
-            (L.bs_f ? bsjobs : jobs).push_back(clhip_wino_wt{params + L.w_off, reinterpret_cast<float*>(base + p->off_wino + L.wino_uf), L.cout, L.cin, 0, 0});
-        if (bwd && L.wino_d)
-            (L.bs_d ? bsjobs : jobs).push_back(clhip_wino_wt{params + L.w_off, reinterpret_cast<float*>(base + p->off_wino + L.wino_ud), L.cin, L.cout, 1, 0});
-        if (fwd && L.bs5_f)
-            bsjobs.push_back(clhip_wino_wt{params + L.w_off, reinterpret_cast<float*>(base + p->off_wino + L.wino_uf), L.cout, L.cin, 0, 5});
-        if (bwd && L.bs5_d)
-            bsjobs.push_back(clhip_wino_wt{params + L.w_off, reinterpret_cast<float*>(base + p->off_wino + L.wino_ud), L.cin, L.cout, 1, 5});
-    }
-}
-
-static int wino_prepare(NetPlan* p, const float* params, char* base, bool fwd, bool bwd, hipStream_t s) {
-    std::vector<clhip_wino_wt> jobs, bsjobs;
-    wino_collect(p, params, base, fwd, bwd, jobs, bsjobs);
-    // (ONE launch for the Winograd U images and the bf16-split images of the pass when they fit one job table: a boundary between two
-    // launches of 5 - 7 us each costs as much as either)
-    return clhip_internal_weight_images(jobs.data(), (int)jobs.size(), bsjobs.data(), (int)bsjobs.size(), s);
-}
-
-static int net_forward_impl(void* handle, const float* params, const float* x, int N, void* ws, float* logits_out,
-                            void* stream, int tail, int* slabs_live = nullptr, bool prep_bwd = false) {
-    NetPlan* p = static_cast<NetPlan*>(handle);
-    if (!p || !params || !x || !ws || N <= 0 || N > p->max_batch) return CLHIP_EINVAL;
-    char* base = static_cast<char*>(ws);
-    float* acts = reinterpret_cast<float*>(base + p->off_acts);
-    uint8_t* idx = reinterpret_cast<uint8_t*>(base + p->off_idx);
-    void* scratch = base + p->off_scratch;
-    // The weight images are first read by layer 1.  Where layer 0 is the fused conv + ReLU + pool launch of a 3-channel image (no
-    // BatchNorm, no dropout on the input, direct kernel) the jobs ride in that launch's grid (conv3x3.hip, c3w64_relu_pool_wt_kernel),
-    // which declines (CLHIP_ENOTSUP) unless the shape is conv3x3_c3w64_relu_pool_kernel's; every other plan: the launch of its own, here
-    std::vector<clhip_wino_wt> edge_jobs, edge_bsjobs;
-    bool edge = false;
-    if (p->wino_bytes) {
-        const LayerPlan& L0 = p->layers[0];
-        edge = p->edge_grids && L0.type == 0 && L0.ks == 3 && L0.st == 1 && L0.pd == 1 && !L0.bn && L0.pool && L0.pk == 2 && L0.ps == 2 &&
-               L0.relu && !L0.wino_f && !L0.drop && L0.cin == 3;
-        if (edge) {
-            wino_collect(p, params, base, true, prep_bwd, edge_jobs, edge_bsjobs);
-        } else {
-            int rcw = wino_prepare(p, params, base, true, prep_bwd, as_stream(stream));
-            if (rcw) return rcw;
-        }
-    }
-    const float* cur = x;
-    int rc;
-    const size_t n_run = tail ? (size_t)p->fc_first + 1 : p->layers.size();
-    int live = 0;            // split-K slabs of the first Linear layer left in `scratch` for the fused tail
-    for (size_t li = 0; li < n_run; ++li) {
-        const LayerPlan& L = p->layers[li];
-        float* y = acts + L.act_off;
-        const bool probed = (int)li == p->probe_layer && p->probe_kind == 0 && !p->probe_ev.empty();
-        if (probed) (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING)], as_stream(stream));
-        struct ProbeEnd {       // closes the pair when the layer's launches are issued (every exit of the loop body)
-            NetPlan* p; bool on; hipStream_t s;
-            ~ProbeEnd() { if (on) { (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING) + 1], s); ++p->probe_count; } }
-        } probe_end{p, probed, as_stream(stream)};
-        if (L.drop && L.has_drop_buf) {       // masked copy: backward reads it as this layer's input, cur stays intact
-            float* dropped = acts + L.drop_off;
-            rc = drop_copy(cur, dropped, L.drop, L.drop_stride, L.in_elems, N, as_stream(stream));
-            if (rc) return rc;
-            cur = dropped;
-        } else if (L.drop) {    // li > 0: cur is the previous layer's saved output; masked in place so that backward sees h * m
-            rc = drop_scale(const_cast<float*>(cur), L.drop, L.drop_stride, L.in_elems, N, as_stream(stream));
-            if (rc) return rc;
-        }
-        const bool vgg = L.type == 0 && L.ks == 3 && L.st == 1 && L.pd == 1;
-        const bool pool22 = L.pool && L.pk == 2 && L.ps == 2;
-        if (L.type == 0 && (L.bn || !(vgg && (!L.pool || pool22)))) {
-            // general geometry (AlexNet) and BatchNorm layers: separate conv (+bias, ReLU), BatchNorm and pool kernels
-            float* zc = L.bn ? acts + L.z_off : y;
-            const int crelu = L.bn ? 0 : L.relu;
-            rc = (vgg && L.wino_f)
-                     ? plan_conv_u(L.bs_f, 0, cur, reinterpret_cast<const float*>(base + p->off_wino + L.wino_uf), params + L.b_off,
-                                                  nullptr, zc, nullptr, 0, N, L.cin, L.cout, L.h, L.w, crelu, as_stream(stream))
-                 : vgg ? clhip_conv3x3_fwd(cur, params + L.w_off, params + L.b_off, zc, N, L.cin, L.cout, L.h, L.w, crelu, stream)
-                 : L.bs5_f ? clhip_internal_bs5_conv_u(0, cur, base + p->off_wino + L.wino_uf, params + L.b_off, nullptr, zc, N, L.cin, L.cout,
-                                                       L.h, L.w, crelu, as_stream(stream))
-                 : L.s2d ? clhip_conv2d_s2d_fwd(cur, params + L.w_off, params + L.b_off, zc, N, L.cin, L.h, L.w, L.cout, L.ks, L.st, L.pd,
-                                                crelu, base + p->off_s2d + L.s2d_off, L.s2d_bytes, stream)
-                     : clhip_conv2d_fwd(cur, params + L.w_off, params + L.b_off, zc, N, L.cin, L.h, L.w, L.cout, L.ks, L.ks, L.st,
-                                        L.pd, crelu, stream);
-            if (rc) return rc;
-            if (L.s2d) p->s2d_fresh_n = N;
-            if (L.bn) {
-                float* st = acts + L.stat_off;
-                rc = clhip_bn_fwd(zc, params + L.bn_w_off, params + L.bn_b_off, L.rmean, L.rvar, y, st, st + L.cout, N, L.cout,
-                                  L.oh * L.ow, p->training, L.bn_momentum, L.bn_eps, L.relu, scratch, p->scratch_bytes, stream);
-                if (rc) return rc;
-            }
-            cur = y;
-            if (L.pool) {
-                float* pl = acts + L.pool_off;
-                rc = pool22 ? clhip_maxpool2_fwd(y, pl, idx + L.idx_off, N * L.cout, L.oh, L.ow, stream)
-                            : clhip_maxpool_fwd(y, pl, idx + L.idx_off, N * L.cout, L.oh, L.ow, L.pk, L.ps, stream);
-                if (rc) return rc;
-                cur = pl;
-            }
-        } else if (L.type == 0) {
-            if (L.pool && L.relu) {
-                // conv + bias + ReLU + max-pool in one kernel; the pre-pool tensor is never materialised
-                float* pl = acts + L.pool_off;
-                if (li == 0 && edge) {
-                    // (a forward probe on layer 0 — clhip_net_probe_kind 0 — times the merged launch, weight blocks included; with
-                    //  CLHIP_EDGE_GRIDS=0 the weight-image launch lies in front of the event pair: the layer-0 figure shifts by it)
-                    rc = clhip_internal_c3w64_pool_weight_images(cur, params + L.w_off, params + L.b_off, pl, idx + L.idx_off, N, L.cin, L.cout,
-                                                                 L.h, L.w, edge_jobs.data(), (int)edge_jobs.size(), edge_bsjobs.data(),
-                                                                 (int)edge_bsjobs.size(), p->edge_grids == 2, as_stream(stream));
-                    if (rc == 0) { ++p->edge_count; cur = pl; continue; }
-                    if (rc != CLHIP_ENOTSUP) return rc;
-                    rc = clhip_internal_weight_images(edge_jobs.data(), (int)edge_jobs.size(), edge_bsjobs.data(), (int)edge_bsjobs.size(),
-                                                      as_stream(stream));
-                    if (rc) return rc;
-                }
-                rc = L.wino_f ? plan_conv_u(L.bs_f, 0, cur, reinterpret_cast<const float*>(base + p->off_wino + L.wino_uf),
-                                                           params + L.b_off, nullptr, pl, idx + L.idx_off, 0, N, L.cin, L.cout, L.h, L.w, 1,
-                                                           as_stream(stream))
-                              : clhip_conv3x3_relu_pool_fwd(cur, params + L.w_off, params + L.b_off, pl, idx + L.idx_off, N, L.cin,
-                                                            L.cout, L.h, L.w, stream);
-                if (rc) return rc;
-                cur = pl;
-            } else {
-                rc = L.wino_f ? plan_conv_u(L.bs_f, 0, cur, reinterpret_cast<const float*>(base + p->off_wino + L.wino_uf),
-                                                           params + L.b_off, nullptr, y, nullptr, 0, N, L.cin, L.cout, L.h, L.w, L.relu,
-                                                           as_stream(stream))
-                              : clhip_conv3x3_fwd(cur, params + L.w_off, params + L.b_off, y, N, L.cin, L.cout, L.h, L.w, L.relu, stream);
-                if (rc) return rc;
-                cur = y;
-                if (L.pool) {
-                    float* pl = acts + L.pool_off;
-                    rc = clhip_maxpool2_fwd(y, pl, idx + L.idx_off, N * L.cout, L.h, L.w, stream);
-                    if (rc) return rc;
-                    cur = pl;
-                }
-            }
-        } else {
-            if (tail && (int)li == p->fc_first) {
-                // the fused tail sums the split-K slabs of this layer itself (no reduction launch)
-                rc = clhip_internal_fc_fwd_partial(cur, params + L.w_off, N, L.cin, L.cout, scratch, p->scratch_bytes, &live,
-                                                   as_stream(stream));
-                if (rc) return rc;
-            }
-            if (!live) {
-                rc = clhip_fc_fwd(cur, params + L.w_off, params + L.b_off, y, N, L.cin, L.cout, L.relu, scratch,
-                                  p->scratch_bytes, stream);
-                if (rc) return rc;
-            }
-            cur = y;
-        }
-    }
-    if (slabs_live) *slabs_live = live;
-    if (tail == 1) return 0;
-    if (tail == 2) {
-        rc = clhip_internal_fc_tail(&p->chain, params, acts, N, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
-                                    base + p->off_rows, p->tail_counter, 0, 0, static_cast<const float*>(scratch), live,
-                                    as_stream(stream));
-        if (rc) return rc;
-        cur = acts + p->layers.back().act_off;
-    }
-    if (logits_out) {
-        hipError_t e = hipMemcpyAsync(logits_out, cur, (size_t)N * p->n_classes * sizeof(float),
-                                      hipMemcpyDeviceToDevice, as_stream(stream));
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
 int clhip_net_forward(void* handle, const float* params, const float* x, int N, void* ws, float* logits_out,
                       void* stream) {
     NetPlan* p = static_cast<NetPlan*>(handle);
     if (!p || !params || !x || !ws || N <= 0 || N > p->max_batch) return CLHIP_EINVAL;
     return net_forward_impl(handle, params, x, N, ws, logits_out, stream, tail_usable(p, params, ws, N) ? 2 : 0);
-}
-
-// Backward pass from dlogits[N][classes] (device) through the activations saved by the last
-// clhip_net_forward on the same ws.  Writes every parameter gradient into `grads` (same offsets
-// as params; overwritten, not accumulated).
-static int net_backward_impl(void* handle, const float* params, float* grads, const float* x, int N, void* ws,
-                             const float* dlogits, void* stream, bool tail_done, bool wino_ready = false) {
-    NetPlan* p = static_cast<NetPlan*>(handle);
-    if (!p || !params || !grads || !x || !ws || !dlogits || N <= 0 || N > p->max_batch) return CLHIP_EINVAL;
-    char* base = static_cast<char*>(ws);
-    float* acts = reinterpret_cast<float*>(base + p->off_acts);
-    uint8_t* idx = reinterpret_cast<uint8_t*>(base + p->off_idx);
-    float* g[2] = {reinterpret_cast<float*>(base + p->off_g0), reinterpret_cast<float*>(base + p->off_g1)};
-    void* scratch = base + p->off_scratch;
-    const float* gin = dlogits;      // gradient w.r.t. the current layer's output (already ReLU-masked)
-    int gin_buf = -1;                // which of g[0..1] holds gin (-1: dlogits / fcdz)
-    int flip = 0;
-    int rc;
-    const int top = (int)p->layers.size() - 1;
-    float* fcdz = reinterpret_cast<float*>(base + p->off_fcdz);
-    hipStream_t main_s = as_stream(stream);
-    if (p->wino_bytes && !wino_ready) {           // a backward on its own: the forward of the same call did not transform for it
-        rc = wino_prepare(p, params, base, false, true, main_s);
-        if (rc) return rc;
-    }
-    const bool ov = p->overlap && p->overlap_mode == 1;          // every layer on the side stream: immediate reductions
-    const bool ov_small = p->overlap && p->overlap_mode == 2;    // only the under-filled deep layers; slabs stay deferred
-    auto side_ok = [&](int layer) {
-        if (ov) return true;
-        const LayerPlan& Ls = p->layers[layer];
-        return ov_small && Ls.type == 0 && Ls.wg3 && Ls.h * Ls.w <= 256;
-    };
-    hipEvent_t pending[2] = {nullptr, nullptr};      // side-stream reader of g[b] that must finish before g[b] is rewritten
-    hipEvent_t last_side = nullptr;
-    int taken = -1;
-    const bool defer = p->n_wg > 0 && !ov;
-    // layers whose backward-data and weight gradient can go out as one grid: plain 3x3 layers on the Winograd kernels with deferred
-    // slabs, a backward-data to compute and nothing to apply to it afterwards (clhip_internal_wino_pair decides on the shape)
-    auto pair_ok = [&](const LayerPlan& Lp, int layer) {
-        return defer && layer > 0 && Lp.type == 0 && Lp.ks == 3 && Lp.st == 1 && Lp.pd == 1 && !Lp.bn && Lp.wino_w && Lp.wino_d &&
-               !Lp.bs_d && !Lp.bs_w && Lp.wg_bytes && !Lp.drop && !Lp.extra_grad && !side_ok(layer);
-    };
-    clhip_wgrad_job jobs[CLHIP_WGRAD_JOBS_MAX];
-    int n_jobs = 0;
-    // next ping-pong buffer as an OUTPUT of a main-stream launch
-    auto take = [&]() -> float* {
-        const int bi = flip;
-        flip ^= 1;
-        if (pending[bi]) { (void)hipStreamWaitEvent(main_s, pending[bi], 0); pending[bi] = nullptr; }
-        taken = bi;
-        return g[bi];
-    };
-    // run `launch(stream)` (a weight-gradient launch reading dy = g[dy_buf]) on the side stream once main has produced dy
-    auto on_side = [&](int layer, int dy_buf, auto&& launch) -> int {
-        if (!side_ok(layer)) return launch(stream);
-        hipError_t e = hipEventRecord(p->ev_dy[layer], main_s);
-        if (e == hipSuccess) e = hipStreamWaitEvent(p->side, p->ev_dy[layer], 0);
-        if (e != hipSuccess) return (int)e;
-        const int r = launch((void*)p->side);
-        if (r) return r;
-        e = hipEventRecord(p->ev_wg[layer], p->side);
-        if (e != hipSuccess) return (int)e;
-        last_side = p->ev_wg[layer];
-        if (dy_buf >= 0) pending[dy_buf] = p->ev_wg[layer];
-        return 0;
-    };
-    for (int i = top; i >= 0; --i) {
-        const LayerPlan& L = p->layers[i];
-        // input of layer i = (pooled) output of layer i-1, or the image batch
-        const float* xin = x;
-        if (i > 0) {
-            const LayerPlan& P = p->layers[i - 1];
-            xin = acts + ((P.type == 0 && P.pool) ? P.pool_off : P.act_off);
-            if (L.drop && L.has_drop_buf) xin = acts + L.drop_off;
-        }
-        // ReLU mask of this layer's backward-data, (input > 0).  Not needed when the input is the pooled output of a fused
-        // conv + ReLU + pool launch: its arg-max bytes mark the windows without a positive maximum (CLHIP_POOL_DEAD) and
-        // the un-pooling consumers of the gradient drop them (common.hpp)
-        const float* xmask = xin;
-        if (i > 0 && L.type == 0 && !L.drop) {
-            const LayerPlan& P = p->layers[i - 1];
-            if (P.type == 0 && !P.bn && P.ks == 3 && P.st == 1 && P.pd == 1 && P.pool && P.pk == 2 && P.ps == 2 && P.relu) xmask = nullptr;
-        }
-        if (L.type == 1 && tail_done && i > p->fc_first) {
-            // the fused tail has already left dz of this layer's input in its fcdz slot
-            gin = fcdz + p->chain.dz_off[i - p->fc_first - 1];
-            gin_buf = -1;
-            continue;
-        }
-        if (L.type == 1) {
-            if (!p->fc_fused) {
-                rc = clhip_fc_bwd_weight(xin, gin, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, scratch, p->scratch_bytes, stream);
-                if (rc) return rc;
-            }
-            bool combo = false;
-            clhip_fc_chain ch;
-            if (p->fc_fused && i == p->fc_first) {
-                ch = p->chain;       // inputs of the hidden layers: their masked copies where a dropout is active
-                for (int l = 1; l < ch.n; ++l) {
-                    const LayerPlan& Ll = p->layers[p->fc_first + l];
-                    if (Ll.drop && Ll.has_drop_buf) ch.act_off[l - 1] = Ll.drop_off;
-                }
-            }
-            if (i > 0) {
-                // fused weight gradients (below) read the hidden layers' dz after the chain: keep them in their own slots
-                float* gout;
-                if (p->fc_fused && i > p->fc_first) { gout = fcdz + p->chain.dz_off[i - p->fc_first - 1]; gin_buf = -1; }
-                else { gout = take(); gin_buf = taken; }
-                // mask with (xin > 0): xin is a ReLU (or pooled ReLU) output
-                clhip_gemm_args ga;
-                const int gb = (p->fc_fused && i == p->fc_first && !p->no_combo)
-                                   ? clhip_internal_fc_bwd_data_args(gin, params + L.w_off, xin, gout, N, L.cin, L.cout, &ga) : 0;
-                if (gb > 0) {
-                    // backward-data of the first Linear layer and every Linear layer's dW / db in ONE launch
-                    rc = clhip_internal_fc_bwd_combo(&ga, gb, &ch, grads, xin, N, acts, dlogits, fcdz, main_s);
-                    combo = true;
-                } else {
-                    rc = clhip_fc_bwd_data(gin, params + L.w_off, xin, gout, N, L.cin, L.cout, scratch, p->scratch_bytes, stream);
-                }
-                if (rc) return rc;
-                gin = gout;
-                if (L.drop) {
-                    rc = drop_scale(gout, L.drop, L.drop_stride, L.in_elems, N, main_s);
-                    if (rc) return rc;
-                }
-                if (L.extra_grad) {
-                    rc = add_inplace(gout, L.extra_grad, L.in_elems * (size_t)N, main_s);
-                    if (rc) return rc;
-                }
-            }
-            if (p->fc_fused && i == p->fc_first && !combo) {
-                // all dz_l are in place: dW_l, db_l of every Linear layer in one launch
-                rc = clhip_internal_fc_chain_wgrad(&ch, grads, xin, N, acts, dlogits, fcdz, main_s);
-                if (rc) return rc;
-            }
-            continue;
-        }
-        const bool vgg = L.ks == 3 && L.st == 1 && L.pd == 1;
-        const bool pool22 = L.pool && L.pk == 2 && L.ps == 2;
-        const float* gy = gin;
-        int gy_buf = gin_buf;
-        bool wdone = false;
-        bool ddone = false;
-        // measurement probe around this layer's backward-data / weight-gradient launch(es) (clhip_net_probe_kind)
-        auto probe_on = [&](int kind) { return i == p->probe_layer && p->probe_kind == kind && !p->probe_ev.empty(); };
-        // (events go on the stream the launch is issued on: a weight-gradient launch may run on the side stream, on_side)
-        auto probe_stream = [&](int kind) { return (kind == 2 && side_ok(i)) ? p->side : main_s; };
-        auto probe_begin = [&](int kind) {
-            if (probe_on(kind)) (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING)], probe_stream(kind));
-        };
-        auto probe_end = [&](int kind) {
-            if (probe_on(kind)) { (void)hipEventRecord(p->probe_ev[2 * (p->probe_count % PROBE_RING) + 1], probe_stream(kind)); ++p->probe_count; }
-        };
-        float* gout_d = nullptr;
-        int gout_d_buf = -1;
-        if (vgg && pool22 && !L.bn && L.wg3) {
-            // fused max-pool backward: weight gradient and backward-data both rebuild the un-pooled gradient tile from
-            // the POOLED gradient + the arg-max codes while staging it, when their kernels support the shape (first
-            // layer: the small-C kernel; others: the 16-byte staging paths).  The 4x larger un-pooled tensor and the
-            // clhip_maxpool2_bwd launch disappear.
-            if (pair_ok(L, i)) {
-                // backward-data and the weight-gradient slabs of this layer as ONE grid (wino.hip, wino_pair_kernel)
-                gout_d = take(); gout_d_buf = taken;
-                if (p->probe_kind) probe_begin(p->probe_kind);   // (kinds 1 and 2 both time the merged launch; a forward probe does not)
-                rc = clhip_internal_wino_pair(gin, idx + L.idx_off, reinterpret_cast<const float*>(base + p->off_wino + L.wino_ud), xmask,
-                                              gout_d, xin, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, L.h, L.w,
-                                              base + p->off_wg + L.wg_off, L.wg_bytes, main_s, &jobs[n_jobs]);
-                if (rc == 0) { wdone = ddone = true; ++n_jobs; if (p->probe_kind) probe_end(p->probe_kind); }
-                else if (rc != CLHIP_ENOTSUP) return rc;
-            }
-            if (!wdone) {
-                probe_begin(2);
-                rc = on_side(i, gin_buf, [&](void* st) {
-                    if (defer && L.bs_w) {
-                        const int r = clhip_internal_bs_wgrad_partial(xin, gin, idx + L.idx_off, grads + L.w_off, grads + L.b_off, N, L.cin,
-                                                                      L.cout, L.h, L.w, base + p->off_wg + L.wg_off, L.wg_bytes, as_stream(st),
-                                                                      &jobs[n_jobs]);
-                        if (r != CLHIP_ENOTSUP && r != CLHIP_ENOSPC) return r;
-                    }
-                    if (defer && L.wino_w) {
-                        const int r = clhip_internal_wino_wgrad_partial(xin, gin, idx + L.idx_off, grads + L.w_off, grads + L.b_off, N, L.cin,
-                                                                        L.cout, L.h, L.w, base + p->off_wg + L.wg_off, L.wg_bytes,
-                                                                        as_stream(st), &jobs[n_jobs]);
-                        if (r != CLHIP_ENOTSUP && r != CLHIP_ENOSPC) return r;
-                    }
-                    if (defer)
-                        return clhip_internal_conv3x3_wgrad_partial(xin, gin, idx + L.idx_off, grads + L.w_off, grads + L.b_off, N, L.cin,
-                                                                    L.cout, L.h, L.w, base + p->off_wg + L.wg_off, L.wg_bytes, st,
-                                                                    &jobs[n_jobs]);
-                    return clhip_conv3x3_bwd_weight_unpool(xin, gin, idx + L.idx_off, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout,
-                                                           L.h, L.w, scratch, p->scratch_bytes, st);
-                });
-                if (rc == 0) { wdone = true; if (defer) ++n_jobs; probe_end(2); }
-                else if (rc != CLHIP_ENOTSUP) return rc;
-            }
-            if (wdone && !ddone && i > 0 && !L.drop && !L.extra_grad) {
-                if (!gout_d) { gout_d = take(); gout_d_buf = taken; }
-                probe_begin(1);
-                rc = L.wino_d ? plan_conv_u(L.bs_d, 1, gin, reinterpret_cast<const float*>(base + p->off_wino + L.wino_ud), nullptr,
-                                                           xmask, gout_d, idx + L.idx_off, 1, N, L.cout, L.cin, L.h, L.w, 0, as_stream(stream))
-                              : clhip_conv3x3_bwd_data_unpool(gin, idx + L.idx_off, params + L.w_off, xmask, gout_d, N, L.cin, L.cout, L.h,
-                                                              L.w, stream);
-                if (rc == 0) { ddone = true; probe_end(1); }
-                else if (rc != CLHIP_ENOTSUP) return rc;
-            }
-        }
-        if (L.pool && !(wdone && (i == 0 || ddone))) {      // somebody still needs the un-pooled gradient
-            float* gout = gout_d;
-            if (gout) taken = gout_d_buf; else gout = take();
-            rc = pool22 ? clhip_maxpool2_bwd(gin, idx + L.idx_off, gout, N * L.cout, L.oh, L.ow, stream)
-                        : clhip_maxpool_bwd(gin, idx + L.idx_off, gout, N * L.cout, L.oh, L.ow, L.pk, L.ps, stream);
-            if (rc) return rc;
-            gy = gout; gy_buf = taken;
-            gout_d = nullptr;
-        }
-        if (L.bn) {
-            // dy (w.r.t. the ReLU output) -> dz (w.r.t. the convolution output), in place; dgamma, dbeta
-            const float* st = acts + L.stat_off;
-            float* dzb = const_cast<float*>(gy);
-            if (gy_buf < 0) return CLHIP_EINVAL;      // a conv layer's incoming gradient always lives in g[0..1]
-            rc = clhip_bn_bwd(gy, acts + L.act_off, acts + L.z_off, params + L.bn_w_off, st, st + L.cout, dzb, grads + L.bn_w_off,
-                              grads + L.bn_b_off, N, L.cout, L.oh * L.ow, p->training, L.relu, scratch, p->scratch_bytes, stream);
-            if (rc) return rc;
-        }
-        if (!wdone && !L.pool && !gout_d && pair_ok(L, i)) {
-            gout_d = take(); gout_d_buf = taken;
-            if (p->probe_kind) probe_begin(p->probe_kind);   // (kinds 1 and 2 both time the merged launch; a forward probe does not)
-            rc = clhip_internal_wino_pair(gy, nullptr, reinterpret_cast<const float*>(base + p->off_wino + L.wino_ud), xmask, gout_d, xin,
-                                          grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, L.h, L.w, base + p->off_wg + L.wg_off,
-                                          L.wg_bytes, main_s, &jobs[n_jobs]);
-            if (rc == 0) { wdone = ddone = true; ++n_jobs; if (p->probe_kind) probe_end(p->probe_kind); }
-            else if (rc != CLHIP_ENOTSUP) return rc;
-        }
-        if (!wdone) {
-            bool job = false;                 // this layer left slabs for the deferred reduction
-            probe_begin(2);
-            rc = on_side(i, gy_buf, [&](void* st) {
-                if (defer && L.bs_w && L.wg_bytes) {
-                    const int r = clhip_internal_bs_wgrad_partial(xin, gy, nullptr, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, L.h, L.w,
-                                                                  base + p->off_wg + L.wg_off, L.wg_bytes, as_stream(st), &jobs[n_jobs]);
-                    if (r == 0) job = true;
-                    if (r != CLHIP_ENOTSUP && r != CLHIP_ENOSPC) return r;
-                }
-                if (defer && L.wino_w && L.wg_bytes) {
-                    const int r = clhip_internal_wino_wgrad_partial(xin, gy, nullptr, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout,
-                                                                    L.h, L.w, base + p->off_wg + L.wg_off, L.wg_bytes, as_stream(st),
-                                                                    &jobs[n_jobs]);
-                    if (r == 0) job = true;
-                    if (r != CLHIP_ENOTSUP && r != CLHIP_ENOSPC) return r;
-                }
-                if (L.wg3 && defer) {
-                    job = true;
-                    return clhip_internal_conv3x3_wgrad_partial(xin, gy, nullptr, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, L.h,
-                                                                L.w, base + p->off_wg + L.wg_off, L.wg_bytes, st, &jobs[n_jobs]);
-                }
-                if (L.bs5_w) {
-                    const int r = clhip_internal_bs5_wgrad(xin, gy, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, L.h, L.w, scratch,
-                                                           p->scratch_bytes, as_stream(st));
-                    if (r != CLHIP_ENOTSUP && r != CLHIP_ENOSPC) return r;
-                }
-                if (L.s2d) {                  // (the phase planes of this pass's forward are still in the layer's frames)
-                    const bool fresh = p->s2d_fresh_n == N;
-                    p->s2d_fresh_n = 0;
-                    return clhip_conv2d_s2d_bwd_weight(fresh ? nullptr : xin, gy, grads + L.w_off, grads + L.b_off, N, L.cin, L.h, L.w, L.cout,
-                                                       L.ks, L.st, L.pd, base + p->off_s2d + L.s2d_off, L.s2d_bytes, st);
-                }
-                return L.wg3 ? clhip_conv3x3_bwd_weight(xin, gy, grads + L.w_off, grads + L.b_off, N, L.cin, L.cout, L.h, L.w, scratch,
-                                                      p->scratch_bytes, st)
-                           : clhip_conv2d_bwd_weight(xin, gy, grads + L.w_off, grads + L.b_off, N, L.cin, L.h, L.w, L.cout, L.ks, L.ks,
-                                                     L.st, L.pd, scratch, p->scratch_bytes, st);
-            });
-            if (rc) return rc;
-            probe_end(2);
-            if (job) ++n_jobs;
-        }
-        if (i > 0 && ddone) {
-            gin = gout_d; gin_buf = gout_d_buf;
-        } else if (i > 0) {
-            float* gout = gout_d;             // (taken for a merged launch that declined the shape)
-            if (gout) taken = gout_d_buf; else gout = take();
-            probe_begin(1);
-            rc = (vgg && L.wino_d)
-                     ? plan_conv_u(L.bs_d, 1, gy, reinterpret_cast<const float*>(base + p->off_wino + L.wino_ud), nullptr, xmask, gout,
-                                                  nullptr, 0, N, L.cout, L.cin, L.h, L.w, 0, as_stream(stream))
-                 : vgg ? clhip_conv3x3_bwd_data(gy, params + L.w_off, xmask, gout, N, L.cin, L.cout, L.h, L.w, stream)
-                 : L.bs5_d ? clhip_internal_bs5_conv_u(1, gy, base + p->off_wino + L.wino_ud, nullptr, xmask, gout, N, L.cout, L.cin, L.h, L.w,
-                                                       0, as_stream(stream))
-                     : clhip_conv2d_bwd_data(gy, params + L.w_off, xmask, gout, N, L.cin, L.h, L.w, L.cout, L.ks, L.ks, L.st, L.pd, stream);
-            if (rc) return rc;
-            probe_end(1);
-            gin = gout; gin_buf = taken;
-            if (L.drop) {
-                rc = drop_scale(gout, L.drop, L.drop_stride, L.in_elems, N, main_s);
-                if (rc) return rc;
-            }
-            if (L.extra_grad) {
-                rc = add_inplace(gout, L.extra_grad, L.in_elems * (size_t)N, main_s);
-                if (rc) return rc;
-            }
-        }
-    }
-    if (last_side) {      // join: every slab / gradient of the side stream is complete on the caller's stream from here on
-        hipError_t e = hipStreamWaitEvent(main_s, last_side, 0);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (n_jobs) {
-        rc = clhip_internal_wgrad_reduce_multi(jobs, n_jobs, main_s);
-        if (rc) return rc;
-    }
-    return 0;
 }
 
 int clhip_net_backward(void* handle, const float* params, float* grads, const float* x, int N, void* ws,
