@@ -43,6 +43,10 @@ class IcarlClass(C.Structure):                     # clhip_icarl_class
     _fields_ = [("row_begin", _i), ("row_end", _i), ("k", _i), ("out_off", _i)]
 
 
+class ReduceJob(C.Structure):                      # clhip_reduce_job
+    _fields_ = [("slabs", _p), ("dw", _p), ("db", _p), ("K", _i), ("C", _i), ("splits", _i), ("taps", _i)]
+
+
 class LayerDesc(C.Structure):
     _fields_ = [("type", _i), ("cin", _i), ("cout", _i), ("relu", _i), ("pool", _i),
                 ("w_off", _l), ("b_off", _l), ("ksize", _i), ("stride", _i), ("pad", _i), ("pool_k", _i), ("pool_s", _i),
@@ -71,6 +75,7 @@ SIGNATURES = {
     "clhip_conv3x3_bs_ws": (_z, [_i, _i]),
     "clhip_conv3x3_bs_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
     "clhip_conv3x3_bs_bwd_data": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "clhip_conv3x3_bs_bwd_data_riders": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _z, C.POINTER(ReduceJob), _i, _i, _i, _p]),
     "clhip_conv3x3_wino_bwd_weight_ws": (_z, [_i, _i, _i, _i, _i]),
     "clhip_conv3x3_wino_bwd_weight": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
     "clhip_conv3x3_wino_bwd_ws": (_z, [_i, _i, _i, _i, _i]),
@@ -154,6 +159,7 @@ SIGNATURES = {
     "clhip_net_layer_pool_idx": (_i, [_p, _i, _p, _p]),
     "clhip_net_prepared_weights": (_i, [_p, _p, _p]),
     "clhip_net_edge_grid_count": (_i, [_p]),
+    "clhip_net_reduce_rider_count": (_i, [_p]),
     "clhip_net_layer_paths": (_i, [_p, _i]),
     "clhip_net_probe_kind": (_i, [_p, _i, _i]),
     "clhip_net_set_input_grad": (_i, [_p, _i, _p]),

@@ -39,6 +39,7 @@
 // Algorithmic FLOPs 2 * 9 * Cin * Cout * H * W * N; issued on the matrix pipe: 6x that, against the 2.5 PFLOP/s dense bf16 peak.
 #include "common.hpp"
 #include "bs_weight.hpp"
+#include "wgrad_reduce.hpp"
 #include <cstdlib>
 
 // Timing-only ablations (tools/experiments; results wrong by design; the product is built with 0): 1 no MFMAs, 2 no weight-operand
@@ -509,6 +510,62 @@ void bs_conv_mixed_kernel(const float* __restrict__ in, const clhip_u32x4* __res
     }
 }
 
+// Backward-data with RIDER blocks: `riders` blocks of the grid reduce weight-gradient slabs that earlier launches of the same stream
+// have finished (the plan executor's deferred reduction, engine.hip) while the other blocks run the convolution — the matrix-bound
+// launch leaves HBM nearly idle, the reduction is nothing but HBM reads.  A rider is exactly wgrad_reduce_multi_kernel's block run
+// in a loop: unit u (64 consecutive elements of one job, wgrad_reduce.hpp) goes to rider u % riders, `partial` lies in the block's
+// staging LDS, one barrier between units because it is reused.  The convolution blocks call bs_conv_body with the block index they
+// have in the launch without riders, so dx, dw and db are bitwise those of the two separate launches
+// (tests/test_gpu_reduce_riders.py).  Nothing waits across blocks.  GA / GB as in bs_conv_mixed_kernel; GB = GA: one geometry.
+// place 1: riders in front of the convolution blocks (what the plan executor takes: the only order that was faster than two launches,
+// profiles/reduce_riders_ab.json); 2: behind them; 3: every stride-th GROUP of 8 blocks is a rider group (block b runs
+// on XCD b % 8: whole groups keep every convolution block on the XCD it has without riders, bs_conv_body's L2 sharing).
+template <class GA, class GB>
+constexpr bool bs_same_geo() { return GA::RW == GB::RW && GA::RH == GB::RH && GA::NI == GB::NI && GA::WM == GB::WM; }
+
+template <class GA, class GB, bool UNPOOL>
+__global__ __launch_bounds__(256, (bs_blocks_per_cu<GA, UNPOOL>() < bs_blocks_per_cu<GB, UNPOOL>() ? bs_blocks_per_cu<GA, UNPOOL>()
+                                                                                                  : bs_blocks_per_cu<GB, UNPOOL>()))
+void bs_conv_riders_kernel(const float* __restrict__ in, const clhip_u32x4* __restrict__ wimg, const float* __restrict__ mask_src,
+                           float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N, int Cin, int Cout, int H, int W, int blocks_a,
+                           int NA, int tiles_xa, int tiles_ya, int npb_a, int tiles_xb, int tiles_yb, int npb_b, int place, int riders,
+                           int stride, RedJobs jobs) {
+    constexpr int LB = 2 * (GA::BUF_BYTES > GB::BUF_BYTES ? GA::BUF_BYTES : GB::BUF_BYTES);
+    static_assert(LB >= (int)(RED_J * RED_EL * sizeof(double)) && RED_THREADS == 256, "a rider is one reduction block inside the host's block");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LB];
+    int b = (int)blockIdx.x, r = -1;
+    if (place == 1) {
+        if (b < riders) r = b; else b -= riders;
+    } else if (place == 3) {
+        const int g = b >> 3, rg = riders >> 3, q = g / stride;
+        if (g - q * stride == stride - 1 && q < rg) r = q * 8 + (b & 7);
+        else { const int before = (g + 1) / stride; b -= 8 * (before < rg ? before : rg); }
+    } else {
+        const int conv_blocks = (int)gridDim.x - riders;
+        if (b >= conv_blocks) r = b - conv_blocks;
+    }
+    if (r >= 0) {
+        double (*partial)[RED_EL] = reinterpret_cast<double (*)[RED_EL]>(lds);
+        const unsigned units = jobs.first[jobs.n];
+        for (unsigned u = (unsigned)r; u < units; u += (unsigned)riders) {
+            wgrad_reduce_unit<RED_EL, RED_J>(jobs, u, partial);
+            __syncthreads();
+        }
+        return;
+    }
+    if (bs_same_geo<GA, GB>() || b < blocks_a) {
+        bs_conv_body<GA, 1, UNPOOL>(lds, b, in, wimg, nullptr, mask_src, out, pool_idx, NA, Cin, Cout, H, W, 0, tiles_xa, tiles_ya, npb_a);
+    } else if constexpr (!bs_same_geo<GA, GB>()) {
+        // (the tensors of images NA .. N - 1, as in bs_conv_mixed_kernel)
+        const size_t in_img = (size_t)Cin * (UNPOOL ? (size_t)(H >> 1) * (W >> 1) : (size_t)H * W);
+        const size_t out_img = (size_t)Cout * H * W;
+        uint8_t* idx_b = pool_idx ? pool_idx + (size_t)NA * in_img : nullptr;
+        bs_conv_body<GB, 1, UNPOOL>(lds, b - blocks_a, in + (size_t)NA * in_img, wimg, nullptr,
+                                    mask_src ? mask_src + (size_t)NA * out_img : nullptr, out + (size_t)NA * out_img, idx_b, N - NA, Cin, Cout,
+                                    H, W, 0, tiles_xb, tiles_yb, npb_b);
+    }
+}
+
 // (A first-layer form of this scheme — 3 -> K, K dimension 27 -> 32, the A operand gathered from a raw fp32 halo tile in LDS and split
 // in registers, weights split once per persistent wave — was built, passed the parity suite and ran 50.9 us against 42 - 45 us for
 // conv3x3_c3w64_relu_pool_kernel on the f32 pipe (profiles/r05_j_conv_layers_small_with_c3.txt): 27 scalar LDS gathers + 88 split
@@ -535,28 +592,41 @@ int bs_launch_geo(const float* in, const clhip_u32x4* wimg, const float* bias, c
 
 // GA = 128-pixel tiles of the 32-wide geometry, GB = its 64-pixel tiles; taken when the launch has whole rounds of GA blocks plus a
 // remainder of at most half a round (CLHIP_BS_MIXED=0: never)
-template <int MODE, bool UNPOOL>
-int bs_launch_mixed32(const float* in, const clhip_u32x4* wimg, const float* bias, const float* mask_src, float* out, uint8_t* pool_idx,
-                      int N, int Cin, int Cout, int H, int W, int relu, hipStream_t s, bool* taken) {
-    using GA = BsGeo<32, 4, 1, 2, 2, 1>;
-    using GB = BsGeo<32, 2, 1, 2, 1, 1>;
-    *taken = false;
+using BsGA32 = BsGeo<32, 4, 1, 2, 2, 1>;
+using BsGB32 = BsGeo<32, 2, 1, 2, 1, 1>;
+struct BsMixed { int blocks_a, NA, txa, tya, npb_a, txb, tyb, npb_b; long long blocks; };
+
+// the two-geometry split of a launch (false: it takes one geometry)
+template <bool UNPOOL>
+bool bs_mixed32_plan(int N, int Cout, int H, int W, BsMixed& m) {
+    using GA = BsGA32;
+    using GB = BsGB32;
     static const int on = bs_env_int("CLHIP_BS_MIXED", 1);
-    if (!on) return 0;
+    if (!on) return false;
     const int kts = (Cout + BS_BN - 1) / BS_BN;
     const long long per_img_a = (long long)((W + GA::RW - 1) / GA::RW) * ((H + GA::RH - 1) / GA::RH);
     const long long slots = 256LL * bs_blocks_per_cu<GA, UNPOOL>();
     const long long total = per_img_a * N * kts, rounds = total / slots, rem = total - rounds * slots;
-    if (rounds < 1 || rem == 0 || 2 * rem > slots) return 0;
+    if (rounds < 1 || rem == 0 || 2 * rem > slots) return false;
     const long long na = rounds * slots / (per_img_a * kts);            // images that fill the whole rounds
-    if (na < 1 || na >= N || na % 8) return 0;                             // (whole groups of 8 pixel tiles: the XCD order of the blocks)
-    const int NA = (int)na;
-    const int txa = (W + GA::RW - 1) / GA::RW, tya = (H + GA::RH - 1) / GA::RH, txb = (W + GB::RW - 1) / GB::RW, tyb = (H + GB::RH - 1) / GB::RH;
-    const long long npb_a = (long long)txa * tya * NA, npb_b = (long long)txb * tyb * (N - NA);
+    if (na < 1 || na >= N || na % 8) return false;                         // (whole groups of 8 pixel tiles: the XCD order of the blocks)
+    m.NA = (int)na;
+    m.txa = (W + GA::RW - 1) / GA::RW; m.tya = (H + GA::RH - 1) / GA::RH; m.txb = (W + GB::RW - 1) / GB::RW; m.tyb = (H + GB::RH - 1) / GB::RH;
+    const long long npb_a = (long long)m.txa * m.tya * m.NA, npb_b = (long long)m.txb * m.tyb * (N - m.NA);
     const long long blocks_a = (npb_a + 7) / 8 * 8 * kts, blocks_b = (npb_b + 7) / 8 * 8 * kts;
-    if (blocks_a + blocks_b > 0x7fffffffLL) return 0;
-    hipLaunchKernelGGL((bs_conv_mixed_kernel<GA, GB, MODE, UNPOOL>), dim3((unsigned)(blocks_a + blocks_b)), dim3(256), 0, s, in, wimg, bias,
-                       mask_src, out, pool_idx, N, Cin, Cout, H, W, relu, (int)blocks_a, NA, txa, tya, (int)npb_a, txb, tyb, (int)npb_b);
+    if (blocks_a + blocks_b > 0x7fffffffLL) return false;
+    m.npb_a = (int)npb_a; m.npb_b = (int)npb_b; m.blocks_a = (int)blocks_a; m.blocks = blocks_a + blocks_b;
+    return true;
+}
+
+template <int MODE, bool UNPOOL>
+int bs_launch_mixed32(const float* in, const clhip_u32x4* wimg, const float* bias, const float* mask_src, float* out, uint8_t* pool_idx,
+                      int N, int Cin, int Cout, int H, int W, int relu, hipStream_t s, bool* taken) {
+    *taken = false;
+    BsMixed m;
+    if (!bs_mixed32_plan<UNPOOL>(N, Cout, H, W, m)) return 0;
+    hipLaunchKernelGGL((bs_conv_mixed_kernel<BsGA32, BsGB32, MODE, UNPOOL>), dim3((unsigned)m.blocks), dim3(256), 0, s, in, wimg, bias,
+                       mask_src, out, pool_idx, N, Cin, Cout, H, W, relu, m.blocks_a, m.NA, m.txa, m.tya, m.npb_a, m.txb, m.tyb, m.npb_b);
     CLHIP_LAUNCH_CHECK();
     *taken = true;
     return 0;
@@ -578,6 +648,48 @@ int bs_launch(const float* in, const clhip_u32x4* wimg, const float* bias, const
     if (W > 8) BS_GO(16, 8, 1, 2, 2, 1);
     BS_GO(8, 8, 2, 2, 2, 1);
 #undef BS_GO
+}
+
+// backward-data with rider blocks (bs_conv_riders_kernel): the geometry choice of bs_launch<1, UNPOOL>, `riders` (a multiple of 8) more blocks
+template <class GA, class GB, bool UNPOOL>
+int bs_launch_riders_geo(const float* in, const clhip_u32x4* wimg, const float* mask_src, float* out, uint8_t* pool_idx, int N, int Cin,
+                         int Cout, int H, int W, const BsMixed& m, const RedJobs& jobs, int place, int riders, hipStream_t s) {
+    const long long total = m.blocks + riders;
+    if (m.blocks <= 0 || total > 0x7fffffffLL) return CLHIP_ENOTSUP;
+    // spread: a rider group after every (stride - 1) groups of convolution blocks; fewer convolution groups than rider groups: behind
+    const int stride = (int)((total / 8) / (riders / 8));
+    if (place == 3 && stride < 2) place = 2;
+    hipLaunchKernelGGL((bs_conv_riders_kernel<GA, GB, UNPOOL>), dim3((unsigned)total), dim3(256), 0, s, in, wimg, mask_src, out, pool_idx, N,
+                       Cin, Cout, H, W, m.blocks_a, m.NA, m.txa, m.tya, m.npb_a, m.txb, m.tyb, m.npb_b, place, riders, stride, jobs);
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+template <class G>
+BsMixed bs_one_geo(int N, int Cout, int H, int W) {
+    BsMixed m{};
+    m.txa = (W + G::RW - 1) / G::RW; m.tya = (H + G::RH - 1) / G::RH; m.NA = N;
+    const long long npb = (long long)m.txa * m.tya * ((N + G::NI - 1) / G::NI);
+    const long long blocks = (npb + 7) / 8 * 8 * ((Cout + BS_BN - 1) / BS_BN);
+    m.blocks = (npb > 0x7fffffffLL || blocks > 0x7fffffffLL) ? 0 : blocks;
+    m.npb_a = (int)npb; m.blocks_a = (int)m.blocks;
+    return m;
+}
+
+template <bool UNPOOL>
+int bs_launch_riders(const float* in, const clhip_u32x4* wimg, const float* mask_src, float* out, uint8_t* pool_idx, int N, int Cin,
+                     int Cout, int H, int W, const RedJobs& jobs, int place, int riders, hipStream_t s) {
+#define BS_RIDE(GA_, GB_, M_) return bs_launch_riders_geo<GA_, GB_, UNPOOL>(in, wimg, mask_src, out, pool_idx, N, Cin, Cout, H, W, M_, jobs, place, riders, s)
+    if (W > 16 && !((H | W) & 1)) {
+        BsMixed m;
+        if (bs_mixed32_plan<UNPOOL>(N, Cout, H, W, m)) BS_RIDE(BsGA32, BsGB32, m);
+    }
+    using G16 = BsGeo<16, 8, 1, 2, 2, 1>;
+    using G8 = BsGeo<8, 8, 2, 2, 2, 1>;
+    if (W > 16) BS_RIDE(BsGA32, BsGA32, bs_one_geo<BsGA32>(N, Cout, H, W));
+    if (W > 8) BS_RIDE(G16, G16, bs_one_geo<G16>(N, Cout, H, W));
+    BS_RIDE(G8, G8, bs_one_geo<G8>(N, Cout, H, W));
+#undef BS_RIDE
 }
 
 // 5 x 5 taps (stride 1, padding 2; no fused pooling: AlexNet pools 3 x 3 / 2)
@@ -673,6 +785,31 @@ int clhip_internal_bs_conv_u(int mode, const float* in, const void* wimg, const 
     return bs_launch<1, false>(in, img, nullptr, mask_src, out, nullptr, N, Cin, Cout, H, W, 0, s);
 }
 
+// backward-data with the reduction of jobs[0 .. n_jobs) in rider blocks of the same launch (common.hpp); the convolution's arguments
+// as clhip_internal_bs_conv_u(1, ...) and the same refusals for them; CLHIP_ENOTSUP: jobs / riders this launch does not carry
+int clhip_internal_bs_conv_u_riders(const float* in, const void* wimg, const float* mask_src, float* out, uint8_t* pool_idx, int unpool,
+                                    int N, int Cin, int Cout, int H, int W, const clhip_wgrad_job* jobs, int n_jobs, int place,
+                                    int riders, hipStream_t s) {
+    if (!in || !wimg || !out || N <= 0 || !clhip_internal_bs_ok(Cin, Cout, H, W) || !clhip_internal_bs_index_ok(Cin, Cout, H, W, 3)) return CLHIP_EINVAL;
+    if (((H | W) & 1) && (pool_idx || unpool)) return CLHIP_ENOTSUP;
+    if (!jobs || n_jobs < 1 || n_jobs > CLHIP_WGRAD_JOBS_MAX || place < 1 || place > 3 || riders < 8 || riders % 8 || riders > (1 << 20))
+        return CLHIP_ENOTSUP;
+    unsigned long long units = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const clhip_wgrad_job& j = jobs[i];
+        if (!j.part || !j.dw || j.K <= 0 || j.C <= 0 || j.splits <= 0 || (j.taps != 0 && j.taps != 9 && j.taps != 25)) return CLHIP_ENOTSUP;
+        units += ((unsigned long long)(j.taps ? j.taps : 9) * j.K * j.C + j.K + RED_EL - 1) / RED_EL;
+    }
+    if (units > 0x7fffffffULL) return CLHIP_ENOTSUP;
+    const int useful = (int)((units + 7) / 8 * 8);                  // (a rider beyond the last unit would find nothing to do)
+    if (riders > useful) riders = useful;
+    RedJobs r;
+    wgrad_reduce_fill(r, jobs, n_jobs);
+    const clhip_u32x4* img = static_cast<const clhip_u32x4*>(wimg);
+    if (unpool) return bs_launch_riders<true>(in, img, mask_src, out, pool_idx, N, Cin, Cout, H, W, r, place, riders, s);
+    return bs_launch_riders<false>(in, img, mask_src, out, nullptr, N, Cin, Cout, H, W, r, place, riders, s);
+}
+
 // the same for 5 x 5 taps (image made by clhip_internal_bs_weights from a job with pad = 5)
 int clhip_internal_bs5_conv_u(int mode, const float* in, const void* wimg, const float* bias, const float* mask_src, float* out, int N,
                               int Cin, int Cout, int H, int W, int relu, hipStream_t s) {
@@ -740,6 +877,29 @@ int clhip_conv3x3_bs_bwd_data(const float* dy, const uint8_t* idx_u8_or_null, co
     if (rc) return rc;
     return clhip_internal_bs_conv_u(1, dy, ws, nullptr, relu_src, dx, const_cast<uint8_t*>(idx_u8_or_null), idx_u8_or_null != nullptr,
                                     N, K, C, H, W, 0, as_stream(stream));
+}
+
+// clhip_conv3x3_bs_bwd_data with `riders` blocks of its launch reducing the given weight-gradient slabs (clhip.h)
+int clhip_conv3x3_bs_bwd_data_riders(const float* dy, const uint8_t* idx_u8_or_null, const float* w, const float* relu_src, float* dx, int N,
+                                     int C, int K, int H, int W, void* ws, size_t ws_bytes, const clhip_reduce_job* jobs, int n_jobs,
+                                     int place, int riders, void* stream) {
+    if (N <= 0 || !clhip_internal_bs_ok(K, C, H, W)) return CLHIP_ENOTSUP;
+    if (!dy || !w || !dx || !ws || ws_bytes < clhip_internal_bs_ws(K, C)) return CLHIP_EINVAL;
+    if (!clhip_internal_bs_index_ok(K, C, H, W, 3)) return CLHIP_EINVAL;
+    if (((H | W) & 1) && idx_u8_or_null) return CLHIP_ENOTSUP;
+    if (!jobs || n_jobs < 1 || n_jobs > CLHIP_WGRAD_JOBS_MAX || place < 1 || place > 3 || riders < 8 || riders % 8 || riders > (1 << 20))
+        return CLHIP_ENOTSUP;
+    clhip_wgrad_job q[CLHIP_WGRAD_JOBS_MAX];
+    for (int i = 0; i < n_jobs; ++i) {
+        const clhip_reduce_job& j = jobs[i];
+        if (!j.slabs || !j.dw || j.K <= 0 || j.C <= 0 || j.splits <= 0 || (j.taps != 9 && j.taps != 25)) return CLHIP_EINVAL;
+        q[i] = clhip_wgrad_job{j.slabs, j.dw, j.db, j.K, j.C, j.splits, j.taps};
+    }
+    const clhip_wino_wt job{w, static_cast<float*>(ws), C, K, 1, 0};
+    const int rc = clhip_internal_bs_weights(&job, 1, as_stream(stream));
+    if (rc) return rc;
+    return clhip_internal_bs_conv_u_riders(dy, ws, relu_src, dx, const_cast<uint8_t*>(idx_u8_or_null), idx_u8_or_null != nullptr, N, K, C, H,
+                                           W, q, n_jobs, place, riders, as_stream(stream));
 }
 
 }  // extern "C"

@@ -215,6 +215,12 @@ size_t clhip_internal_bs_ws(int Cin, int Cout);
 int clhip_internal_bs_weights(const clhip_wino_wt* jobs, int n, hipStream_t s);
 int clhip_internal_bs_conv_u(int mode, const float* in, const void* wimg, const float* bias, const float* mask_src, float* out,
                              uint8_t* pool_idx, int unpool, int N, int Cin, int Cout, int H, int W, int relu, hipStream_t s);
+// backward-data (mode 1) with the reduction of finished weight-gradient slabs (jobs[0 .. n_jobs), complete on `s` before this call) run
+// by `riders` extra blocks of the same grid; place: 1 riders in front of the convolution blocks, 2 behind them, 3 spread through the grid.
+// CLHIP_ENOTSUP: not taken (nothing launched, nothing reduced) — the caller issues the plain launch and reduces the jobs itself
+int clhip_internal_bs_conv_u_riders(const float* in, const void* wimg, const float* mask_src, float* out, uint8_t* pool_idx, int unpool,
+                                    int N, int Cin, int Cout, int H, int W, const clhip_wgrad_job* jobs, int n_jobs, int place,
+                                    int riders, hipStream_t s);
 // bswgrad5.hip: 5x5 / padding-2 weight gradient on the bf16 matrix cores (AlexNet's second convolution): slabs + reduction
 bool clhip_internal_bs5_wgrad_ok(int N, int C, int K, int H, int W);
 size_t clhip_internal_bs5_wgrad_ws(int N, int C, int K, int H, int W);

@@ -82,6 +82,9 @@ constexpr unsigned PROBE_RING = 64;
 #ifndef CLHIP_EDGE_GRIDS_DEFAULT
 #define CLHIP_EDGE_GRIDS_DEFAULT 1
 #endif
+#ifndef CLHIP_REDUCE_RIDERS_DEFAULT
+#define CLHIP_REDUCE_RIDERS_DEFAULT 1
+#endif
 #ifndef CLHIP_OVERLAP_DEFAULT
 #define CLHIP_OVERLAP_DEFAULT 0
 #endif
@@ -92,11 +95,22 @@ bool wino_enabled() { return !env_starts("CLHIP_WINO", '0'); }           // =0: 
 bool bs5_wgrad_enabled() { return !env_starts("CLHIP_BS_WGRAD", '0'); }  // =0: no bf16-split weight gradient on the 5x5 layers
 bool s2d_enabled() { return env_starts("CLHIP_S2D", '1'); }              // =1: a strided first layer over phase planes (choose_paths)
 bool fc_tail_enabled() { return !env_starts("CLHIP_FC_TAIL", '0'); }     // =0: per-layer classifier launches (the bitwise reference of the fused tail)
-// CLHIP_WGRAD_OVERLAP=1 / 2 (make_resources), CLHIP_EDGE_GRIDS=0 / 1 / 2 (NetPlan::edge_grids)
+// CLHIP_WGRAD_OVERLAP=1 / 2 (make_resources), CLHIP_EDGE_GRIDS=0 / 1 / 2 (NetPlan::edge_grids), CLHIP_REDUCE_RIDERS=0 .. 3 (NetPlan::reduce_riders)
 int overlap_mode() { return env_starts("CLHIP_WGRAD_OVERLAP", '1') ? 1 : env_starts("CLHIP_WGRAD_OVERLAP", '2') ? 2 : CLHIP_OVERLAP_DEFAULT; }
 int edge_grids_mode() {
     const char* e = std::getenv("CLHIP_EDGE_GRIDS");
     return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : CLHIP_EDGE_GRIDS_DEFAULT;
+}
+
+int reduce_riders_mode() {
+    const char* e = std::getenv("CLHIP_REDUCE_RIDERS");
+    return (e && e[0] >= '0' && e[0] <= '3' && !e[1]) ? e[0] - '0' : CLHIP_REDUCE_RIDERS_DEFAULT;
+}
+// tuning switch (tools/experiments): rider blocks of the host launch, a multiple of 256
+int reduce_rider_blocks() {
+    const char* e = std::getenv("CLHIP_REDUCE_RIDER_BLOCKS");
+    const int v = e && e[0] ? std::atoi(e) : 0;
+    return (v > 0 && v % 256 == 0 && v <= 16384) ? v : 256;
 }
 
 struct NetPlan {
@@ -135,6 +149,13 @@ struct NetPlan {
     // 1 / 2: weight blocks at the end / at the front of the merged grid (both measured, DESIGN 9: the end is the faster side)
     int edge_grids;
     unsigned edge_count;     // merged launches issued so far (clhip_net_edge_grid_count: tests tell the merged grid from its fallback)
+    // CLHIP_REDUCE_RIDERS (default 1): the weight-gradient slabs that are complete when the LAST bf16-split backward-data launch of a
+    // pass is issued (layer rider_host: the lowest conv layer > 0 whose backward-data is Conv::Bs3; -1: none) are reduced by rider
+    // blocks of that launch (bsconv.hip, bs_conv_riders_kernel); the reduction launch of the pass keeps what is left, the first
+    // layer's slabs.  0: every slab in the reduction launch (the bitwise A/B reference); 1 / 2 / 3: riders in front of / behind /
+    // spread through the convolution blocks (all measured, DESIGN 9: in front is the only order faster than the two launches)
+    int reduce_riders, rider_blocks, rider_host = -1;
+    unsigned rider_count;    // backward passes whose host launch carried riders (clhip_net_reduce_rider_count)
     // backward (optional, CLHIP_WGRAD_OVERLAP): the weight-gradient launches of the conv layers run on a side stream
     // next to the backward-data launch of the same layer (both only read dy)
     bool overlap;
@@ -410,6 +431,10 @@ void make_resources(NetPlan& p) {
         } else { (void)hipGetLastError(); p.side = nullptr; }
     }
     p.edge_grids = edge_grids_mode();
+    p.reduce_riders = reduce_riders_mode();
+    p.rider_blocks = reduce_rider_blocks();
+    for (size_t i = n_layers; i-- > 1;)
+        if (p.layers[i].type == 0 && p.layers[i].bwd == Conv::Bs3) p.rider_host = (int)i;
     const bool tail = fc_tail_enabled();
     p.no_combo = !tail;
     if (p.fc_fused && tail && clhip_internal_fc_tail_ok(&p.chain) && p.max_batch <= 1024) {
@@ -472,10 +497,19 @@ static int launch_conv_fwd(const Pass& c, const LayerPlan& L, const float* in, f
 // Backward-data launch of a conv layer (> 0): dx = conv^T(dy), masked with (xmask > 0) where xmask is given.  unpool_idx: dy is the
 // POOLED gradient of a 2x2 pool and the kernel rebuilds the un-pooled tile from it and the arg-max bytes while staging
 // (3x3 kernels only; they may decline a shape with CLHIP_ENOTSUP).
-static int launch_conv_bwd_data(const Pass& c, const LayerPlan& L, const float* dy, uint8_t* unpool_idx, const float* xmask, float* dx) {
+// ride != NULL (the plan's rider host, a Conv::Bs3 layer): the launch also reduces the slab jobs ride[0 .. n_ride) in rider blocks and
+// sets *rode; where the kernel declines them (CLHIP_ENOTSUP) the plain launch goes out and *rode stays false.
+static int launch_conv_bwd_data(const Pass& c, const LayerPlan& L, const float* dy, uint8_t* unpool_idx, const float* xmask, float* dx,
+                                const clhip_wgrad_job* ride = nullptr, int n_ride = 0, bool* rode = nullptr) {
     const float* w = c.params + L.w_off;
     switch (L.bwd) {
     case Conv::Wino: case Conv::Bs3:
+        if (ride && L.bwd == Conv::Bs3) {
+            const int r = clhip_internal_bs_conv_u_riders(dy, c.image(L.img_d), xmask, dx, unpool_idx, unpool_idx ? 1 : 0, c.N, L.cout, L.cin,
+                                                          L.h, L.w, ride, n_ride, c.p->reduce_riders, c.p->rider_blocks, c.s());
+            if (r == 0) *rode = true;
+            if (r != CLHIP_ENOTSUP) return r;
+        }
         return plan_conv_u(L.bwd, 1, dy, c.image(L.img_d), nullptr, xmask, dx, unpool_idx, unpool_idx ? 1 : 0, c.N, L.cout, L.cin, L.h, L.w, 0,
                            c.s());
     case Conv::Direct3:
@@ -678,6 +712,7 @@ struct BackwardPass {
     hipEvent_t pending[2] = {nullptr, nullptr};      // side-stream reader of g[b] that must finish before g[b] is rewritten
     clhip_wgrad_job jobs[CLHIP_WGRAD_JOBS_MAX];
     int n_jobs = 0;
+    bool side_jobs = false;  // one of jobs[] was issued on the side stream: its slabs are not ordered before a main-stream launch
 
     BackwardPass(NetPlan* plan, const float* params, float* grads_, int N, void* ws, const float* dl, void* stream)
         : c(plan, params, N, ws, stream), p(plan), grads(grads_), dlogits(dl),
@@ -805,7 +840,16 @@ int BackwardPass::conv_layer(int i, const float* xin, const float* xmask) {
         bool job = false;
         probe_begin(2);
         const int r = on_side(i, dy_buf, [&](void* st) { return launch_wgrad(c, grads, L, xin, dy, idx_or_null, st, defer, &jobs[n_jobs], &job); });
-        if (r == 0) { wdone = true; probe_end(2); if (job) ++n_jobs; }
+        if (r == 0) { wdone = true; probe_end(2); if (job) { ++n_jobs; side_jobs = side_jobs || side_ok(i); } }
+        return r;
+    };
+    // the backward-data launch; at the plan's rider host it takes the slab jobs collected so far along (all of them issued on the
+    // main stream in front of it) and they are done: the reduction launch of the pass keeps the jobs that follow
+    auto bwd_data = [&](const float* dy, uint8_t* idx_or_null, float* dx) {
+        const bool host = i == p->rider_host && p->reduce_riders && defer && n_jobs > 0 && !side_jobs;
+        bool rode = false;
+        const int r = launch_conv_bwd_data(c, L, dy, idx_or_null, xmask, dx, host ? jobs : nullptr, n_jobs, &rode);
+        if (rode) { n_jobs = 0; ++p->rider_count; }
         return r;
     };
     if (L.vgg && L.pool22 && !L.bn && (L.wg & WG_3X3)) {
@@ -824,7 +868,7 @@ int BackwardPass::conv_layer(int i, const float* xin, const float* xmask) {
         if (wdone && !ddone && i > 0 && !L.drop && !L.extra_grad) {
             if (!gout_d) { gout_d = take(); gout_d_buf = taken; }
             probe_begin(1);
-            rc = launch_conv_bwd_data(c, L, gin, pidx, xmask, gout_d);
+            rc = bwd_data(gin, pidx, gout_d);
             if (rc == 0) { ddone = true; probe_end(1); }
             else if (rc != CLHIP_ENOTSUP) return rc;
         }
@@ -860,7 +904,7 @@ int BackwardPass::conv_layer(int i, const float* xin, const float* xmask) {
     float* gout = gout_d;             // (taken for a merged launch that declined the shape)
     if (gout) taken = gout_d_buf; else gout = take();
     probe_begin(1);
-    rc = launch_conv_bwd_data(c, L, gy, nullptr, xmask, gout);
+    rc = bwd_data(gy, nullptr, gout);
     if (rc) return rc;
     probe_end(1);
     gin = gout; gin_buf = taken;
@@ -972,6 +1016,11 @@ int clhip_net_edge_grid_count(void* handle) {
     return p ? (int)(p->edge_count & 0x7fffffffu) : CLHIP_EINVAL;
 }
 
+int clhip_net_reduce_rider_count(void* handle) {
+    NetPlan* p = static_cast<NetPlan*>(handle);
+    return p ? (int)(p->rider_count & 0x7fffffffu) : CLHIP_EINVAL;
+}
+
 int clhip_net_prepared_weights(void* handle, size_t* ws_byte_off, size_t* bytes) {
     NetPlan* p = static_cast<NetPlan*>(handle);
     if (!p || !ws_byte_off || !bytes) return CLHIP_EINVAL;
@@ -1012,7 +1061,9 @@ int clhip_net_set_input_grad(void* handle, int layer, const float* extra) {
 }
 
 // Measurement: time the forward launch(es) of plan layer `layer` with HIP events on the stream they are issued on
-// (layer < 0: off).  clhip_net_probe_read waits for the recorded launches and returns their average duration over the
+// (layer < 0: off).  A backward-data probe (clhip_net_probe_kind 1) on the plan's rider host times that launch WITH its rider
+// blocks (CLHIP_REDUCE_RIDERS; with 0 the slabs are reduced outside the pair) — as the layer-0 forward probe does with the weight
+// blocks of the edge grid.  clhip_net_probe_read waits for the recorded launches and returns their average duration over the
 // last (at most 64) forward passes, then clears the count.
 int clhip_net_probe(void* handle, int layer) {
     NetPlan* p = static_cast<NetPlan*>(handle);

@@ -289,6 +289,14 @@ class NetEngine:
             raise RuntimeError("clhip_net_edge_grid_count")
         return n
 
+    def reduce_rider_count(self):
+        """Backward passes so far whose finished weight-gradient slabs were reduced by rider blocks of the lowest bf16-split
+        layer's backward-data launch (CLHIP_REDUCE_RIDERS) instead of by the reduction launch at the end of the pass."""
+        n = _lib.lib().clhip_net_reduce_rider_count(self._h)
+        if n < 0:
+            raise RuntimeError("clhip_net_reduce_rider_count")
+        return n
+
     def layer_paths(self, layer):
         """{'fwd', 'bwd_data', 'bwd_weight'} -> True where the plan runs the layer's kernel through a prepared-weights path
         (Winograd, csrc/wino.hip) instead of the direct f32 kernels; 'bs_fwd' / 'bs_bwd_data' -> True where that launch is the

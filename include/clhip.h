@@ -318,6 +318,22 @@ int clhip_conv3x3_bs_fwd(const float* x, const float* w, const float* b, float* 
                          int H, int W, int relu, void* ws, size_t ws_bytes, void* stream);
 int clhip_conv3x3_bs_bwd_data(const float* dy, const uint8_t* idx_u8_or_null, const float* w, const float* relu_src, float* dx,
                               int N, int C, int K, int H, int W, void* ws, size_t ws_bytes, void* stream);
+/* clhip_conv3x3_bs_bwd_data whose launch also carries `riders` extra blocks that reduce finished weight-gradient slabs while the
+ * convolution blocks run (csrc/bsconv.hip, bs_conv_riders_kernel; what the plan executor does at its lowest bf16-split layer,
+ * CLHIP_REDUCE_RIDERS).  Job i: `splits` slabs of taps * K * C + K floats back to back at `slabs`, complete on `stream` before the
+ * call; dw [K][C][taps] and db [K] (may be NULL) receive exactly what clhip_conv3x3_bwd_weight_reduce writes (taps: 9 or 25).
+ * place: 1 riders in front of the convolution blocks, 2 behind them, 3 spread through the grid; riders: a multiple of 8.
+ * dx is bitwise that of clhip_conv3x3_bs_bwd_data.  Answers as there; a bad job -> CLHIP_EINVAL; n_jobs outside 1 .. 32, another
+ * place, riders no positive multiple of 8 -> CLHIP_ENOTSUP, nothing launched. */
+typedef struct clhip_reduce_job {
+    const float* slabs;
+    float* dw;
+    float* db;
+    int K, C, splits, taps;
+} clhip_reduce_job;
+int clhip_conv3x3_bs_bwd_data_riders(const float* dy, const uint8_t* idx_u8_or_null, const float* w, const float* relu_src, float* dx,
+                                     int N, int C, int K, int H, int W, void* ws, size_t ws_bytes, const clhip_reduce_job* jobs,
+                                     int n_jobs, int place, int riders, void* stream);
 /* The same kernel with 5 x 5 taps (stride 1, padding 2): torchvision AlexNet's features[3], nn.Conv2d(64, 192, 5, padding=2) + ReLU
  * (models/net.py:96-125) and its autograd w.r.t. the input (dx *= (relu_src > 0) when relu_src != NULL).  w: [K][C][5][5].
  * C % 32 == 0, K % 64 == 0 on the forward (roles swapped on backward-data), W > 8.  ws: clhip_conv5x5_bs_ws(C, K) bytes.      */
@@ -472,6 +488,11 @@ int clhip_net_prepared_weights(void* handle, size_t* ws_byte_off, size_t* bytes)
  * CLHIP_EDGE_GRIDS != 0) instead of by a launch of their own; < 0 on error.  While it counts, a forward probe on layer 0
  * (clhip_net_probe_kind 0) times the merged launch, weight blocks included; with the separate launches they lie outside the pair. */
 int clhip_net_edge_grid_count(void* handle);
+/* How many backward passes of this plan reduced the weight-gradient slabs finished so far INSIDE the backward-data launch of the
+ * plan's lowest bf16-split layer (rider blocks, CLHIP_REDUCE_RIDERS != 0; csrc/bsconv.hip) instead of leaving them to the one
+ * reduction launch at the end of the pass; < 0 on error.  While it counts, a backward-data probe on that layer
+ * (clhip_net_probe_kind 1) times the launch with its riders, and the reduction launch of the pass holds the remaining slabs only. */
+int clhip_net_reduce_rider_count(void* handle);
 /* Which kernels the plan chose for a layer (measurement harnesses time the same ones): bit 0 forward, bit 1 backward-data, bit 2
  * weight gradient through a prepared-weights path instead of the direct f32 MFMA kernels — Winograd F(2x2,3x3) (csrc/wino.hip)
  * unless bit 3 (forward) / bit 4 (backward-data) says the launch is the bf16-split kernel (csrc/bsconv.hip); bit 5: the weight
