@@ -150,6 +150,18 @@ static int gather_resized(const TS* tasks_dev, int T, int C, int Hs, int Ws, int
 
 extern "C" {
 
+// Host read-outs of the launch plans (no launch, no device): what the tests assert their geometries against.
+int clhip_resized_crop_plan(int Hs, int Ws, int th, int tw, int byte_frames, int* out7) {
+    if (Hs < 1 || Ws < 1 || th < 1 || tw < 1 || !out7) return CLHIP_EINVAL;
+    rz_plan p;
+    if (!rz_make_plan(Hs, Ws, th, tw, byte_frames ? 256 * sizeof(float) : 0, &p)) return CLHIP_ENOTSUP;   // (gather_resized's call)
+    out7[0] = p.rpb; out7[1] = p.chunks; out7[2] = p.nb; out7[3] = p.wmax; out7[4] = p.ktx; out7[5] = p.kty;
+    out7[6] = (int)p.lds;
+    return 0;
+}
+
+int clhip_crop_rows_per_block(int tw) { return tw < 1 ? CLHIP_EINVAL : cf_rows_per_block(tw); }
+
 int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const int64_t* idx,
                                  const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
     return gather_crop_flip(tasks_dev, T, C, Hs, Ws, th, tw, nullptr, idx, params, B, x_out, labels_out, stream);

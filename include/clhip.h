@@ -759,6 +759,21 @@ int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T,
                                          const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out,
                                          void* stream);
 
+/* Host read-outs of the launch plans of the window entries (the gathers above, clhip_rehearsal_assemble_*crop_flip*,
+ * clhip_icarl_assemble_*crop_flip*); nothing is launched and no device is needed.  Test infrastructure: a test asserts through
+ * them that a geometry still splits a channel plane into the blocks it was chosen for.
+ *   resized_crop_plan     the plan every resized entry makes for frames Hs x Ws resized to th x tw (byte_frames != 0: the _u8
+ *                         entries, whose blocks also hold a 1024-byte table): out7 = {rpb, chunks, nb, wmax, ktx, kty, lds_bytes}
+ *                         = output lines per block, blocks per channel plane (chunks rpb >= th > (chunks - 1) rpb), the source
+ *                         lines and the line width the block's LDS band holds, the taps per axis at the largest window, and the
+ *                         dynamic LDS of a block (at most 48 KB, up to 64 KB only with rpb == 1).  Returns 0; CLHIP_ENOTSUP
+ *                         where the entries return it (no plan; out7 is not written); CLHIP_EINVAL for an argument < 1 or
+ *                         out7 == NULL.
+ *   crop_rows_per_block   the output lines per block of every crop + flip entry for output width tw (blocks per channel plane:
+ *                         ceil(th / that)); CLHIP_EINVAL for tw < 1. */
+int clhip_resized_crop_plan(int Hs, int Ws, int th, int tw, int byte_frames, int* out7);
+int clhip_crop_rows_per_block(int tw);
+
 /* ------------------------------------------------------------------ byte frames
  * ToTensor -> Normalize, the last step of every Compose of the reference (data/recogseq_dataprep.py:53-60,
  * data/inaturalist_dataprep.py:232-277, data/tinyimgnet_dataprep.py:105-122), done inside the gathers: the task tensors hold the

@@ -1,7 +1,8 @@
 """Shared helpers of the kernel-level parity tests (test_gpu_loss_kernels.py, test_gpu_hat_kernels.py,
 test_gpu_gemm_kernels.py, test_gpu_pool_kernels.py, test_gpu_bn_kernels.py, test_gpu_packnet_kernels.py,
 test_gpu_elementwise_kernels.py, test_gpu_gem_kernels.py, test_gpu_fc_chain_kernels.py, test_gpu_conv2d_kernels.py,
-test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py, test_gpu_conv3x3_kernels.py, test_gpu_bs3x3_kernels.py) — test infrastructure.
+test_gpu_conv5x5_bs_kernels.py, test_gpu_wino_kernels.py, test_gpu_conv3x3_kernels.py, test_gpu_bs3x3_kernels.py,
+test_gpu_window_chunks.py, test_window_plan_cpu.py) — test infrastructure.
 
 The fp32-chain rule is the one of assert_fp32_parity in test_gpu_parity.py with the bounds these two files use: the device
 result's distance from an fp64 evaluation of the same formula on the same float32 inputs, relative to the tensor's largest
