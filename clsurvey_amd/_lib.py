@@ -185,7 +185,9 @@ SIGNATURES = {
     "clhip_slice_argmax_count": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
     "clhip_gather_tasks_crop_flip": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p]),
     "clhip_gather_tasks_resized_crop_flip": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p]),
-    "clhip_resized_crop_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "clhip_gather_tasks_pad_crop_flip": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
+    "clhip_gather_tasks_pad_crop_flip_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "clhip_resized_crop_plan":(_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
     "clhip_crop_rows_per_block": (_i, [_i]),
     "clhip_gather_tasks_u8": (_i, [_p, _i, _i, _z, _p, _p, _i, _p, _p, _p]),
     "clhip_gather_tasks_crop_flip_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),

@@ -8,7 +8,11 @@
 //   gather_tasks_resized_crop_flip   one (top, left, h, w, flip) per batch position: the h x w window of the frame resized to
 //                            th x tw by the antialiased bilinear filter of ATen's _upsample_bilinear2d_aa (align_corners =
 //                            False), then mirrored.  Separable: lines first, then columns, fp32, taps in ascending source order.
-// Both also serve BYTE frames (the ..._u8 entries; TS = clhip_task_src_u8): a stored byte v of channel c means lut[c][v], the
+// and torchvision's RandomCrop(size, padding, fill, padding_mode) + RandomHorizontalFlip (the CIFAR-style rule; not in the
+// reference's Composes, which crop a larger frame):
+//   gather_tasks_pad_crop_flip   one (top, left, flip, h, w) per batch position: the window of the sample's PADDED image
+//                            (constant / edge / reflect / symmetric around its h x w extent), then mirrored.  A copy: bitwise.
+// All also serve BYTE frames (the ..._u8 entries; TS = clhip_task_src_u8): a stored byte v of channel c means lut[c][v], the
 // ToTensor -> Normalize of the reference's Compose as a table the host computed.  The block's channel of the table is staged in
 // LDS and every source element is decoded where it is loaded; everything after the load is the fp32 code, so the result is
 // bitwise the fp32 entry's on the decoded frames.
@@ -60,6 +64,58 @@ __global__ __launch_bounds__(CF_BLOCK) void gather_crop_flip_kernel(const TS* __
         typedef const float __attribute__((address_space(1))) gfloat;
         gfloat* src = (gfloat*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws + (size_t)(top + y0) * Ws + left);
         cf_copy_window<VEC>(src, Ws, dst, (unsigned)nrows * (unsigned)tw, tw, flip);  // total <= max(CF_SEG, tw) < 2^31
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- padded crop
+// gather_crop_flip_kernel for RandomCrop(size, padding, fill, padding_mode) + flip: same grid, same block -> (channel, chunk
+// of lines) split, same task selection and labels.  params rows are (top, left, flip, h, w): the window's corner in the
+// UNPADDED coordinates of the sample's h x w extent (top in [-pt, h + pb - th], left in [-pl, w + pr - tw]); cf_copy_window_pad
+// maps every source coordinate into the extent, so the frame is never read outside it.  The rows the header lists as bad copy
+// nothing and write label -1 (64-bit compares: a bad table may hold any int32).  MODE (the padding mode) is a template argument:
+// the maps compile to the mode's own two or three instructions.
+template <bool VEC, int MODE, typename TS>
+__global__ __launch_bounds__(CF_BLOCK) void gather_pad_crop_flip_kernel(const TS* __restrict__ tasks, int T, int C, int Hs,
+                                                                         int Ws, int th, int tw, int rpb, int chunks,
+                                                                         int pl, int pt, int pr, int pb,
+                                                                         const float* __restrict__ fill,
+                                                                         const float* __restrict__ lut,
+                                                                         const int64_t* __restrict__ idx, const int* __restrict__ params,
+                                                                         float* __restrict__ x_out, int64_t* __restrict__ labels_out) {
+    const int r = blockIdx.y;
+    const int64_t g = idx[r];
+    const int top = params[5 * r], left = params[5 * r + 1], flip = params[5 * r + 2], h = params[5 * r + 3], w = params[5 * r + 4];
+    const int lane = threadIdx.x & 63;                                      // bisect_right by ballot, as gather_tasks_kernel
+    const int64_t cum = lane < T ? tasks[lane].cum_rows : INT64_MAX;
+    const int t = __popcll(__ballot(cum <= g));
+    constexpr int lim = MODE == CF_PAD_REFLECT ? 1 : 0;                     // reflect: pad <= extent - 1, symmetric: pad <= extent
+    const bool one_reflection = MODE < CF_PAD_REFLECT || (max(pl, pr) <= w - lim && max(pt, pb) <= h - lim);
+    if (g < 0 || t >= T || (flip != 0 && flip != 1) || h < 1 || h > Hs || w < 1 || w > Ws || top < -pt ||
+        (int64_t)top > (int64_t)h + pb - th || left < -pl || (int64_t)left > (int64_t)w + pr - tw || !one_reflection) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) labels_out[r] = -1;
+        return;
+    }
+    const int64_t local = g - (t ? tasks[t - 1].cum_rows : 0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) labels_out[r] = tasks[t].labels[local] + tasks[t].label_shift;
+    const int c = (int)blockIdx.x / chunks;
+    const int y0 = ((int)blockIdx.x - c * chunks) * rpb;
+    const int nrows = min(rpb, th - y0);
+    float* dst = x_out + (((size_t)r * C + c) * th + y0) * tw;
+    const float fill_c = fill[c];
+    // (a pointer read out of the table is generic to the compiler; it is device memory, so say so: global_load, not flat_load)
+    if constexpr (ts_u8<TS>) {
+        __shared__ float lut_s[257];                                        // the table of channel c (CF_BLOCK == 256: one entry each)
+        lut_s[threadIdx.x] = lut[c * 256 + (int)threadIdx.x];
+        if (threadIdx.x == 0) lut_s[256] = fill_c;                          // entry 256: what a fill element decodes to
+        __syncthreads();
+        typedef const uint8_t __attribute__((address_space(1))) gbyte;
+        gbyte* plane = (gbyte*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws);
+        cf_copy_window_pad<VEC, MODE>(plane, Ws, h, w, top + y0, left, fill_c, dst, (unsigned)nrows * (unsigned)tw, tw, flip,
+                                      cf_load_u8{lut_s});
+    } else {
+        typedef const float __attribute__((address_space(1))) gfloat;
+        gfloat* plane = (gfloat*)(tasks[t].x + ((size_t)local * C + c) * Hs * Ws);
+        cf_copy_window_pad<VEC, MODE>(plane, Ws, h, w, top + y0, left, fill_c, dst, (unsigned)nrows * (unsigned)tw, tw, flip);
     }
 }
 
@@ -127,6 +183,39 @@ static int gather_crop_flip(const TS* tasks_dev, int T, int C, int Hs, int Ws, i
 }
 
 template <typename TS>
+static int gather_pad_crop_flip(const TS* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, int mode, int pl, int pt, int pr,
+                                int pb, const float* fill, const float* lut, const int64_t* idx, const int* params, int B,
+                                float* x_out, int64_t* labels_out, void* stream) {
+    // (a crop larger than the frame is legal here: the padded image may hold it, and a row whose image does not is a bad row)
+    if (!tasks_dev || !fill || T < 1 || T > CLHIP_MAX_TASKS || C < 1 || Hs < 1 || Ws < 1 || th < 1 || tw < 1 || B < 0)
+        return CLHIP_EINVAL;
+    if (Hs > CLHIP_PAD_MAX_EXTENT || Ws > CLHIP_PAD_MAX_EXTENT) return CLHIP_EINVAL;   // (2 n - 1 - s stays an int)
+    if (mode < CF_PAD_CONSTANT || mode > CF_PAD_SYMMETRIC) return CLHIP_EINVAL;
+    if (pl < 0 || pt < 0 || pr < 0 || pb < 0 || pl > CLHIP_PAD_MAX || pt > CLHIP_PAD_MAX || pr > CLHIP_PAD_MAX || pb > CLHIP_PAD_MAX)
+        return CLHIP_EINVAL;
+    if (ts_u8<TS> && !lut) return CLHIP_EINVAL;
+    if (B == 0) return 0;
+    if (!idx || !params || !x_out || !labels_out || B > 65535) return CLHIP_EINVAL;
+    const int rpb = cf_rows_per_block(tw);
+    const int chunks = (th + rpb - 1) / rpb;
+    if ((size_t)C * chunks > 0x7fffffffull) return CLHIP_EINVAL;
+    const dim3 grid((unsigned)(C * chunks), (unsigned)B);
+    const bool vec = tw % 4 == 0 && aligned16(x_out);
+#define CLHIP_PAD_LAUNCH(VEC, MODE)                                                                                                \
+    hipLaunchKernelGGL((gather_pad_crop_flip_kernel<VEC, MODE, TS>), grid, dim3(CF_BLOCK), 0, as_stream(stream), tasks_dev, T, C, \
+                       Hs, Ws, th, tw, rpb, chunks, pl, pt, pr, pb, fill, lut, idx, params, x_out, labels_out)
+    switch (mode) {
+    case CF_PAD_CONSTANT: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_CONSTANT); else CLHIP_PAD_LAUNCH(false, CF_PAD_CONSTANT); break;
+    case CF_PAD_EDGE: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_EDGE); else CLHIP_PAD_LAUNCH(false, CF_PAD_EDGE); break;
+    case CF_PAD_REFLECT: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_REFLECT); else CLHIP_PAD_LAUNCH(false, CF_PAD_REFLECT); break;
+    default: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_SYMMETRIC); else CLHIP_PAD_LAUNCH(false, CF_PAD_SYMMETRIC); break;
+    }
+#undef CLHIP_PAD_LAUNCH
+    CLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename TS>
 static int gather_resized(const TS* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const float* lut, const int64_t* idx,
                           const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
     // (an output larger than the frame is an enlargement here, not an error)
@@ -170,6 +259,20 @@ int clhip_gather_tasks_crop_flip(const clhip_task_src* tasks_dev, int T, int C, 
 int clhip_gather_tasks_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, const float* lut,
                                     const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
     return gather_crop_flip(tasks_dev, T, C, Hs, Ws, th, tw, lut, idx, params, B, x_out, labels_out, stream);
+}
+
+int clhip_gather_tasks_pad_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, int mode, int pl,
+                                     int pt, int pr, int pb, const float* fill, const int64_t* idx, const int* params, int B,
+                                     float* x_out, int64_t* labels_out, void* stream) {
+    return gather_pad_crop_flip(tasks_dev, T, C, Hs, Ws, th, tw, mode, pl, pt, pr, pb, fill, nullptr, idx, params, B, x_out,
+                                labels_out, stream);
+}
+
+int clhip_gather_tasks_pad_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, int mode,
+                                        int pl, int pt, int pr, int pb, const float* fill, const float* lut, const int64_t* idx,
+                                        const int* params, int B, float* x_out, int64_t* labels_out, void* stream) {
+    return gather_pad_crop_flip(tasks_dev, T, C, Hs, Ws, th, tw, mode, pl, pt, pr, pb, fill, lut, idx, params, B, x_out, labels_out,
+                                stream);
 }
 
 int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,

@@ -13,7 +13,9 @@ the reference run under the same seed (utilities/utils.py:52-58).
 A split may carry a `RandomCropFlip` spec (the `train` split of a RecogSeq task, the `rnd_transform` file of iNaturalist):
 its stored frames stay static in HBM and the loaders crop and mirror them inside the gather that assembles each batch
 (clhip_gather_tasks_crop_flip), a fresh draw per sample per epoch.  A `RandomResizedCropFlip` spec (the `train` split of the
-cropped Tiny-ImageNet variant) is served the same way by the gather that resamples (clhip_gather_tasks_resized_crop_flip).
+cropped Tiny-ImageNet variant) is served the same way by the gather that resamples (clhip_gather_tasks_resized_crop_flip), and a
+`RandomPadCropFlip` spec (torchvision's RandomCrop(size, padding, fill, padding_mode) + flip, the CIFAR-style rule for frames already
+at the net's input size) by the gather that pads (clhip_gather_tasks_pad_crop_flip): the stored frames carry no margin.
 
 A split may also hold its frames as the decoded uint8 images (`ByteTaskDataset`): ToTensor -> Normalize, the last step of every
 Compose of the reference, then happens inside the same gathers through a 256-entry table per channel (the ..._u8 entries of
@@ -72,6 +74,110 @@ class RandomResizedCropFlip(object):
             self.size, self.scale, self.ratio, self.p, "" if self.extents is None else ", extents=[%d][2]" % len(self.extents))
 
 
+PAD_MODES = ("constant", "edge", "reflect", "symmetric")      # torchvision's padding_mode; the position is the gathers' `mode`
+PAD_MAX = 32767               # CLHIP_PAD_MAX (include/clhip.h): the largest pad the padded gathers take
+
+
+class RandomPadCropFlip(object):
+    """torchvision's RandomCrop(size, padding, fill, padding_mode) + RandomHorizontalFlip(p) of stored frames (pad, crop, then
+    hflip; RandomCrop(32, padding=4) + flip is the standard augmentation of the CIFAR-style split benchmarks) as a picklable spec
+    like RandomCropFlip — a class of its own, not a subclass: code that asks isinstance(t, RandomCropFlip) never takes one for
+    the other.  size = (th, tw) of the output.  padding: an int, (left/right, top/bottom) or (left, top, right, bottom), kept
+    as (pl, pt, pr, pb); it goes around each sample's valid extent, not around the common storage frame.  padding_mode: one of
+    PAD_MODES.  fill (read by `constant` only): one value per channel IN THE DOMAIN OF THE STORED FRAMES, a scalar or a
+    C-sequence: floats (the normalised value) on a TensorTaskDataset, ints in 0..255 on a ByteTaskDataset, where byte v of
+    channel c means lut()[c][v] (torchvision pads the decoded image before ToTensor -> Normalize).  extents as in RandomCropFlip.
+    pad_if_needed is not built."""
+
+    def __init__(self, size, padding, fill=0, padding_mode="constant", p=0.5, extents=None):
+        th, tw = (int(v) for v in size)
+        if th < 1 or tw < 1 or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("RandomPadCropFlip: size >= 1 and 0 <= p <= 1, got %s, %s" % (size, p))
+        if isinstance(padding, (list, tuple)):
+            pads = tuple(padding)
+        elif isinstance(padding, bool) or not isinstance(padding, int):
+            raise ValueError("RandomPadCropFlip: padding is an int or a sequence of 2 or 4 ints, got %r" % (padding,))
+        else:
+            pads = (padding,)
+        if len(pads) not in (1, 2, 4) or any(isinstance(v, bool) or not isinstance(v, int) for v in pads):
+            raise ValueError("RandomPadCropFlip: padding is an int or a sequence of 2 or 4 ints, got %r" % (padding,))
+        pads = pads * 4 if len(pads) == 1 else pads * 2 if len(pads) == 2 else pads
+        if min(pads) < 0 or max(pads) > PAD_MAX:
+            raise ValueError("RandomPadCropFlip: pads in 0..%d, got %r" % (PAD_MAX, padding))
+        if padding_mode not in PAD_MODES:
+            raise ValueError("RandomPadCropFlip: padding_mode is one of %s, got %r" % (PAD_MODES, padding_mode))
+        if isinstance(fill, (list, tuple)):
+            fill = tuple(fill)
+            vals = fill
+            if not vals:
+                raise ValueError("RandomPadCropFlip: fill is a number or one number per channel, got %r" % (fill,))
+        else:
+            vals = (fill,)
+        if any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in vals):
+            raise ValueError("RandomPadCropFlip: fill is a number or one number per channel, got %r" % (fill,))
+        self.size = (th, tw)
+        self.padding = pads
+        self.fill = fill
+        self.padding_mode = padding_mode
+        self.p = float(p)
+        self.extents = None if extents is None else torch.as_tensor(extents, dtype=torch.int64).cpu().reshape(-1, 2)
+
+    def fill_values(self, C, byte=False):
+        """The C fill values, checked: one per channel, and on byte frames ints in 0..255."""
+        vals = self.fill if isinstance(self.fill, tuple) else (self.fill,) * int(C)
+        if len(vals) != int(C):
+            raise ValueError("RandomPadCropFlip: %d fill values for %d channels" % (len(vals), C))
+        if byte and any(not isinstance(v, int) or not 0 <= v <= 255 for v in vals):
+            raise ValueError("RandomPadCropFlip: the fill of byte frames is ints in 0..255, got %r" % (self.fill,))
+        return vals
+
+    def __repr__(self):
+        return "RandomPadCropFlip(size=%s, padding=%s, fill=%s, padding_mode=%r, p=%s%s)" % (
+            self.size, self.padding, self.fill, self.padding_mode, self.p,
+            "" if self.extents is None else ", extents=[%d][2]" % len(self.extents))
+
+
+def draw_pad_crop_flip(n, spec, frame_hw, generator, order=None):
+    """int32 [n][5] of (top, left, flip, h, w), one row per position of an epoch: the window's corner uniform over the padded
+    image of the sample served there (RandomCrop.get_params after the pad), in the sample's UNPADDED coordinates: with
+    (pl, pt, pr, pb) = spec.padding, i = min(floor(u0 (h + pt + pb - th + 1)), h + pt + pb - th) and top = i - pt in
+    [-pt, h + pb - th]; left likewise from u1 in [-pl, w + pr - tw]; flip = u2 < spec.p.  (h, w) is frame_hw, or with
+    spec.extents the extent of the sample (extents[order[k]], as in draw_crop_flip).  One torch.rand((n, 3), float64) call: with
+    all pads 0 the first three columns are bitwise draw_crop_flip's from the same generator state.
+    Raises if a padded extent is smaller than spec.size, an extent is empty or exceeds the frame, or the pads exceed what the
+    mode takes for the smallest extent (reflect: extent - 1, symmetric: extent, as torch.nn.functional.pad)."""
+    th, tw = spec.size
+    pl, pt, pr, pb = spec.padding
+    Hs, Ws = (int(v) for v in frame_hw)
+    n = int(n)
+    if spec.extents is None:
+        h = torch.full((n,), Hs, dtype=torch.int64)
+        w = torch.full((n,), Ws, dtype=torch.int64)
+    else:
+        ext = spec.extents if order is None else spec.extents.index_select(0, torch.as_tensor(order, dtype=torch.int64))
+        if ext.shape[0] != n:
+            raise ValueError("draw_pad_crop_flip: %d extents for %d positions" % (ext.shape[0], n))
+        h, w = ext[:, 0], ext[:, 1]
+    if n:
+        hmin, wmin = int(h.min()), int(w.min())
+        if hmin < 1 or wmin < 1:
+            raise ValueError("draw_pad_crop_flip: an empty extent")
+        if hmin + pt + pb < th or wmin + pl + pr < tw:
+            raise ValueError("draw_pad_crop_flip: a frame of %d x %d padded by %s is smaller than the crop %d x %d"
+                             % (hmin, wmin, spec.padding, th, tw))
+        if int(h.max()) > Hs or int(w.max()) > Ws:
+            raise ValueError("draw_pad_crop_flip: an extent exceeds the stored frame %d x %d" % (Hs, Ws))
+        slack = {"reflect": 1, "symmetric": 0}.get(spec.padding_mode)
+        if slack is not None and (max(pt, pb) > hmin - slack or max(pl, pr) > wmin - slack):
+            raise ValueError("draw_pad_crop_flip: padding_mode %r takes pads up to the extent%s, got %s for a frame of %d x %d"
+                             % (spec.padding_mode, " - 1" if slack else "", spec.padding, hmin, wmin))
+    u = torch.rand((n, 3), generator=generator, dtype=torch.float64)
+    top = torch.minimum((u[:, 0] * (h + (pt + pb - th + 1))).floor().long(), h + (pt + pb - th)) - pt
+    left = torch.minimum((u[:, 1] * (w + (pl + pr - tw + 1))).floor().long(), w + (pl + pr - tw)) - pl
+    flip = (u[:, 2] < spec.p).long()
+    return torch.stack([top, left, flip, h, w], 1).to(torch.int32).contiguous()
+
+
 def draw_crop_flip(n, spec, frame_hw, generator, order=None):
     """int32 [n][3] of (top, left, flip), one row per position of an epoch: top uniform on [0, h - th] and left on [0, w - tw],
     both inclusive (RandomCrop.get_params), flip = 1 with probability spec.p (RandomHorizontalFlip: rand < p).  (h, w) is
@@ -102,6 +208,9 @@ def draw_crop_flip(n, spec, frame_hw, generator, order=None):
     left = torch.minimum((u[:, 1] * (w - tw + 1)).floor().long(), w - tw)
     flip = (u[:, 2] < spec.p).long()
     return torch.stack([top, left, flip], 1).to(torch.int32).contiguous()
+
+
+SPECS = (RandomCropFlip, RandomResizedCropFlip, RandomPadCropFlip)
 
 
 RESIZED_TRIES = 10            # RandomResizedCrop.get_params: tries before the central fallback window
@@ -166,21 +275,24 @@ def draw_resized_crop_flip(n, spec, frame_hw, generator, order=None):
 
 def _spec_key(t):
     """What two specs must share to be served as one (the extents are per task)."""
-    return (type(t), t.size, t.p, getattr(t, "scale", None), getattr(t, "ratio", None))
+    return (type(t), t.size, t.p, getattr(t, "scale", None), getattr(t, "ratio", None),
+            getattr(t, "padding", None), getattr(t, "padding_mode", None), getattr(t, "fill", None))
 
 
 def _respec(t, extents=None):
     """`t` with other extents."""
     if isinstance(t, RandomResizedCropFlip):
         return RandomResizedCropFlip(t.size, t.scale, t.ratio, t.p, extents)
+    if isinstance(t, RandomPadCropFlip):
+        return RandomPadCropFlip(t.size, t.padding, t.fill, t.padding_mode, t.p, extents)
     return RandomCropFlip(t.size, t.p, extents)
 
 
 def _transform_of(dataset):
-    """The RandomCropFlip or RandomResizedCropFlip a dataset carries, else None (any other `transform` attribute is the
-    dataset's own business)."""
+    """The RandomCropFlip, RandomResizedCropFlip or RandomPadCropFlip a dataset carries, else None (any other `transform`
+    attribute is the dataset's own business)."""
     t = getattr(dataset, "transform", None)
-    return t if isinstance(t, (RandomCropFlip, RandomResizedCropFlip)) else None
+    return t if isinstance(t, SPECS) else None
 
 
 def norm_lut(mean, std):
@@ -213,7 +325,8 @@ def merged_transform(dsets):
     if all(t is None for t in ts):
         return None
     if any(t is None for t in ts) or any(_spec_key(t) != _spec_key(ts[0]) for t in ts):
-        raise ValueError("tasks served as one dataset carry equal RandomCropFlip size and p, or none: %s" % ts)
+        raise ValueError("tasks served as one dataset carry equal RandomCropFlip size and p (a RandomPadCropFlip: and equal "
+                         "padding, mode and fill), or none: %s" % ts)
     if all(t.extents is None for t in ts):
         return _respec(ts[0])
     ext = [t.extents if t.extents is not None else torch.tensor(tuple(d.x.shape[-2:])).repeat(len(d), 1) for t, d in zip(ts, dsets)]
@@ -236,8 +349,10 @@ class TensorTaskDataset(Dataset):
 
     def _set_transform(self, transform):
         if transform is not None:
-            if not isinstance(transform, (RandomCropFlip, RandomResizedCropFlip)):
+            if not isinstance(transform, SPECS):
                 raise TypeError("TensorTaskDataset: transform is None or a RandomCropFlip")
+            if isinstance(transform, RandomPadCropFlip):
+                transform.fill_values(self.x.shape[1], byte=self.x.dtype == torch.uint8)
             if transform.extents is not None and len(transform.extents) != len(self):
                 raise ValueError("TensorTaskDataset: %d extents for %d frames" % (len(transform.extents), len(self)))
             self.transform = transform
@@ -285,7 +400,15 @@ class ByteTaskDataset(TensorTaskDataset):
         for c in range(self.x.shape[1]):
             plane = self.x[:, c]
             x[:, c] = lut[c].index_select(0, plane.reshape(-1).int()).view(plane.shape)
-        return TensorTaskDataset(x, self.y, self.classes, transform=self.transform)
+        t = self.transform
+        if isinstance(t, RandomPadCropFlip):           # its fill is bytes here: the decoded split's is what they mean
+            t = RandomPadCropFlip(t.size, t.padding, self.decoded_fill(t), t.padding_mode, t.p, t.extents)
+        return TensorTaskDataset(x, self.y, self.classes, transform=t)
+
+    def decoded_fill(self, spec):
+        """The fill of a RandomPadCropFlip on these frames in the decoded domain: lut()[c][fill byte of c], one float a channel."""
+        lut = self.lut()
+        return tuple(float(lut[c, v]) for c, v in enumerate(spec.fill_values(self.x.shape[1], byte=True)))
 
 
 _TASK_CACHE = {}          # (path, mtime_ns, size, device) -> {'train' / 'val' / 'test': TensorTaskDataset in HBM}
@@ -362,10 +485,15 @@ class DeviceLoader:
     split would take; clhip_gather_tasks_u8 with idx = arange when there is neither a transform nor a shuffle): `.x`, `.frames`,
     `last_idx` and `last_idx_host` behave as in augmented mode, `.transform` stays what the dataset carries.  The table of the
     byte values is uploaded once per loader.  Batches, labels and the consumption of the generators are those of the loader
-    over `dataset.decoded()`."""
+    over `dataset.decoded()`.
+    A RandomPadCropFlip is served by the same steps too: (top, left, flip, h, w) rows from draw_pad_crop_flip, the launch
+    clhip_gather_tasks_pad_crop_flip[_u8]; a crop larger than the stored frame is legal when the padded image holds it.  The
+    fill vector (on byte frames lut[c][fill byte of c]) is uploaded once per loader."""
 
     transform = None
     _resized = False
+    _padded = False
+    _fill = None              # device float32 [C] of a RandomPadCropFlip, output domain
     _norm = None              # (mean, std) of byte frames
     _lut = None
     base_seed = None
@@ -403,12 +531,15 @@ class DeviceLoader:
             raise ValueError("%s needs frames [n, C, Hs, Ws] of one shape" % type(transform).__name__)
         C, Hs, Ws = (int(v) for v in xs[0].shape[1:])
         th, tw = transform.size
-        if (th > Hs or tw > Ws) and not isinstance(transform, RandomResizedCropFlip):      # (a resized window may be enlarged)
+        if (th > Hs or tw > Ws) and isinstance(transform, RandomCropFlip):      # (a resized window may be enlarged, a padded image larger)
             raise ValueError("%s: crop %d x %d of frames %d x %d" % (type(transform).__name__, th, tw, Hs, Ws))
         if transform.extents is not None and len(transform.extents) != self.n:
             raise ValueError("%s: %d extents for %d frames" % (type(transform).__name__, len(transform.extents), self.n))
         self.transform = transform
         self._resized = isinstance(transform, RandomResizedCropFlip)
+        self._padded = isinstance(transform, RandomPadCropFlip)
+        if self._padded:
+            transform.fill_values(C, byte=self._norm is not None)
         self.frames = xs
         self.geometry = (C, Hs, Ws, th, tw)
         self.x = torch.empty((0, C, th, tw), dtype=torch.float32, device=xs[0].device)    # (row shape only: what engine_for reads; no memory)
@@ -430,11 +561,12 @@ class DeviceLoader:
         return torch.randperm(self.n, generator=g)
 
     def epoch_params(self, perm):
-        """Host int32 table of the epoch whose order() returned `perm` (None: dataset order): [n][3] rows of draw_crop_flip, or
-        [n][5] rows of draw_resized_crop_flip."""
+        """Host int32 table of the epoch whose order() returned `perm` (None: dataset order): [n][3] rows of draw_crop_flip,
+        [n][5] rows of draw_resized_crop_flip, or [n][5] rows of draw_pad_crop_flip."""
         g = torch.Generator()
         g.manual_seed(self.base_seed)
-        return (draw_resized_crop_flip if self._resized else draw_crop_flip)(self.n, self.transform, self.geometry[1:3], g, order=perm)
+        draw = draw_resized_crop_flip if self._resized else draw_pad_crop_flip if self._padded else draw_crop_flip
+        return draw(self.n, self.transform, self.geometry[1:3], g, order=perm)
 
     def _augmented(self, perm):
         from . import ops
@@ -442,20 +574,29 @@ class DeviceLoader:
             self._table = ops.task_table(*self._sources, self.device)
             if self._norm is not None:
                 self._lut = norm_lut(*self._norm).to(self.device)
+            if self._padded:
+                fill = self.transform.fill_values(self.geometry[0], byte=self._norm is not None)
+                if self._norm is not None:          # a byte means what the table says
+                    lut = norm_lut(*self._norm)
+                    fill = [lut[c, v] for c, v in enumerate(fill)]
+                self._fill = torch.tensor([float(v) for v in fill], dtype=torch.float32).to(self.device)
         params = self.epoch_params(perm).to(self.device) if self.transform is not None else None
         idx_host = torch.arange(self.n) if perm is None else perm
         idx = idx_host.to(self.device)
+        pad = (self.transform.padding_mode, self.transform.padding, self._fill) if self._padded else ()
         if self._norm is None:
-            gather, lut = (ops.gather_tasks_resized_crop_flip if self._resized else ops.gather_tasks_crop_flip), ()
+            gather, lut = (ops.gather_tasks_resized_crop_flip if self._resized else ops.gather_tasks_pad_crop_flip if self._padded
+                           else ops.gather_tasks_crop_flip), ()
         else:
-            gather, lut = (ops.gather_tasks_resized_crop_flip_u8 if self._resized else ops.gather_tasks_crop_flip_u8), (self._lut,)
+            gather, lut = (ops.gather_tasks_resized_crop_flip_u8 if self._resized else ops.gather_tasks_pad_crop_flip_u8
+                           if self._padded else ops.gather_tasks_crop_flip_u8), (self._lut,)
         for s in range(0, self.n, self.batch_size):
             self.last_idx, self.last_idx_host = idx[s:s + self.batch_size], idx_host[s:s + self.batch_size]
             if params is None:                      # byte frames without a transform: whole rows
                 x, y = ops.gather_tasks_u8(self._table, self.row_shape[0], math.prod(self.row_shape[1:]), self._lut, self.last_idx)
                 yield x.view((x.shape[0],) + self.row_shape), y
             else:
-                yield gather(self._table, self.geometry, *lut, self.last_idx, params[s:s + self.batch_size])
+                yield gather(self._table, self.geometry, *pad, *lut, self.last_idx, params[s:s + self.batch_size])
 
     def __iter__(self):
         perm = self.order()
@@ -511,7 +652,7 @@ class TaskList(Dataset):
 class MultiTaskLoader(DeviceLoader):
     """DeviceLoader over a TaskList: same length, order and consumption of the global RNG, but a batch is gathered straight
     out of the per-task tensors (clhip_gather_tasks) — the merged copy `ConcatTasks` makes (a second copy in HBM of every
-    task the cache already holds) is never built.  Tasks that carry a RandomCropFlip or a RandomResizedCropFlip (all of one class and
+    task the cache already holds) is never built.  Tasks that carry a RandomCropFlip, a RandomResizedCropFlip or a RandomPadCropFlip (all of one class and
     equal parameters, or none) are served augmented as DeviceLoader describes, the crop and flip done in the same gather.
     Tasks that hold byte frames (all of them, with equal mean and std) are decoded in the same gather; no merged copy either."""
 

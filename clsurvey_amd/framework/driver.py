@@ -110,6 +110,13 @@ def build_parser():
                         "pass sees a fresh RandomResizedCrop to hw x hw (scale 0.08 - 1, ratio 3/4 - 4/3, antialiased bilinear) + "
                         "horizontal flip of them, the cropped Tiny-ImageNet rule (data/tinyimgnet_dataprep.py:105-122); evaluation "
                         "reads the centre crops.  0: no augmentation")
+    p.add_argument("--rnd_pad", type=int, default=0,
+                   help="with --synthetic, instead of --rnd_margin / --rnd_resized: images are generated at hw, no margin, and every "
+                        "training pass sees a fresh RandomCrop(hw, padding=M) + horizontal flip of them (pad, crop, flip: the "
+                        "CIFAR-style rule), padded inside the batch gather; evaluation reads the images as they are.  GEM, the "
+                        "rehearsal baselines and iCaRL refuse such tasks (padded replay is not built).  0: no augmentation")
+    p.add_argument("--pad_mode", type=str, default=None, choices=("constant", "edge", "reflect", "symmetric"),
+                   help="with --rnd_pad: torchvision's padding_mode (default constant, fill 0.0 = byte 128 of --u8_frames)")
     return p
 
 
@@ -791,6 +798,14 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         raise SystemExit("--rnd_margin and --rnd_resized exclude each other: a train split carries one transform")
     if args.rnd_resized < 0:
         raise SystemExit("--rnd_resized >= 0")
+    if args.rnd_pad < 0:
+        raise SystemExit("--rnd_pad >= 0")
+    if args.rnd_pad and (dataset is not None or not args.synthetic):
+        raise SystemExit("--rnd_pad belongs to --synthetic: a dataset object says itself which of its files are augmented")
+    if args.rnd_pad and (args.rnd_margin or args.rnd_resized):
+        raise SystemExit("--rnd_pad excludes --rnd_margin and --rnd_resized: a train split carries one transform")
+    if args.pad_mode is not None and not args.rnd_pad:
+        raise SystemExit("--pad_mode belongs with --rnd_pad: it is the padding mode of that crop")
     if dataset is None and args.synthetic:
         from .tasks import SyntheticTaskSequence
         fields = args.synthetic.split(",")
@@ -801,7 +816,7 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
                                         sizes=(n_tr, n_va, n_te), hw=hw, noise=float(fields[6]) if len(fields) > 6 else 1.0,
                                         kind=kind, blobs=blobs, seed=int(fields[12]) if len(fields) > 12 else 7,
                                         rnd_margin=args.rnd_margin, rnd_always=True, rnd_resized=args.rnd_resized,
-                                        u8_frames=args.u8_frames)
+                                        u8_frames=args.u8_frames, rnd_pad=args.rnd_pad, pad_mode=args.pad_mode or "constant")
     set_random(7)                                                 # utils.init -> set_random()
     if method is None:
         method = methods.parse(args.method_name)

@@ -13,13 +13,13 @@ from collections import OrderedDict
 
 import torch
 
-from ..data import ByteTaskDataset, RandomCropFlip, RandomResizedCropFlip, TensorTaskDataset, synthetic_task
+from ..data import PAD_MODES, ByteTaskDataset, RandomCropFlip, RandomPadCropFlip, RandomResizedCropFlip, TensorTaskDataset, synthetic_task
 
 
 class SyntheticTaskSequence(object):
     def __init__(self, root, task_count=10, classes_per_task=20, sizes=(8000, 2000, 1000), hw=64, seed=7, noise=1.0,
                  name="synthetic_tiny_imagenet", kind="protos", blobs=None, rnd_margin=0, rnd_always=False, rnd_resized=0,
-                 u8_frames=False):
+                 u8_frames=False, rnd_pad=0, pad_mode="constant"):
         """rnd_margin = m > 0: images are generated at (hw + m)^2; task_N.pth.tar holds their centre hw^2 crops (the Resize(256) /
         CenterCrop(224) of get_transforms(), data/inaturalist_dataprep.py:256-277) and task_N_rndtrans.pth.tar (named after
         data/dataset.py:108) the same images with the full frames + RandomCropFlip((hw, hw)) as `train` split.  rnd_always: the
@@ -32,7 +32,12 @@ class SyntheticTaskSequence(object):
         not exist.
         u8_frames: the same generated images, quantised as clamp(round(x * 48 + 128), 0, 255), are stored as ByteTaskDatasets
         with mean = 128 / 255 and std = 48 / 255 on every channel (what a pipeline that keeps the decoded images hands over), in
-        both files of a task and with either margin option.  False: as if the option did not exist."""
+        both files of a task and with either margin option.  False: as if the option did not exist.
+        rnd_pad = m > 0 (instead of rnd_margin / rnd_resized): the CIFAR-style rule, RandomCrop(hw, padding=m) + flip of images
+        ALREADY at the net's input size.  Images are generated at hw^2, no margin; both files of a task hold the same images and
+        the `train` split of task_N_rndtrans.pth.tar carries RandomPadCropFlip((hw, hw), padding=m, padding_mode=pad_mode) with
+        fill 0.0, or with u8_frames byte 128, which decodes to exactly 0.0 under the mean and std above.  0: as if the option
+        did not exist."""
         self.name = name
         self.argname = name
         self.test_results_dir = name
@@ -53,10 +58,14 @@ class SyntheticTaskSequence(object):
         self.rnd_always = bool(rnd_always)
         self.rnd_resized = int(rnd_resized)
         self.u8_frames = bool(u8_frames)
-        if self.rnd_margin < 0 or self.rnd_resized < 0:
-            raise ValueError("SyntheticTaskSequence: rnd_margin >= 0 and rnd_resized >= 0")
-        if self.rnd_margin and self.rnd_resized:
-            raise ValueError("SyntheticTaskSequence: rnd_margin or rnd_resized, not both")
+        self.rnd_pad = int(rnd_pad)
+        self.pad_mode = str(pad_mode)
+        if self.rnd_margin < 0 or self.rnd_resized < 0 or self.rnd_pad < 0:
+            raise ValueError("SyntheticTaskSequence: rnd_margin >= 0, rnd_resized >= 0 and rnd_pad >= 0")
+        if bool(self.rnd_margin) + bool(self.rnd_resized) + bool(self.rnd_pad) > 1:
+            raise ValueError("SyntheticTaskSequence: one of rnd_margin, rnd_resized and rnd_pad, not several")
+        if self.pad_mode not in PAD_MODES:
+            raise ValueError("SyntheticTaskSequence: pad_mode is one of %s, got %r" % (PAD_MODES, pad_mode))
 
     def get_taskname(self, task_index):
         return str(task_index)
@@ -70,7 +79,10 @@ class SyntheticTaskSequence(object):
             out["rnd_margin"] = self.rnd_margin
         if self.rnd_resized:
             out["rnd_resized"] = self.rnd_resized
-        if (self.rnd_margin or self.rnd_resized) and rnd_transform:
+        if self.rnd_pad:
+            out["rnd_pad"] = self.rnd_pad
+            out["pad_mode"] = self.pad_mode
+        if (self.rnd_margin or self.rnd_resized or self.rnd_pad) and rnd_transform:
             out["rnd_transform"] = True
         if self.u8_frames:
             out["u8_frames"] = True
@@ -90,6 +102,10 @@ class SyntheticTaskSequence(object):
         m = self.rnd_margin or self.rnd_resized
         d = synthetic_task(self.sizes[0], self.sizes[1], self.sizes[2], self.n_classes, self.hw + m,
                            seed=want["seed"], noise=self.noise, kind=self.kind, blobs=self.blobs)
+        if self.rnd_pad:                           # no margin: the padded crop jitters frames of the output size
+            spec = RandomPadCropFlip((self.hw, self.hw), padding=self.rnd_pad, fill=128 if self.u8_frames else 0.0,
+                                     padding_mode=self.pad_mode) if rnd_transform else None
+            return {s: self._split(v.x, v.y, v.classes, transform=spec if s == "train" else None) for s, v in d.items()}
         if not m:
             return {s: self._split(v.x, v.y, v.classes) for s, v in d.items()} if self.u8_frames else d
         o = int(round(m / 2.0))                    # torchvision's center_crop offset
@@ -104,10 +120,10 @@ class SyntheticTaskSequence(object):
         file of ANOTHER spec (other kind / blobs / noise / sizes / seed under the same results root) is an error, not a hit:
         the results tree beside it holds success tokens and models of that other data.
         task_name=None asks for a pre-merged file of ALL tasks (Joint.grid_datafetch, method.py:1204): there is none.
-        With a margin (rnd_margin or rnd_resized), rnd_transform (or rnd_always) selects task_N_rndtrans.pth.tar, which has its own sidecar."""
+        With a margin (rnd_margin or rnd_resized) or rnd_pad, rnd_transform (or rnd_always) selects task_N_rndtrans.pth.tar, which has its own sidecar."""
         if task_name is None:
             return None
-        rnd = bool(self.rnd_margin or self.rnd_resized) and (bool(rnd_transform) or self.rnd_always)
+        rnd = bool(self.rnd_margin or self.rnd_resized or self.rnd_pad) and (bool(rnd_transform) or self.rnd_always)
         stem = "task_%s%s" % (task_name, "_rndtrans" if rnd else "")
         path = os.path.join(self.root, self.name, stem + ".pth.tar")
         side = os.path.join(self.root, self.name, stem + ".spec.json")

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 from ..data import load_task_datasets
 
-from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, RandomResizedCropFlip
+from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, RandomPadCropFlip, RandomResizedCropFlip
 from .exemplar import batch_source
 from . import gem as G
 from . import rehearsal as R
@@ -130,6 +130,16 @@ def exemplar_split(args, dset_sizes):
     return args.total_batch_size + args.n_exemplars_to_append_per_batch
 
 
+def refuse_padded_replay(who, train):
+    """A train split carrying a RandomPadCropFlip is refused by every method that replays stored exemplars (GEM, the rehearsal
+    baselines, iCaRL): the exemplar assemblies and the memory loaders crop stored frames without padding.  Decided on the
+    split alone, before any loader or device is needed."""
+    spec = getattr(train, "transform", None)
+    if isinstance(spec, RandomPadCropFlip):
+        raise NotImplementedError("%s: padded replay is not built: exemplars are replayed with RandomCropFlip (or, opt-in, "
+                                  "RandomResizedCropFlip) only, the train split carries %r" % (who, spec))
+
+
 def main(overwrite_args, nc_per_task, device="cuda"):
     """main_rehearsal.py:69-255 for method 'gem' and the rehearsal baselines ('baseline_rehearsal_{partial,full}_mem').
     overwrite_args['exemplar_dtype'] (not in the reference; default 'float32'): 'uint8' stores the exemplars of an augmented byte
@@ -173,6 +183,7 @@ def main(overwrite_args, nc_per_task, device="cuda"):
 
     dsets = load_task_datasets(args.dataset_path)
     args.task_imgfolders = dsets
+    refuse_padded_replay("rehearsal method %r" % (args.method,), dsets["train"])
     resized = isinstance(getattr(dsets["train"], "transform", None), RandomResizedCropFlip)
     if resized and not args.exemplar_resized:
         # by default the exemplar wrappers replay stored frames through clhip_rehearsal_assemble_crop_flip, which does not resample

@@ -96,6 +96,7 @@ def main(overwrite_args, nc_per_task, device="cuda"):
 
     dsets = load_task_datasets(args.dataset_path, device)
     args.task_imgfolders = dsets
+    gem_main.refuse_padded_replay("icarl", dsets["train"])           # with or without exemplar_frames
     frames = _frame_arguments(args, dsets["train"]) if args.exemplar_frames else {}
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}

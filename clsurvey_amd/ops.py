@@ -904,6 +904,50 @@ def gather_tasks_resized_crop_flip_u8(table, geometry, lut, idx, params, x_out=N
     return _gather_window_u8("clhip_gather_tasks_resized_crop_flip_u8", 5, table, geometry, lut, idx, params, x_out, labels_out)
 
 
+PAD_MODES = ("constant", "edge", "reflect", "symmetric")     # the `mode` argument of the padded gathers is the position here
+
+
+def _gather_pad(entry, table, geometry, mode, pads, fill, lut, idx, params, x_out, labels_out):
+    _chk(table, fill, idx, params, x_out, labels_out, *lut)
+    C, Hs, Ws, th, tw = (int(v) for v in geometry)
+    pl, pt, pr, pb = (int(v) for v in pads)
+    mode = PAD_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    assert idx.dtype == torch.int64 and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 4
+    assert fill.dtype == torch.float32 and tuple(fill.shape) == (C,) and fill.is_contiguous(), "fill: float32 [C]"
+    for t in lut:
+        _chk_lut(t, C)
+    B = idx.shape[0]
+    assert params.dtype == torch.int32 and tuple(params.shape) == (B, 5) and params.is_contiguous()
+    if x_out is None:
+        x_out = torch.empty((B, C, th, tw), dtype=torch.float32, device=idx.device)
+    if labels_out is None:
+        labels_out = torch.empty((B,), dtype=torch.int64, device=idx.device)
+    row_elems = C * th * tw
+    assert x_out.dtype == torch.float32 and x_out.numel() >= B * row_elems and labels_out.numel() >= B
+    xf, step = x_out.view(-1), 65535                     # one launch takes at most 65535 rows (grid y): larger batches in pieces
+    for s in range(0, max(B, 1), step):
+        n = min(step, B - s)
+        check(getattr(_lib.lib(), entry)(_ptr(table), table.shape[0], C, Hs, Ws, th, tw, mode, pl, pt, pr, pb, _ptr(fill),
+                                         *(_ptr(t) for t in lut), _ptr(idx[s:s + n]), _ptr(params[s:s + n]), n,
+                                         _ptr(xf[s * row_elems:]), _ptr(labels_out[s:]), _stream()), entry)
+    return x_out, labels_out
+
+
+def gather_tasks_pad_crop_flip(table, geometry, mode, pads, fill, idx, params, x_out=None, labels_out=None):
+    """clhip_gather_tasks_pad_crop_flip: geometry = (C, Hs, Ws, th, tw) of the stored frames and of the output, mode one of
+    PAD_MODES (or its position), pads = (left, top, right, bottom), fill device float32[C] in the domain of the stored frames,
+    idx device int64[B] GLOBAL sample numbers, params device int32[B, 5] of (top, left, flip, h, w) per batch position (the
+    corner in the sample's unpadded coordinates), both checked by the caller.  Returns (x_out [B, C, th, tw], labels_out [B])."""
+    return _gather_pad("clhip_gather_tasks_pad_crop_flip", table, geometry, mode, pads, fill, (), idx, params, x_out, labels_out)
+
+
+def gather_tasks_pad_crop_flip_u8(table, geometry, mode, pads, fill, lut, idx, params, x_out=None, labels_out=None):
+    """clhip_gather_tasks_pad_crop_flip_u8: gather_tasks_pad_crop_flip out of uint8 frames, decoded through lut (device float32
+    [C, 256]); fill stays float32[C] in the OUTPUT domain (lut[c, fill byte of c]): bitwise gather_tasks_pad_crop_flip of the
+    decoded frames."""
+    return _gather_pad("clhip_gather_tasks_pad_crop_flip_u8", table, geometry, mode, pads, fill, (lut,), idx, params, x_out, labels_out)
+
+
 def _assemble_crop_flip(entry, frame_dtype, ncols, geometry, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0,
                         ring_rows, gather, params, x_mix, y_mix):
     """The frame-mode assembly entries: ncols = 3, params rows (top, left, flip); 5, (top, left, h, w, flip)."""

@@ -759,6 +759,47 @@ int clhip_gather_tasks_resized_crop_flip(const clhip_task_src* tasks_dev, int T,
                                          const int64_t* idx, const int* params, int B, float* x_out, int64_t* labels_out,
                                          void* stream);
 
+/* torchvision's RandomCrop(size, padding, fill, padding_mode) -> RandomHorizontalFlip: the standard augmentation of the
+ * CIFAR-style split benchmarks (RandomCrop(32, padding = 4) + flip), and the only translation jitter for frames already at the
+ * net's input size.  The reference's own Composes do not pad (data/recogseq_dataprep.py:56-57 and
+ * data/inaturalist_dataprep.py:240-241 crop a LARGER Resize(256) frame); with it a task file stores frames of the output size
+ * and no margin.  It replaces F.pad of the whole task tensor on the host followed by clhip_gather_tasks_crop_flip.
+ *
+ *   gather_tasks_pad_crop_flip   clhip_gather_tasks_crop_flip over the PADDED image of each sample.  params is device
+ *                            int32[B][5] of (top, left, flip, h, w): (h, w) the valid extent of the sample inside its stored
+ *                            frame [C][Hs][Ws] (top-left anchored), (top, left) the window's corner in the sample's UNPADDED
+ *                            coordinates, top in [-pt, h + pb - th] and left in [-pl, w + pr - tw] (uniform over the padded
+ *                            image of (h + pt + pb) x (w + pl + pr), RandomCrop.get_params; th > Hs is legal when the padded
+ *                            image holds it).  x_out is [B][C][th][tw] and
+ *                              x_out[b][c][y][x] = P(c, top + y, left + (flip ? tw - 1 - x : x))      (pad, crop, then hflip)
+ *                              P(c, i, j) = frame(idx[b])[c][m(i, h)][m(j, w)], or fill[c] where a map says so
+ *                            m(s, n) = s inside [0, n), otherwise by mode:
+ *                              0 constant   nowhere: the element is fill[c], nothing is loaded
+ *                              1 edge       clamp(s, 0, n - 1)
+ *                              2 reflect    -s below 0, 2 (n - 1) - s at or above n     [1,2,3,4], pad 2 -> [3,2,1,2,3,4,3,2]
+ *                              3 symmetric  -s - 1 below 0, 2 n - 1 - s at or above n                    -> [2,1,1,2,3,4,4,3]
+ *                            fill is device float[C] in the OUTPUT domain (the stored, normalised values), read in every mode.
+ *                            A copy: bitwise.  A row copies nothing and writes label -1 when its sample number is outside
+ *                            [0, cum_rows[T-1]), flip is outside {0, 1}, h is outside [1, Hs] or w outside [1, Ws], top or
+ *                            left is outside its range above, or the pads exceed the mode's limit for (h, w) (reflect: every
+ *                            pad <= extent - 1 on its axis, symmetric: <= extent, as torch; one reflection then suffices).
+ *                            No address outside the sample's h x w extent is formed in any mode.  Callers draw and check the
+ *                            table on the host.  CLHIP_EINVAL before any launch: the checks of clhip_gather_tasks, fill ==
+ *                            NULL, C, Hs, Ws, th or tw < 1, Hs or Ws > CLHIP_PAD_MAX_EXTENT, mode outside 0..3, a pad < 0 or
+ *                            > CLHIP_PAD_MAX.  B == 0 returns 0.  Grid, lines per block (clhip_crop_rows_per_block) and
+ *                            stores as clhip_gather_tasks_crop_flip: float4 stores when tw % 4 == 0 and x_out is 16-byte
+ *                            aligned, dword-aligned loads; 4 columns are one wide load only when all 4 lie inside [0, w).
+ *   gather_tasks_pad_crop_flip_u8   the same for byte frames (the byte-frames section below): the frame's bytes are decoded
+ *                            through the device table lut (fp32 [C][256], NULL is CLHIP_EINVAL), staged per channel in LDS;
+ *                            fill STAYS float[C] in the output domain (callers pass lut[c][fill byte of c]), so the result is
+ *                            bitwise the fp32 entry's on the decoded frames.  Byte loads, one dword load per 4 interior columns
+ *                            only behind a test of that address. */
+#define CLHIP_PAD_MAX 32767
+#define CLHIP_PAD_MAX_EXTENT (1 << 30)
+int clhip_gather_tasks_pad_crop_flip(const clhip_task_src* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, int mode, int pl,
+                                     int pt, int pr, int pb, const float* fill, const int64_t* idx, const int* params, int B,
+                                     float* x_out, int64_t* labels_out, void* stream);
+
 /* Host read-outs of the launch plans of the window entries (the gathers above, clhip_rehearsal_assemble_*crop_flip*,
  * clhip_icarl_assemble_*crop_flip*); nothing is launched and no device is needed.  Test infrastructure: a test asserts through
  * them that a geometry still splits a channel plane into the blocks it was chosen for.
@@ -836,6 +877,10 @@ int clhip_gather_tasks_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, i
 int clhip_gather_tasks_resized_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw,
                                             const float* lut, const int64_t* idx, const int* params, int B, float* x_out,
                                             int64_t* labels_out, void* stream);
+/* (documented with clhip_gather_tasks_pad_crop_flip above) */
+int clhip_gather_tasks_pad_crop_flip_u8(const clhip_task_src_u8* tasks_dev, int T, int C, int Hs, int Ws, int th, int tw, int mode,
+                                        int pl, int pt, int pr, int pb, const float* fill, const float* lut, const int64_t* idx,
+                                        const int* params, int B, float* x_out, int64_t* labels_out, void* stream);
 int clhip_rehearsal_assemble_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
                                           const float* lut, const uint8_t* src_frames, long src_rows, const int64_t* src_idx,
                                           uint8_t* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
