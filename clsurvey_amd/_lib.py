@@ -194,6 +194,8 @@ SIGNATURES = {
     "clhip_gather_tasks_resized_crop_flip_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "clhip_rehearsal_assemble_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
     "clhip_rehearsal_assemble_resized_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
+    "clhip_rehearsal_assemble_pad_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
+    "clhip_rehearsal_assemble_pad_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _l, _p, _p, _p, _l, _l, _i, _p, _p, _i, _p, _p, _p]),
     "clhip_icarl_herd": (_i, [_p, _l, _i, _p, C.POINTER(IcarlClass), _i, _p, _l, _p]),
     "clhip_icarl_herd_wide_ws": (_z, [_i, _i]),
     "clhip_icarl_herd_wide": (_i, [_p, _l, _i, _p, C.POINTER(IcarlClass), _i, _p, _l, _p, _z, _p]),

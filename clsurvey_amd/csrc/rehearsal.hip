@@ -9,6 +9,9 @@
 //                                  copies, the gathered exemplars are decoded through the table where they are loaded
 //   rehearsal_assemble_resized_crop_flip[_u8]  the train transform is RandomResizedCrop + flip: the gathered exemplars are
 //                                  RESAMPLED in the same launch, by the block body of the loaders' resizing gather
+//   rehearsal_assemble_pad_crop_flip[_u8]  the train transform is RandomCrop(size, padding, fill, padding_mode) + flip: the
+//                                  gathered exemplars are windows of their PADDED frames, by the block body of the loaders'
+//                                  padded gather
 #include "resized_crop.hpp"
 #include <type_traits>
 
@@ -238,18 +241,86 @@ __global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_rz_kernel(const 
                                a.kty, lut_c, a.x_mix + (((size_t)(a.B + e) * a.C + c) * a.th + y0) * a.tw);
 }
 
+// The frame-mode assembly under RandomCrop(size, padding, fill, padding_mode) + flip: the grid and the copy / ring runs of
+// rehearsal_assemble_cf_kernel; the exemplar run is E x (C * chunks) blocks, each copying rpb = cf_rows_per_block(tw) output
+// lines of the window of store[gather[e]]'s PADDED image by cf_copy_window_pad (crop_flip.hpp), the block body of
+// gather_pad_crop_flip_kernel (augment.hip): bitwise that gather's result for the same frame and params.  params: int32[E][5] of
+// (top, left, flip, h, w), the corner in the frame's unpadded coordinates, (h, w) its valid extent; fill: float[C], output domain.
+// A gather row outside [0, store_rows) or a row that gather lists as bad (flip outside {0, 1}, h outside [1, Hs], w outside
+// [1, Ws], top outside [-pt, h + pb - th], left outside [-pl, w + pr - tw], pads over the mode's limit for (h, w)) copies nothing
+// and writes label -1 (64-bit compares: a bad table may hold any int32); every source coordinate is mapped into the h x w extent,
+// so no address outside it is formed.  MODE (the padding mode) is a template argument, as in augment.hip.
+template <typename T>
+struct assemble_pad_args {
+    assemble_cf_args<T> a;
+    int pl, pt, pr, pb;
+    const float* fill;                                                         // [C]
+};
+
+template <bool VEC, int MODE, typename T>
+__global__ __launch_bounds__(ASM_BLOCK) void rehearsal_assemble_pad_kernel(const assemble_pad_args<T> p) {
+    const assemble_cf_args<T>& a = p.a;
+    unsigned b = blockIdx.x;
+    if (assemble_copy_ring(a, b)) return;
+    // (the role and the bad-row test are block-uniform: every thread of a block reaches the barrier below or none does)
+    const unsigned e = b / a.crop_blocks;
+    const int k = (int)(b - e * a.crop_blocks);
+    const long g = a.gather[e];
+    const int top = a.params[5 * e], left = a.params[5 * e + 1], flip = a.params[5 * e + 2], h = a.params[5 * e + 3],
+              w = a.params[5 * e + 4];
+    int64_t* ydst = a.y_mix + a.B + e;
+    constexpr int lim = MODE == CF_PAD_REFLECT ? 1 : 0;                        // reflect: pad <= extent - 1, symmetric: pad <= extent
+    const bool one_reflection = MODE < CF_PAD_REFLECT || (max(p.pl, p.pr) <= w - lim && max(p.pt, p.pb) <= h - lim);
+    if (g < 0 || g >= a.store_rows || (flip != 0 && flip != 1) || h < 1 || h > a.Hs || w < 1 || w > a.Ws || top < -p.pt ||
+        (int64_t)top > (int64_t)h + p.pb - a.th || left < -p.pl || (int64_t)left > (int64_t)w + p.pr - a.tw || !one_reflection) {
+        if (k == 0 && threadIdx.x == 0) *ydst = -1;
+        return;
+    }
+    if (k == 0 && threadIdx.x == 0) *ydst = a.store_y[g];
+    const int c = k / a.chunks;
+    const int y0 = (k - c * a.chunks) * a.rpb;
+    const int nrows = min(a.rpb, a.th - y0);
+    float* dst = a.x_mix + (((size_t)(a.B + e) * a.C + c) * a.th + y0) * a.tw;
+    const float fill_c = p.fill[c];
+    typedef const T __attribute__((address_space(1))) gelem;                   // (device memory: global_load, not flat_load)
+    gelem* plane = (gelem*)(a.store + ((size_t)g * a.C + c) * a.Hs * a.Ws);
+    if constexpr (std::is_same<T, uint8_t>::value) {
+        __shared__ float lut_s[257];                                           // the table of channel c (CF_BLOCK == 256: one entry each)
+        lut_s[threadIdx.x] = a.lut[c * 256 + (int)threadIdx.x];
+        if (threadIdx.x == 0) lut_s[256] = fill_c;                             // entry 256: what a fill element decodes to
+        __syncthreads();
+        cf_copy_window_pad<VEC, MODE>(plane, a.Ws, h, w, top + y0, left, fill_c, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip,
+                                      cf_load_u8{lut_s});
+    } else {
+        cf_copy_window_pad<VEC, MODE>(plane, a.Ws, h, w, top + y0, left, fill_c, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip);
+    }
+}
+
 }  // namespace
+
+// What the padded entries add to the frame-mode arguments.
+struct assemble_pad { int mode, pl, pt, pr, pb; const float* fill; };
 
 // One body for the frame-mode entries: T selects the frames' element type, lut is NULL for floats; RESIZED: gather_params rows
 // are (top, left, h, w, flip) and the exemplar run resamples, under a plan made here for the frame (needed only with E > 0).
+// pad (never with RESIZED): gather_params rows are (top, left, flip, h, w) and the exemplar run copies windows of the padded frames.
 template <typename T, bool RESIZED>
 static int assemble_frames(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
                            const float* lut, const T* src_frames, long src_rows, const int64_t* src_idx, T* store_frames,
                            int64_t* store_labels, long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
-                           const int* gather_params, int E, float* x_mix, int64_t* labels_mix, void* stream) {
+                           const int* gather_params, int E, float* x_mix, int64_t* labels_mix, void* stream,
+                           const assemble_pad* pad = nullptr) {
     if (B < 0 || E < 0 || ring_rows < 0 || store_rows < 0 || src_rows < 0) return CLHIP_EINVAL;
     if (C < 1 || th < 1 || tw < 1 || Hs < 1 || Ws < 1) return CLHIP_EINVAL;
-    if (!RESIZED && (th > Hs || tw > Ws)) return CLHIP_EINVAL;                   // (a resized window may be enlarged)
+    if (!RESIZED && !pad && (th > Hs || tw > Ws)) return CLHIP_EINVAL;           // (a resized window may be enlarged, a padded image larger)
+    if (pad) {
+        if (Hs > CLHIP_PAD_MAX_EXTENT || Ws > CLHIP_PAD_MAX_EXTENT) return CLHIP_EINVAL;   // (2 n - 1 - s stays an int)
+        if (pad->mode < CF_PAD_CONSTANT || pad->mode > CF_PAD_SYMMETRIC) return CLHIP_EINVAL;
+        if (pad->pl < 0 || pad->pt < 0 || pad->pr < 0 || pad->pb < 0 || pad->pl > CLHIP_PAD_MAX || pad->pt > CLHIP_PAD_MAX ||
+            pad->pr > CLHIP_PAD_MAX || pad->pb > CLHIP_PAD_MAX)
+            return CLHIP_EINVAL;
+        if (E > 0 && !pad->fill) return CLHIP_EINVAL;                            // (a ring-only call pads nothing)
+    }
     if (ring_rows > B) return CLHIP_EINVAL;                                      // ring rows are a prefix of the batch
     if (E > 0 && (!x_mix || !gather_rows || !gather_params)) return CLHIP_EINVAL;
     if (std::is_same<T, uint8_t>::value && E > 0 && !lut) return CLHIP_EINVAL;   // (a ring-only call decodes nothing)
@@ -291,7 +362,18 @@ static int assemble_frames(const float* x, const int64_t* labels_i64, int B, int
     a.vec_frame = (frame_elems * sizeof(T)) % 16 == 0 && aligned16(src_frames) && aligned16(store_frames);
     const bool vec = tw % 4 == 0 && aligned16(x_mix);
     const dim3 grid((unsigned)blocks), block(ASM_BLOCK);
-    if constexpr (RESIZED) {
+    if (pad) {
+        const assemble_pad_args<T> p{a, pad->pl, pad->pt, pad->pr, pad->pb, pad->fill};
+#define CLHIP_PAD_LAUNCH(VEC, MODE) \
+    hipLaunchKernelGGL((rehearsal_assemble_pad_kernel<VEC, MODE, T>), grid, block, 0, as_stream(stream), p)
+        switch (pad->mode) {
+        case CF_PAD_CONSTANT: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_CONSTANT); else CLHIP_PAD_LAUNCH(false, CF_PAD_CONSTANT); break;
+        case CF_PAD_EDGE: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_EDGE); else CLHIP_PAD_LAUNCH(false, CF_PAD_EDGE); break;
+        case CF_PAD_REFLECT: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_REFLECT); else CLHIP_PAD_LAUNCH(false, CF_PAD_REFLECT); break;
+        default: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_SYMMETRIC); else CLHIP_PAD_LAUNCH(false, CF_PAD_SYMMETRIC); break;
+        }
+#undef CLHIP_PAD_LAUNCH
+    } else if constexpr (RESIZED) {
         if (vec) hipLaunchKernelGGL((rehearsal_assemble_rz_kernel<true, T>), grid, block, lds, as_stream(stream), a);
         else hipLaunchKernelGGL((rehearsal_assemble_rz_kernel<false, T>), grid, block, lds, as_stream(stream), a);
     } else {
@@ -368,6 +450,29 @@ int clhip_rehearsal_assemble_resized_crop_flip_u8(const float* x, const int64_t*
     return assemble_frames<uint8_t, true>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, src_frames, src_rows, src_idx, store_frames,
                                           store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
                                           labels_mix, stream);
+}
+
+int clhip_rehearsal_assemble_pad_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                           int mode, int pl, int pt, int pr, int pb, const float* fill, const float* src_frames,
+                                           long src_rows, const int64_t* src_idx, float* store_frames, int64_t* store_labels,
+                                           long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
+                                           const int* gather_params, int E, float* x_mix, int64_t* labels_mix, void* stream) {
+    const assemble_pad pad{mode, pl, pt, pr, pb, fill};
+    return assemble_frames<float, false>(x, labels_i64, B, C, Hs, Ws, th, tw, nullptr, src_frames, src_rows, src_idx, store_frames,
+                                         store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
+                                         labels_mix, stream, &pad);
+}
+
+int clhip_rehearsal_assemble_pad_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th,
+                                              int tw, int mode, int pl, int pt, int pr, int pb, const float* fill, const float* lut,
+                                              const uint8_t* src_frames, long src_rows, const int64_t* src_idx,
+                                              uint8_t* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
+                                              int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
+                                              int64_t* labels_mix, void* stream) {
+    const assemble_pad pad{mode, pl, pt, pr, pb, fill};
+    return assemble_frames<uint8_t, false>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, src_frames, src_rows, src_idx, store_frames,
+                                           store_labels, store_rows, ring_row0, ring_rows, gather_rows, gather_params, E, x_mix,
+                                           labels_mix, stream, &pad);
 }
 
 }  // extern "C"

@@ -99,12 +99,17 @@ def build_parser():
     p.add_argument("--u8_exemplars", action="store_true",
                    help="GEM, the rehearsal baselines and iCaRL (--icarl_frames): the exemplar store holds uint8 frames, decoded where they are replayed (a "
                         "quarter of the store's bytes in HBM and in every checkpoint, bitwise the run on the decoded files).  "
-                        "Belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars): the train "
-                        "splits are augmented byte splits")
+                        "Belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars, or --u8_frames "
+                        "--rnd_pad --padded_exemplars): the train splits are augmented byte splits")
     p.add_argument("--resized_exemplars", action="store_true",
                    help="GEM, the rehearsal baselines and iCaRL (--icarl_frames) with --rnd_resized: the stored exemplar frames are replayed through the "
                         "task's RandomResizedCrop + flip, a fresh window per exemplar and replay, resampled inside the step's batch "
                         "assembly launch.  Without it these methods refuse --rnd_resized tasks")
+    p.add_argument("--padded_exemplars", action="store_true",
+                   help="GEM and the rehearsal baselines with --rnd_pad: the exemplar store holds the tasks' unpadded frames and they "
+                        "are replayed through the task's RandomCrop(hw, padding=M) + flip, a fresh window of the padded frame per "
+                        "exemplar and replay, padded inside the step's batch assembly launch.  Without it these methods refuse "
+                        "--rnd_pad tasks; iCaRL refuses them either way")
     p.add_argument("--rnd_resized", type=int, default=0,
                    help="with --synthetic, instead of --rnd_margin: images are generated M pixels larger than hw and every training "
                         "pass sees a fresh RandomResizedCrop to hw x hw (scale 0.08 - 1, ratio 3/4 - 4/3, antialiased bilinear) + "
@@ -113,8 +118,9 @@ def build_parser():
     p.add_argument("--rnd_pad", type=int, default=0,
                    help="with --synthetic, instead of --rnd_margin / --rnd_resized: images are generated at hw, no margin, and every "
                         "training pass sees a fresh RandomCrop(hw, padding=M) + horizontal flip of them (pad, crop, flip: the "
-                        "CIFAR-style rule), padded inside the batch gather; evaluation reads the images as they are.  GEM, the "
-                        "rehearsal baselines and iCaRL refuse such tasks (padded replay is not built).  0: no augmentation")
+                        "CIFAR-style rule), padded inside the batch gather; evaluation reads the images as they are.  GEM and "
+                        "the rehearsal baselines take such tasks with --padded_exemplars only, iCaRL refuses them (its padded "
+                        "replay is not built).  0: no augmentation")
     p.add_argument("--pad_mode", type=str, default=None, choices=("constant", "edge", "reflect", "symmetric"),
                    help="with --rnd_pad: torchvision's padding_mode (default constant, fill 0.0 = byte 128 of --u8_frames)")
     return p
@@ -791,9 +797,12 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         raise SystemExit("--icarl_frames belongs with --rnd_margin or --rnd_resized: iCaRL stores frames only of augmented tasks")
     if args.resized_exemplars and not args.rnd_resized:
         raise SystemExit("--resized_exemplars belongs with --rnd_resized: it replays the exemplars through the tasks' RandomResizedCrop")
-    if args.u8_exemplars and not (args.u8_frames and (args.rnd_margin or (args.rnd_resized and args.resized_exemplars))):
-        raise SystemExit("--u8_exemplars belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars): a "
-                         "byte exemplar store holds the frames of augmented byte splits")
+    if args.padded_exemplars and not args.rnd_pad:
+        raise SystemExit("--padded_exemplars belongs with --rnd_pad: it replays the exemplars through the tasks' padded RandomCrop")
+    if args.u8_exemplars and not (args.u8_frames and (args.rnd_margin or (args.rnd_resized and args.resized_exemplars) or
+                                                      (args.rnd_pad and args.padded_exemplars))):
+        raise SystemExit("--u8_exemplars belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars, or "
+                         "--u8_frames --rnd_pad --padded_exemplars): a byte exemplar store holds the frames of augmented byte splits")
     if args.rnd_resized and args.rnd_margin:
         raise SystemExit("--rnd_margin and --rnd_resized exclude each other: a train split carries one transform")
     if args.rnd_resized < 0:

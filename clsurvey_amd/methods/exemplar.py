@@ -22,6 +22,12 @@ RandomResizedCrop window of its stored frame, drawn over the frame's own extent 
 (clhip_rehearsal_assemble_resized_crop_flip[_u8], the block body of the loaders' resizing gather); the draws are rows of
 (top, left, h, w, flip).  Store, ring update and extents are those of frame mode.
 
+Padded replay (frame mode with a RandomPadCropFlip spec, the CIFAR-style rule RandomCrop(size, padding) + flip): the store holds
+the UNPADDED frames and the replayed exemplar is a fresh window of its padded frame, drawn over the frame's own extent and padded
+inside the assembly launch (clhip_rehearsal_assemble_pad_crop_flip[_u8], the block body of the loaders' padded gather); the draws
+are rows of (top, left, flip, h, w).  A frame may be smaller than the crop.  The wrapper keeps the spec's fill as a transient
+device vector; on a byte store the spec's fill is bytes and the vector holds what they decode to.
+
 iCaRL in frame mode (icarl.py): the same store of frames, extents and replay draws, but its exemplars are chosen by herding, not
 copied out of the batches, and each carries a distillation row.  Two things need ONE fixed image of a randomly transformed
 frame: the ranking (the herding view, one draw per training image at manage_memory) and the class means of the nearest-mean
@@ -36,7 +42,8 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ..data import RandomCropFlip, RandomResizedCropFlip, _respec, draw_crop_flip, draw_resized_crop_flip, norm_lut
+from ..data import (RandomCropFlip, RandomPadCropFlip, RandomResizedCropFlip, _respec, draw_crop_flip, draw_pad_crop_flip,
+                    draw_resized_crop_flip, norm_lut)
 from ..net import NetEngine
 
 FUSED_MAX_ROWS, FUSED_MAX_SEGS = ops.LOSS_MAX_ROWS, ops.LOSS_MAX_SEGS        # the fused loss's limits (include/clhip.h)
@@ -146,17 +153,18 @@ class ExemplarNet:
     pickle carries the wrapped net, the counters and what _rows_state() returns of the store; engine / workspaces /
     optimizer are rebuilt on load (_bind, then the trainer's init_setup)."""
 
-    _TRANSIENT = ("engine", "A", "stats", "opt", "x_mix", "y_mix", "_acc", "lut")
+    _TRANSIENT = ("engine", "A", "stats", "opt", "x_mix", "y_mix", "_acc", "lut", "fill")
     _TRANSIENT_POLICY = ()          # the dropout policy's state
     _TRANSIENT_EXTRA = ()           # the subclass's own device state
     _HOST_ROWS = ("_rows_ext",)     # rows of _rows_state() that stay on the host
 
     # class-level defaults: a wrapper pickled before frame mode existed loads in crop mode
-    exemplar_transform = None       # RandomCropFlip(size, p) or RandomResizedCropFlip(size, scale, ratio, p) of the replayed
-                                    # exemplars, or None: the store holds crops
+    exemplar_transform = None       # RandomCropFlip(size, p), RandomResizedCropFlip(size, scale, ratio, p) or RandomPadCropFlip(
+                                    # size, padding, fill, padding_mode, p) of the replayed exemplars, or None: the store holds crops
     frame_shape = None              # (C, Hs, Ws) of the stored frames
     frame_norm = None               # (mean, std), CPU fp32 [C] each: the frames are stored as uint8 and mean norm_lut(mean, std)
     lut = None                      # device fp32 [C][256] of a byte store (transient: rebuilt by _bind)
+    fill = None                     # device fp32 [C] of a RandomPadCropFlip, output domain (transient: rebuilt by _bind)
 
     def _init_frames(self, exemplar_transform, frame_shape, frame_norm=None):
         """Frame mode on (a spec and the frame shape) or off (both None).  in_shape stays the crop shape.  frame_norm = (mean,
@@ -167,13 +175,20 @@ class ExemplarNet:
             if frame_norm is not None:
                 raise ValueError("exemplar wrapper: a byte store holds frames (frame_norm needs an exemplar_transform)")
             return
-        if not isinstance(exemplar_transform, (RandomCropFlip, RandomResizedCropFlip)) or frame_shape is None:
+        if not isinstance(exemplar_transform, (RandomCropFlip, RandomResizedCropFlip, RandomPadCropFlip)) or frame_shape is None:
             raise TypeError("exemplar wrapper: exemplar_transform is a RandomCropFlip and comes with the frame shape (C, Hs, Ws) "
-                            "(or a RandomResizedCropFlip: resized replay)")
+                            "(or a RandomResizedCropFlip: resized replay; or a RandomPadCropFlip: padded replay)")
         C, Hs, Ws = (int(v) for v in frame_shape)
-        if (C,) + exemplar_transform.size != tuple(self.in_shape) or Hs < self.in_shape[1] or Ws < self.in_shape[2]:
+        pl, pt, pr, pb = getattr(exemplar_transform, "padding", (0, 0, 0, 0))      # (the PADDED frame holds the crop)
+        if (C,) + exemplar_transform.size != tuple(self.in_shape) or Hs + pt + pb < self.in_shape[1] or Ws + pl + pr < self.in_shape[2]:
             raise ValueError("exemplar wrapper: frames %s, crop %s, net input %s" % (tuple(frame_shape), exemplar_transform.size,
                                                                                  self.in_shape))
+        if isinstance(exemplar_transform, RandomPadCropFlip):
+            slack = {"reflect": 1, "symmetric": 0}.get(exemplar_transform.padding_mode)
+            if slack is not None and (max(pt, pb) > Hs - slack or max(pl, pr) > Ws - slack):
+                raise ValueError("exemplar wrapper: padding_mode %r takes pads up to the extent%s, got %s for frames of %d x %d"
+                                 % (exemplar_transform.padding_mode, " - 1" if slack else "", exemplar_transform.padding, Hs, Ws))
+            exemplar_transform.fill_values(C, byte=frame_norm is not None)          # (one per channel; bytes on a byte store)
         self.exemplar_transform = _respec(exemplar_transform)                                       # (the extents are a task's)
         self.frame_shape = (C, Hs, Ws)
         if frame_norm is not None:
@@ -189,13 +204,22 @@ class ExemplarNet:
 
     @property
     def params_width(self):
-        """Columns of an exemplar's draw: (top, left, flip), or (top, left, h, w, flip) of a resized spec."""
-        return 5 if isinstance(self.exemplar_transform, RandomResizedCropFlip) else 3
+        """Columns of an exemplar's draw: (top, left, flip), (top, left, h, w, flip) of a resized spec, or (top, left, flip, h, w)
+        of a padded one."""
+        return 5 if isinstance(self.exemplar_transform, (RandomResizedCropFlip, RandomPadCropFlip)) else 3
 
     def _assemble(self, *args):
         """The frame-mode assembly launch of this wrapper's spec and store kind (ops.rehearsal_assemble_crop_flip's arguments
         after the geometry)."""
-        resized = isinstance(self.exemplar_transform, RandomResizedCropFlip)
+        spec = self.exemplar_transform
+        if isinstance(spec, RandomPadCropFlip):
+            pad = (self.geometry, spec.padding_mode, spec.padding, self.fill)
+            if self.frame_norm is None:
+                ops.rehearsal_assemble_pad_crop_flip(*pad, *args)
+            else:
+                ops.rehearsal_assemble_pad_crop_flip_u8(*pad, self.lut, *args)
+            return
+        resized = isinstance(spec, RandomResizedCropFlip)
         if self.frame_norm is None:
             (ops.rehearsal_assemble_resized_crop_flip if resized else ops.rehearsal_assemble_crop_flip)(self.geometry, *args)
         else:
@@ -244,11 +268,13 @@ class ExemplarNet:
     def draw_exemplar_params(self, ext, seed):
         """Host int32 [n][3] of (top, left, flip) for exemplars whose frames have the valid sizes ext [n][2], in that order, from
         a private CPU generator: the global one is not touched (DeviceLoader's rule for its epoch table).  A resized spec:
-        [n][5] of (top, left, h, w, flip), RandomResizedCrop's windows over the same extents."""
+        [n][5] of (top, left, h, w, flip), RandomResizedCrop's windows over the same extents.  A padded spec: [n][5] of (top,
+        left, flip, h, w), draw_pad_crop_flip's corners over the padded extents."""
         g = torch.Generator()
         g.manual_seed(seed)
         spec = _respec(self.exemplar_transform, ext)
-        draw = draw_resized_crop_flip if isinstance(spec, RandomResizedCropFlip) else draw_crop_flip
+        draw = (draw_resized_crop_flip if isinstance(spec, RandomResizedCropFlip) else
+                draw_pad_crop_flip if isinstance(spec, RandomPadCropFlip) else draw_crop_flip)
         return draw(ext.shape[0], spec, self.frame_shape[1:], g)
 
     def _bind(self, mix=True):
@@ -258,7 +284,14 @@ class ExemplarNet:
         self.engine.auto_dropout = False        # the masks are the wrapper's own (its dropout policy), not the engine's
         self.A = self.engine.arena
         self.stats = torch.zeros(2, dtype=torch.float64, device=self.device)
-        self.lut = None if self.frame_norm is None else norm_lut(*self.frame_norm).to(self.device)
+        lut = None if self.frame_norm is None else norm_lut(*self.frame_norm)
+        self.lut = None if lut is None else lut.to(self.device)
+        self.fill = None
+        if isinstance(self.exemplar_transform, RandomPadCropFlip):
+            fill = self.exemplar_transform.fill_values(self.frame_shape[0], byte=lut is not None)
+            if lut is not None:                 # a byte means what the table says (ByteTaskDataset.decoded_fill)
+                fill = [lut[c, v] for c, v in enumerate(fill)]
+            self.fill = torch.tensor([float(v) for v in fill], dtype=torch.float32).to(self.device)
         if mix:
             self.x_mix = torch.empty((rows,) + self.in_shape, dtype=torch.float32, device=self.device)
             self.y_mix = torch.empty((rows,), dtype=torch.int64, device=self.device)

@@ -12,6 +12,9 @@ clhip_rehearsal_assemble_crop_flip), and a past-task pass serves memory[t] throu
 and flip per exemplar per pass as gem.py:233-234 rebuilds its ImagePathlist with the train transform.  With a byte store
 (frame_norm) memory[t] holds uint8 frames and the memory loader is one over a ByteTaskDataset: the ..._u8 crop gather decodes them.
 With a RandomResizedCropFlip spec the memory loader carries it, so a past-task pass runs the loaders' resizing gather.
+With a RandomPadCropFlip spec (padded replay) memory[t] holds the UNPADDED frames, fill_buffer is the ring-only form of
+clhip_rehearsal_assemble_pad_crop_flip[_u8] (a crop larger than the frame is legal there) and the memory loader carries the
+spec with its fill (bytes on a byte store), so a past-task pass runs the loaders' padded gather.
 """
 import copy
 import ctypes as C
@@ -130,7 +133,8 @@ class GemNet(SharedRowDropout, ExemplarNet):
         if self.frame_norm is not None:
             mem.mean, mem.std = self.frame_norm                     # the ..._u8 crop gather decodes the stored bytes
         if self.exemplar_transform is not None:
-            mem.transform = _respec(self.exemplar_transform, self.memory_ext[past])     # (crop or resized: the loader serves both)
+            # (crop, resized or padded: the loader serves all three; a padded spec keeps its fill, bytes on a byte store)
+            mem.transform = _respec(self.exemplar_transform, self.memory_ext[past])
         return DeviceLoader(mem, self.batch_size, True, self.device)
 
     # ------------------------------------------------------------------ kernels

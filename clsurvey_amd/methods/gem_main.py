@@ -131,9 +131,9 @@ def exemplar_split(args, dset_sizes):
 
 
 def refuse_padded_replay(who, train):
-    """A train split carrying a RandomPadCropFlip is refused by every method that replays stored exemplars (GEM, the rehearsal
-    baselines, iCaRL): the exemplar assemblies and the memory loaders crop stored frames without padding.  Decided on the
-    split alone, before any loader or device is needed."""
+    """A train split carrying a RandomPadCropFlip is refused by iCaRL, and by GEM and the rehearsal baselines unless they were
+    asked for padded replay (main's exemplar_padded): by default the exemplar assemblies crop stored frames without padding.
+    Decided on the split alone, before any loader or device is needed."""
     spec = getattr(train, "transform", None)
     if isinstance(spec, RandomPadCropFlip):
         raise NotImplementedError("%s: padded replay is not built: exemplars are replayed with RandomCropFlip (or, opt-in, "
@@ -145,7 +145,9 @@ def main(overwrite_args, nc_per_task, device="cuda"):
     overwrite_args['exemplar_dtype'] (not in the reference; default 'float32'): 'uint8' stores the exemplars of an augmented byte
     train split as byte frames (exemplar.py, byte store).  overwrite_args['exemplar_resized'] (not in the reference; default
     False): True replays the exemplars through the RandomResizedCropFlip of the train split (exemplar.py, resized replay);
-    without it such a split is refused."""
+    without it such a split is refused.  overwrite_args['exemplar_padded'] (not in the reference; default False): True replays
+    the exemplars through the RandomPadCropFlip of the train split (exemplar.py, padded replay); without it such a split is
+    refused."""
     parser = argparse.ArgumentParser()
     for name, kw in (("--task_name", dict(type=str)), ("--task_count", dict(type=int)),
                      ("--prev_model_path", dict(type=str)), ("--save_path", dict(type=str, default="results/")),
@@ -156,7 +158,8 @@ def main(overwrite_args, nc_per_task, device="cuda"):
                      ("--n_epochs", dict(type=int, default=1)), ("--batch_size", dict(type=int, default=70)),
                      ("--lr", dict(type=float, default=1e-3)), ("--n_tasks", dict(type=int, default=10)),
                      ("--exemplar_dtype", dict(type=str, default="float32")),
-                     ("--exemplar_resized", dict(action="store_true"))):
+                     ("--exemplar_resized", dict(action="store_true")),
+                     ("--exemplar_padded", dict(action="store_true"))):
         parser.add_argument(name, **kw)
     args = parser.parse_known_args([])[0]
     args.nc_per_task = nc_per_task
@@ -183,7 +186,11 @@ def main(overwrite_args, nc_per_task, device="cuda"):
 
     dsets = load_task_datasets(args.dataset_path)
     args.task_imgfolders = dsets
-    refuse_padded_replay("rehearsal method %r" % (args.method,), dsets["train"])
+    if not args.exemplar_padded:
+        refuse_padded_replay("rehearsal method %r" % (args.method,), dsets["train"])
+    elif not isinstance(getattr(dsets["train"], "transform", None), RandomPadCropFlip):
+        raise ValueError("rehearsal method %r: exemplar_padded=True replays the exemplars through the RandomPadCropFlip of the "
+                         "train split; this one carries %r" % (args.method, getattr(dsets["train"], "transform", None)))
     resized = isinstance(getattr(dsets["train"], "transform", None), RandomResizedCropFlip)
     if resized and not args.exemplar_resized:
         # by default the exemplar wrappers replay stored frames through clhip_rehearsal_assemble_crop_flip, which does not resample
@@ -197,10 +204,12 @@ def main(overwrite_args, nc_per_task, device="cuda"):
         raise ValueError("rehearsal method %r: exemplar_dtype is 'float32' or 'uint8', got %r" % (args.method, args.exemplar_dtype))
     byte_store = args.exemplar_dtype == "uint8"
     byte_frames = isinstance(dsets["train"], ByteTaskDataset) and isinstance(getattr(dsets["train"], "transform", None),
-                                                                             (RandomCropFlip, RandomResizedCropFlip))
+                                                                             (RandomCropFlip, RandomResizedCropFlip,
+                                                                              RandomPadCropFlip))
     if byte_store and not byte_frames:
         raise ValueError("rehearsal method %r: exemplar_dtype='uint8' stores the byte frames of a train split that is a "
-                         "ByteTaskDataset carrying a RandomCropFlip (or, with exemplar_resized=True, a RandomResizedCropFlip); "
+                         "ByteTaskDataset carrying a RandomCropFlip (or, with exemplar_resized=True, a RandomResizedCropFlip; with "
+                         "exemplar_padded=True, a RandomPadCropFlip); "
                          "this one is a %s with transform %r"
                          % (args.method, type(dsets["train"]).__name__, getattr(dsets["train"], "transform", None)))
     if isinstance(dsets["train"], ByteTaskDataset) and getattr(dsets["train"], "transform", None) is not None and not byte_store:

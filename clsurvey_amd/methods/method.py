@@ -453,6 +453,8 @@ def _gem_run(self, args, manager, strength, out_dir, prev=None, finetune=False, 
         kw["exemplar_dtype"] = "uint8"
     if getattr(args, "resized_exemplars", False):               # (only then, as above)
         kw["exemplar_resized"] = True
+    if getattr(args, "padded_exemplars", False):                # (only then, as above)
+        kw["exemplar_padded"] = True
     manager.overwrite_args = kw
     return _gem.main(kw, nc, device=_dev(args))
 
@@ -545,6 +547,8 @@ def _rehearsal_grid_train(self, args, manager, lr):
         kw["exemplar_dtype"] = "uint8"
     if getattr(args, "resized_exemplars", False):               # (only then, as above)
         kw["exemplar_resized"] = True
+    if getattr(args, "padded_exemplars", False):                # (only then, as above)
+        kw["exemplar_padded"] = True
     manager.overwrite_args = kw
     return _gem.main(kw, nc, device=_dev(args))
 

@@ -19,6 +19,8 @@ exemplars get one fresh (top, left, flip) each, drawn on the host after the plan
 (clhip_rehearsal_assemble_crop_flip in place of clhip_rehearsal_assemble; everything after it is the same).  With a byte
 store (frame_norm) the launch is clhip_rehearsal_assemble_crop_flip_u8: byte ring rows, exemplars decoded as they are cropped.
 With a RandomResizedCropFlip spec it is clhip_rehearsal_assemble_resized_crop_flip[_u8]: the exemplars are resampled in the launch.
+With a RandomPadCropFlip spec (padded replay) it is clhip_rehearsal_assemble_pad_crop_flip[_u8]: the store holds the unpadded
+frames and the exemplars are windows of their padded frames, one (top, left, flip, h, w) each.
 """
 import random
 
@@ -189,8 +191,8 @@ class RehearsalNet(SharedRowDropout, ExemplarNet):
         return sample_plan(t, self.n_append, self.observed_tasks, self.n_memories, self.chunk_size, self.filled, seeds)
 
     def exemplar_params(self, gather, seeds):
-        """Frame mode: host int32 [len(gather)][params_width], one (top, left, flip) (a resized spec: (top, left, h, w, flip))
-        per gathered store row in gather order, over the rows' own extents; the generator is seeded with the base seed the plan's last exemplar loader drew anyway (`seeds`
+        """Frame mode: host int32 [len(gather)][params_width], one (top, left, flip) (a resized spec: (top, left, h, w, flip); a
+        padded one: (top, left, flip, h, w)) per gathered store row in gather order, over the rows' own extents; the generator is seeded with the base seed the plan's last exemplar loader drew anyway (`seeds`
         of plan()), so the global generator and Python `random` are consumed exactly as in crop mode.  No exemplars: no draws."""
         if not gather:
             return torch.zeros((0, self.params_width), dtype=torch.int32)

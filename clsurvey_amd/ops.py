@@ -949,10 +949,18 @@ def gather_tasks_pad_crop_flip_u8(table, geometry, mode, pads, fill, lut, idx, p
 
 
 def _assemble_crop_flip(entry, frame_dtype, ncols, geometry, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0,
-                        ring_rows, gather, params, x_mix, y_mix):
-    """The frame-mode assembly entries: ncols = 3, params rows (top, left, flip); 5, (top, left, h, w, flip)."""
+                        ring_rows, gather, params, x_mix, y_mix, pad=None):
+    """The frame-mode assembly entries: ncols = 3, params rows (top, left, flip); 5, (top, left, h, w, flip).  pad = (mode, pads,
+    fill) of the padded entries: 5 columns (top, left, flip, h, w); the three go after the geometry, fill may be None without
+    exemplars, and a store row may be smaller than the crop."""
     _chk(lut, x, y, src_frames, src_idx, store, store_y, gather, params, x_mix, y_mix)
     C, Hs, Ws, th, tw = (int(v) for v in geometry)
+    padding = ()
+    if pad is not None:
+        mode, pads, fill = pad
+        _chk(fill)
+        assert fill is None or (fill.dtype == torch.float32 and tuple(fill.shape) == (C,) and fill.is_contiguous()), "fill: float32 [C]"
+        padding = (PAD_MODES.index(mode) if isinstance(mode, str) else int(mode),) + tuple(int(v) for v in pads) + (_ptr(fill),)
     E = 0 if gather is None else int(gather.shape[0])
     assert store.dtype == frame_dtype and store_y.dtype == torch.int64 and store.numel() == store.shape[0] * C * Hs * Ws
     assert store_y.numel() >= store.shape[0]
@@ -973,8 +981,10 @@ def _assemble_crop_flip(entry, frame_dtype, ncols, geometry, lut, x, y, B, src_f
             assert lut is not None, "lut: needed to decode the exemplar rows"
             _chk_lut(lut, C)
         table = (_ptr(lut),)
+    if E and pad is not None:
+        assert pad[2] is not None, "fill: needed to pad the exemplar rows"
     check(getattr(_lib.lib(), entry)(
-        _ptr(x), _ptr(y), B, C, Hs, Ws, th, tw, *table, _ptr(src_frames), 0 if src_frames is None else src_frames.shape[0],
+        _ptr(x), _ptr(y), B, C, Hs, Ws, th, tw, *padding, *table, _ptr(src_frames), 0 if src_frames is None else src_frames.shape[0],
         _ptr(src_idx), _ptr(store), _ptr(store_y), store.shape[0], ring_row0, ring_rows, _ptr(gather) if E else None,
         _ptr(params) if E else None, E, _ptr(x_mix), _ptr(y_mix), _stream()), entry)
 
@@ -1014,6 +1024,25 @@ def rehearsal_assemble_resized_crop_flip_u8(geometry, lut, x, y, B, src_frames, 
     store (lut as rehearsal_assemble_crop_flip_u8): bitwise the fp32 entry on the decoded store."""
     _assemble_crop_flip("clhip_rehearsal_assemble_resized_crop_flip_u8", torch.uint8, 5, geometry, lut, x, y, B, src_frames,
                         src_idx, store, store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix)
+
+
+def rehearsal_assemble_pad_crop_flip(geometry, mode, pads, fill, x, y, B, src_frames, src_idx, store, store_y, ring_row0, ring_rows,
+                                     gather, params, x_mix, y_mix):
+    """clhip_rehearsal_assemble_pad_crop_flip: rehearsal_assemble_crop_flip over the PADDED frames of the store: mode one of
+    PAD_MODES (or its position), pads = (left, top, right, bottom), fill device float32[C] in the domain of the stored frames (may
+    be None without exemplars), params device int32[E, 5] of (top, left, flip, h, w) as gather_tasks_pad_crop_flip takes them.  The
+    exemplar rows are bitwise that gather over the store; a frame may be smaller than the crop."""
+    _assemble_crop_flip("clhip_rehearsal_assemble_pad_crop_flip", torch.float32, 5, geometry, None, x, y, B, src_frames, src_idx,
+                        store, store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix, pad=(mode, pads, fill))
+
+
+def rehearsal_assemble_pad_crop_flip_u8(geometry, mode, pads, fill, lut, x, y, B, src_frames, src_idx, store, store_y, ring_row0,
+                                        ring_rows, gather, params, x_mix, y_mix):
+    """clhip_rehearsal_assemble_pad_crop_flip_u8: rehearsal_assemble_pad_crop_flip with uint8 frames in src_frames and store (lut
+    as rehearsal_assemble_crop_flip_u8); fill stays float32[C] in the OUTPUT domain (lut[c, fill byte of c]): bitwise the fp32
+    entry on the decoded store."""
+    _assemble_crop_flip("clhip_rehearsal_assemble_pad_crop_flip_u8", torch.uint8, 5, geometry, lut, x, y, B, src_frames, src_idx,
+                        store, store_y, ring_row0, ring_rows, gather, params, x_mix, y_mix, pad=(mode, pads, fill))
 
 
 def slice_argmax_count(logits, cols, labels, correct, total, out_of_range):

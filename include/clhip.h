@@ -636,7 +636,29 @@ int clhip_gem_project_dev_wide(const float* G, size_t ld, const int* row_idx_hos
  *                       1000 -> 125 is not served).  With E == 0 (the ring update alone, x_mix == NULL allowed) no plan is
  *                       needed and CLHIP_ENOTSUP is never returned.  float4 stores of the exemplar rows when tw % 4 == 0 and
  *                       x_mix is 16-byte aligned, dword loads of the frames.
- *   loss_segments       segs (device, n_segs <= CLHIP_LOSS_MAX_SEGS) cover rows of logits[N][ld], N <= CLHIP_LOSS_MAX_ROWS, each
+ *   rehearsal_assemble_pad_crop_flip  rehearsal_assemble_crop_flip when the task's train transform is torchvision's
+ *                       RandomCrop(size, padding, fill, padding_mode) + RandomHorizontalFlip (the CIFAR-style rule, see
+ *                       clhip_gather_tasks_pad_crop_flip below): the store holds the UNPADDED frames and a replayed exemplar is a
+ *                       fresh window of its padded frame.  Same single launch (a 1-D grid of the copy rows, the ring rows and
+ *                       the exemplar rows), same copy and ring rows; mode, (pl, pt, pr, pb) and fill (device float[C], output
+ *                       domain) as in that gather, gather_params is device int32[E][5] of (top, left, flip, h, w), that
+ *                       gather's row: the corner in the frame's unpadded coordinates, (h, w) the stored frame's valid extent, and
+ *                         x_mix[B + e][c][y][x] = P(c, top + y, left + (flip ? tw - 1 - x : x))
+ *                       with P the padded image of store[gather_rows[e]] as that gather defines it, by the same device code
+ *                       (E x C x ceil(th / clhip_crop_rows_per_block(tw)) blocks): the exemplar rows are BITWISE what that
+ *                       gather yields for a one-task table laid over the store, idx = gather_rows and the same params, and with
+ *                       all pads 0 and full extents the whole launch is bitwise rehearsal_assemble_crop_flip.
+ *                       A src_idx outside [0, src_rows): as rehearsal_assemble_crop_flip.  An exemplar row copies nothing and
+ *                       writes label -1 when its gather row is outside [0, store_rows), flip is outside {0, 1}, h is outside
+ *                       [1, Hs] or w outside [1, Ws], top is outside [-pt, h + pb - th] or left outside [-pl, w + pr - tw], or the
+ *                       pads exceed the mode's limit for (h, w) (reflect: extent - 1, symmetric: extent); no address outside a
+ *                       stored frame's h x w extent is formed in any mode.  CLHIP_EINVAL before any launch: the checks of
+ *                       clhip_rehearsal_assemble_crop_flip except th > Hs and tw > Ws (the padded image may hold the crop), and
+ *                       mode outside 0..3, a pad < 0 or > CLHIP_PAD_MAX, Hs or Ws > CLHIP_PAD_MAX_EXTENT, fill == NULL with
+ *                       E > 0.  The ring-only form (x_mix == NULL, E == 0) needs no fill.  float4 stores of the exemplar rows
+ *                       when tw % 4 == 0 and x_mix is 16-byte aligned; dword-aligned loads, 4 columns one wide load only when all
+ *                       4 lie inside [0, w).
+ *   loss_segments      segs (device, n_segs <= CLHIP_LOSS_MAX_SEGS) cover rows of logits[N][ld], N <= CLHIP_LOSS_MAX_ROWS, each
  *                       with a class slice [col_off, col_off + ncols), a scale and a kind:
  *                         kind 0  scale * mean_i CE_i over the slice against labels (relative to the slice)
  *                         kind 1  scale * T^2 * KLDiv_batchmean(log_softmax(z / T), softmax(target / T)) over the slice,
@@ -669,6 +691,11 @@ int clhip_rehearsal_assemble_resized_crop_flip(const float* x, const int64_t* la
                                                float* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
                                                int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
                                                int64_t* labels_mix, void* stream);
+int clhip_rehearsal_assemble_pad_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                           int mode, int pl, int pt, int pr, int pb, const float* fill, const float* src_frames,
+                                           long src_rows, const int64_t* src_idx, float* store_frames, int64_t* store_labels,
+                                           long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
+                                           const int* gather_params, int E, float* x_mix, int64_t* labels_mix, void* stream);
 int clhip_loss_segments(const float* logits, const int64_t* labels_i64, const float* targets, int ld_t, int N, int ld,
                         const clhip_loss_segment* segs, int n_segs, float T, float* dlogits, float* loss_out, double* stats,
                         void* stream);
@@ -868,7 +895,14 @@ int clhip_crop_rows_per_block(int tw);
  *                       flip) rows, bad rows, CLHIP_EINVAL and CLHIP_ENOTSUP (the table's 1 KB counted in the plan) as the fp32
  *                       entry.  The bytes of the source band are decoded through the block's channel of the table as they are
  *                       staged, everything after is the fp32 code: bitwise the fp32 entry on the decoded store, and bitwise
- *                       clhip_gather_tasks_resized_crop_flip_u8 over the store.  Byte loads of the frames. */
+ *                       clhip_gather_tasks_resized_crop_flip_u8 over the store.  Byte loads of the frames.
+ *   rehearsal_assemble_pad_crop_flip_u8   clhip_rehearsal_assemble_pad_crop_flip for a store of BYTE frames: frames, ring rows
+ *                       and the lut rule (NULL is CLHIP_EINVAL only with E > 0) as rehearsal_assemble_crop_flip_u8; mode, pads,
+ *                       (top, left, flip, h, w) rows, bad rows and CLHIP_EINVAL as the fp32 entry.  fill STAYS float[C] in the
+ *                       output domain (callers pass lut[c][fill byte of c]); the block's channel of the table is staged in LDS as
+ *                       257 entries, the last one fill[c], and the bytes are decoded where they are loaded, as
+ *                       gather_tasks_pad_crop_flip_u8 does: bitwise the fp32 entry on the decoded store, and bitwise that gather
+ *                       over the store. */
 typedef struct clhip_task_src_u8 { const uint8_t* x; const int64_t* labels; int64_t cum_rows; int64_t label_shift; } clhip_task_src_u8;
 int clhip_gather_tasks_u8(const clhip_task_src_u8* tasks_dev, int T, int C, size_t plane_elems, const float* lut,
                           const int64_t* idx, int B, float* x_out, int64_t* labels_out, void* stream);
@@ -892,6 +926,12 @@ int clhip_rehearsal_assemble_resized_crop_flip_u8(const float* x, const int64_t*
                                                   long store_rows, long ring_row0, int ring_rows, const int* gather_rows,
                                                   const int* gather_params, int E, float* x_mix, int64_t* labels_mix,
                                                   void* stream);
+int clhip_rehearsal_assemble_pad_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th,
+                                              int tw, int mode, int pl, int pt, int pr, int pb, const float* fill, const float* lut,
+                                              const uint8_t* src_frames, long src_rows, const int64_t* src_idx,
+                                              uint8_t* store_frames, int64_t* store_labels, long store_rows, long ring_row0,
+                                              int ring_rows, const int* gather_rows, const int* gather_params, int E, float* x_mix,
+                                              int64_t* labels_mix, void* stream);
 
 /* ------------------------------------------------------------------ iCaRL
  * rehearsal/model/icarl.py: exemplar herding (manage_memory :384-471) and the nearest-mean-of-exemplars classifier of
