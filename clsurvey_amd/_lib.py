@@ -204,6 +204,8 @@ SIGNATURES = {
     "clhip_icarl_assemble_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
     "clhip_icarl_assemble_resized_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
     "clhip_icarl_assemble_resized_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
+    "clhip_icarl_assemble_pad_crop_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
+    "clhip_icarl_assemble_pad_crop_flip_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _l, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -5,7 +5,10 @@
 // the stored target rows of the same exemplars (the crop-mode step takes two clhip_rehearsal_assemble launches for that).
 //   icarl_assemble_crop_flip[_u8]           RandomCrop + flip: the window is copied by cf_copy_window (crop_flip.hpp)
 //   icarl_assemble_resized_crop_flip[_u8]   RandomResizedCrop + flip: the window is resampled by rz_resample_block (resized_crop.hpp)
-// Both are the block bodies of the loaders' gathers (augment.hip) and of the rehearsal assembly (rehearsal.hip): bitwise their
+//   icarl_assemble_pad_crop_flip[_u8]       RandomCrop(size, padding, fill, padding_mode) + flip (datasets/dataset_utils.py's
+//                                           CIFAR-style train transform): the store holds the UNPADDED frames and the window of
+//                                           the padded image is copied by cf_copy_window_pad (crop_flip.hpp)
+// All are the block bodies of the loaders' gathers (augment.hip) and of the rehearsal assembly (rehearsal.hip): bitwise their
 // results for the same frame and draw.
 #include "resized_crop.hpp"
 #include <type_traits>
@@ -58,14 +61,28 @@ struct icarl_asm_args {
     int rpb, chunks;                                                           // crop_blocks = C * chunks, rpb lines each
     int nb, wmax, ktx, kty;                                                    // the rest of the rz_plan (resized entries only)
     int vec_row, vec_t;                                                        // 16-byte accesses of the copy / target runs
+    int pl, pt, pr, pb;                                                        // the padded entries only
+    const float* fill;                                                         // [C], the padded entries only
 };
 
-// A draw the window blocks and the target blocks both refuse (the rules of rehearsal_assemble_cf_kernel / ..._rz_kernel).
-template <bool RESIZED, typename T>
+// What a launch's params rows hold: (top, left, flip), (top, left, h, w, flip), or, KIND >= 0, the padded row (top, left, flip,
+// h, w) under the padding mode KIND (CF_PAD_*).
+constexpr int IA_CROP = -1, IA_RESIZED = -2;
+
+// A draw the window blocks and the target blocks both refuse (the rules of rehearsal_assemble_cf_kernel / ..._rz_kernel /
+// ..._pad_kernel).
+template <int KIND, typename T>
 __device__ __forceinline__ bool ia_bad_row(const icarl_asm_args<T>& a, unsigned e) {
     const long g = a.gather[e];
     if (g < 0 || g >= a.store_rows) return true;
-    if constexpr (RESIZED) {
+    if constexpr (KIND >= 0) {
+        const int top = a.params[5 * e], left = a.params[5 * e + 1], flip = a.params[5 * e + 2], h = a.params[5 * e + 3],
+                  w = a.params[5 * e + 4];
+        constexpr int lim = KIND == CF_PAD_REFLECT ? 1 : 0;                    // reflect: pad <= extent - 1, symmetric: pad <= extent
+        const bool one_reflection = KIND < CF_PAD_REFLECT || (max(a.pl, a.pr) <= w - lim && max(a.pt, a.pb) <= h - lim);
+        return (flip != 0 && flip != 1) || h < 1 || h > a.Hs || w < 1 || w > a.Ws || top < -a.pt ||
+               (int64_t)top > (int64_t)h + a.pb - a.th || left < -a.pl || (int64_t)left > (int64_t)w + a.pr - a.tw || !one_reflection;
+    } else if constexpr (KIND == IA_RESIZED) {
         const int top = a.params[5 * e], left = a.params[5 * e + 1], h = a.params[5 * e + 2], w = a.params[5 * e + 3],
                   flip = a.params[5 * e + 4];
         return h < 1 || w < 1 || top < 0 || left < 0 || top > a.Hs - h || left > a.Ws - w || (flip != 0 && flip != 1) ||
@@ -96,7 +113,7 @@ __device__ __forceinline__ bool ia_copy_run(const icarl_asm_args<T>& a, unsigned
 // The target run: block b (counted from the run's first block) moves IA_TGT_UNITS accesses of the E x n_outputs target rows,
 // store_t[gather[e]] -> t_mix[B + e]; a thread's accesses are IA_BLOCK apart, so a wave's lanes run along a row.  A bad row
 // (ia_bad_row, per access: nothing here is block-uniform, and there is no barrier) is left as it is.
-template <bool RESIZED, typename T>
+template <int KIND, typename T>
 __device__ __forceinline__ void ia_target_run(const icarl_asm_args<T>& a, unsigned b) {
     const unsigned per_row = a.vec_t ? (unsigned)a.n_outputs / 4 : (unsigned)a.n_outputs;   // accesses per target row
     const size_t total = (size_t)a.E * per_row;
@@ -111,7 +128,7 @@ __device__ __forceinline__ void ia_target_run(const icarl_asm_args<T>& a, unsign
         if (i < total) {
             const unsigned e = (unsigned)(i / per_row);
             const unsigned j = (unsigned)(i - (size_t)e * per_row);
-            if (!ia_bad_row<RESIZED>(a, e)) {
+            if (!ia_bad_row<KIND>(a, e)) {
                 ok[k] = true;
                 const size_t src = (size_t)a.gather[e] * a.n_outputs;
                 dst[k] = (size_t)(a.B + e) * a.n_outputs;
@@ -143,14 +160,14 @@ __global__ __launch_bounds__(IA_BLOCK) void icarl_assemble_cf_kernel(const icarl
     if (ia_copy_run(a, b)) return;
     const unsigned n_crop = (unsigned)a.E * a.crop_blocks;
     if (b >= n_crop) {
-        ia_target_run<false>(a, b - n_crop);
+        ia_target_run<IA_CROP>(a, b - n_crop);
         return;
     }
     // (the role and the bad-row test are block-uniform: every thread of a block reaches the barrier below or none does)
     const unsigned e = b / a.crop_blocks;
     const int k = (int)(b - e * a.crop_blocks);
     int64_t* ydst = a.y_mix + a.B + e;
-    if (ia_bad_row<false>(a, e)) {
+    if (ia_bad_row<IA_CROP>(a, e)) {
         if (k == 0 && threadIdx.x == 0) *ydst = -1;
         return;
     }
@@ -182,14 +199,14 @@ __global__ __launch_bounds__(IA_BLOCK) void icarl_assemble_rz_kernel(const icarl
     if (ia_copy_run(a, b)) return;
     const unsigned n_crop = (unsigned)a.E * a.crop_blocks;
     if (b >= n_crop) {
-        ia_target_run<true>(a, b - n_crop);
+        ia_target_run<IA_RESIZED>(a, b - n_crop);
         return;
     }
     // (the role and the bad-row test are block-uniform: every thread of a block reaches the body's barriers or none does)
     const unsigned e = b / a.crop_blocks;
     const int k = (int)(b - e * a.crop_blocks);
     int64_t* ydst = a.y_mix + a.B + e;
-    if (ia_bad_row<true>(a, e)) {
+    if (ia_bad_row<IA_RESIZED>(a, e)) {
         if (k == 0 && threadIdx.x == 0) *ydst = -1;
         return;
     }
@@ -209,18 +226,75 @@ __global__ __launch_bounds__(IA_BLOCK) void icarl_assemble_rz_kernel(const icarl
                                a.kty, lut_c, a.x_mix + (((size_t)(a.B + e) * a.C + c) * a.th + y0) * a.tw);
 }
 
+// RandomCrop(size, padding, fill, padding_mode) + flip.  The window run is rehearsal_assemble_pad_kernel's exemplar run: one
+// block per (exemplar, channel, chunk of rpb output lines) copies its lines of the window of store[gather[e]]'s PADDED image by
+// cf_copy_window_pad, every source coordinate mapped into the row's own h x w extent; byte frames are decoded through the
+// block's channel of the table staged in LDS, entry 256 the decoded fill.  MODE (the padding mode) is a template argument, as
+// in augment.hip.
+template <bool VEC, int MODE, typename T>
+__global__ __launch_bounds__(IA_BLOCK) void icarl_assemble_pad_kernel(const icarl_asm_args<T> a) {
+    unsigned b = blockIdx.x;
+    if (ia_copy_run(a, b)) return;
+    const unsigned n_crop = (unsigned)a.E * a.crop_blocks;
+    if (b >= n_crop) {
+        ia_target_run<MODE>(a, b - n_crop);
+        return;
+    }
+    // (the role and the bad-row test are block-uniform: every thread of a block reaches the barrier below or none does)
+    const unsigned e = b / a.crop_blocks;
+    const int k = (int)(b - e * a.crop_blocks);
+    int64_t* ydst = a.y_mix + a.B + e;
+    if (ia_bad_row<MODE>(a, e)) {
+        if (k == 0 && threadIdx.x == 0) *ydst = -1;
+        return;
+    }
+    if (k == 0 && threadIdx.x == 0) *ydst = 0;
+    const long g = a.gather[e];
+    const int top = a.params[5 * e], left = a.params[5 * e + 1], flip = a.params[5 * e + 2], h = a.params[5 * e + 3],
+              w = a.params[5 * e + 4];
+    const int c = k / a.chunks;
+    const int y0 = (k - c * a.chunks) * a.rpb;
+    const int nrows = min(a.rpb, a.th - y0);
+    float* dst = a.x_mix + (((size_t)(a.B + e) * a.C + c) * a.th + y0) * a.tw;
+    const float fill_c = a.fill[c];
+    typedef const T __attribute__((address_space(1))) gelem;                   // (device memory: global_load, not flat_load)
+    gelem* plane = (gelem*)(a.store + ((size_t)g * a.C + c) * a.Hs * a.Ws);
+    if constexpr (std::is_same<T, uint8_t>::value) {
+        __shared__ float lut_s[257];                                           // the table of channel c (CF_BLOCK == 256: one entry each)
+        lut_s[threadIdx.x] = a.lut[c * 256 + (int)threadIdx.x];
+        if (threadIdx.x == 0) lut_s[256] = fill_c;                             // entry 256: what a fill element decodes to
+        __syncthreads();
+        cf_copy_window_pad<VEC, MODE>(plane, a.Ws, h, w, top + y0, left, fill_c, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip,
+                                      cf_load_u8{lut_s});
+    } else {
+        cf_copy_window_pad<VEC, MODE>(plane, a.Ws, h, w, top + y0, left, fill_c, dst, (unsigned)nrows * (unsigned)a.tw, a.tw, flip);
+    }
+}
+
 }  // namespace
 
-// One body for the four entries: T selects the frames' element type, lut is NULL for floats; RESIZED: gather_params rows are
+// What the padded entries add to the arguments.
+struct icarl_pad { int mode, pl, pt, pr, pb; const float* fill; };
+
+// One body for the six entries: T selects the frames' element type, lut is NULL for floats; RESIZED: gather_params rows are
 // (top, left, h, w, flip) and the window run resamples, under a plan made here for the frame (needed only with E > 0).
+// pad (never with RESIZED): gather_params rows are (top, left, flip, h, w) and the window run copies windows of the padded frames.
 template <typename T, bool RESIZED>
 static int icarl_assemble(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
                           const float* lut, const T* store_frames, long store_rows, const int* gather_rows,
                           const int* gather_params, int E, const float* store_t, int n_outputs, float* x_mix,
-                          int64_t* labels_mix, float* t_mix, void* stream) {
+                          int64_t* labels_mix, float* t_mix, void* stream, const icarl_pad* pad = nullptr) {
     if (B < 0 || E < 0 || store_rows < 0) return CLHIP_EINVAL;
     if (C < 1 || th < 1 || tw < 1 || Hs < 1 || Ws < 1 || n_outputs < 1) return CLHIP_EINVAL;
-    if (!RESIZED && (th > Hs || tw > Ws)) return CLHIP_EINVAL;                   // (a resized window may be enlarged)
+    if (!RESIZED && !pad && (th > Hs || tw > Ws)) return CLHIP_EINVAL;           // (a resized window may be enlarged, a padded image larger)
+    if (pad) {
+        if (Hs > CLHIP_PAD_MAX_EXTENT || Ws > CLHIP_PAD_MAX_EXTENT) return CLHIP_EINVAL;   // (2 n - 1 - s stays an int)
+        if (pad->mode < CF_PAD_CONSTANT || pad->mode > CF_PAD_SYMMETRIC) return CLHIP_EINVAL;
+        if (pad->pl < 0 || pad->pt < 0 || pad->pr < 0 || pad->pb < 0 || pad->pl > CLHIP_PAD_MAX || pad->pt > CLHIP_PAD_MAX ||
+            pad->pr > CLHIP_PAD_MAX || pad->pb > CLHIP_PAD_MAX)
+            return CLHIP_EINVAL;
+        if (E > 0 && !pad->fill) return CLHIP_EINVAL;                            // (a copy-only call pads nothing)
+    }
     if (B > 0 && (!x || !labels_i64 || !x_mix || !labels_mix)) return CLHIP_EINVAL;
     if (E > 0 && (!store_frames || !gather_rows || !gather_params || !store_t || !x_mix || !labels_mix || !t_mix)) return CLHIP_EINVAL;
     if (std::is_same<T, uint8_t>::value && E > 0 && !lut) return CLHIP_EINVAL;
@@ -239,6 +313,8 @@ static int icarl_assemble(const float* x, const int64_t* labels_i64, int B, int 
     a.rpb = cf_rows_per_block(tw);
     a.chunks = (th + a.rpb - 1) / a.rpb;
     a.nb = a.wmax = a.ktx = a.kty = 0;
+    a.pl = a.pt = a.pr = a.pb = 0; a.fill = nullptr;
+    if (pad) { a.pl = pad->pl; a.pt = pad->pt; a.pr = pad->pr; a.pb = pad->pb; a.fill = pad->fill; }
     size_t lds = 0;
     if (RESIZED && E > 0) {
         rz_plan p;
@@ -256,7 +332,17 @@ static int icarl_assemble(const float* x, const int64_t* labels_i64, int B, int 
     a.row_blocks = (unsigned)row_blocks; a.crop_blocks = (unsigned)crop_blocks;
     const bool vec = tw % 4 == 0 && aligned16(x_mix);
     const dim3 grid((unsigned)blocks), block(IA_BLOCK);
-    if constexpr (RESIZED) {
+    if (pad) {
+#define CLHIP_PAD_LAUNCH(VEC, MODE) \
+    hipLaunchKernelGGL((icarl_assemble_pad_kernel<VEC, MODE, T>), grid, block, 0, as_stream(stream), a)
+        switch (pad->mode) {
+        case CF_PAD_CONSTANT: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_CONSTANT); else CLHIP_PAD_LAUNCH(false, CF_PAD_CONSTANT); break;
+        case CF_PAD_EDGE: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_EDGE); else CLHIP_PAD_LAUNCH(false, CF_PAD_EDGE); break;
+        case CF_PAD_REFLECT: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_REFLECT); else CLHIP_PAD_LAUNCH(false, CF_PAD_REFLECT); break;
+        default: if (vec) CLHIP_PAD_LAUNCH(true, CF_PAD_SYMMETRIC); else CLHIP_PAD_LAUNCH(false, CF_PAD_SYMMETRIC); break;
+        }
+#undef CLHIP_PAD_LAUNCH
+    } else if constexpr (RESIZED) {
         if (vec) hipLaunchKernelGGL((icarl_assemble_rz_kernel<true, T>), grid, block, lds, as_stream(stream), a);
         else hipLaunchKernelGGL((icarl_assemble_rz_kernel<false, T>), grid, block, lds, as_stream(stream), a);
     } else {
@@ -299,6 +385,26 @@ int clhip_icarl_assemble_resized_crop_flip_u8(const float* x, const int64_t* lab
                                               int n_outputs, float* x_mix, int64_t* labels_mix, float* t_mix, void* stream) {
     return icarl_assemble<uint8_t, true>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, store_frames, store_rows, gather_rows,
                                          gather_params, E, store_t, n_outputs, x_mix, labels_mix, t_mix, stream);
+}
+
+int clhip_icarl_assemble_pad_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                       int mode, int pl, int pt, int pr, int pb, const float* fill, const float* store_frames,
+                                       long store_rows, const int* gather_rows, const int* gather_params, int E,
+                                       const float* store_t, int n_outputs, float* x_mix, int64_t* labels_mix, float* t_mix,
+                                       void* stream) {
+    const icarl_pad pad{mode, pl, pt, pr, pb, fill};
+    return icarl_assemble<float, false>(x, labels_i64, B, C, Hs, Ws, th, tw, nullptr, store_frames, store_rows, gather_rows,
+                                        gather_params, E, store_t, n_outputs, x_mix, labels_mix, t_mix, stream, &pad);
+}
+
+int clhip_icarl_assemble_pad_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                          int mode, int pl, int pt, int pr, int pb, const float* fill, const float* lut,
+                                          const uint8_t* store_frames, long store_rows, const int* gather_rows,
+                                          const int* gather_params, int E, const float* store_t, int n_outputs, float* x_mix,
+                                          int64_t* labels_mix, float* t_mix, void* stream) {
+    const icarl_pad pad{mode, pl, pt, pr, pb, fill};
+    return icarl_assemble<uint8_t, false>(x, labels_i64, B, C, Hs, Ws, th, tw, lut, store_frames, store_rows, gather_rows,
+                                          gather_params, E, store_t, n_outputs, x_mix, labels_mix, t_mix, stream, &pad);
 }
 
 }  // extern "C"

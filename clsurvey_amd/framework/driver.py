@@ -96,11 +96,16 @@ def build_parser():
                         "herding ranks one draw of the train transform per training image (the herding view) and every replay "
                         "crops the stored frames afresh inside the step's one assembly launch.  Without it iCaRL refuses "
                         "augmented tasks.  With --rnd_resized it goes with --resized_exemplars, with --u8_frames with --u8_exemplars")
+    p.add_argument("--icarl_padded", action="store_true",
+                   help="iCaRL on --rnd_pad tasks: the exemplar store holds the tasks' unpadded frames, herding ranks one draw of "
+                        "the task's RandomCrop(hw, padding=M) + flip per training image and every replay is a fresh window of the "
+                        "padded frame, padded inside the step's one assembly launch.  Without it iCaRL refuses --rnd_pad tasks.  "
+                        "Excludes --icarl_frames and --resized_exemplars; with --u8_frames it goes with --u8_exemplars")
     p.add_argument("--u8_exemplars", action="store_true",
-                   help="GEM, the rehearsal baselines and iCaRL (--icarl_frames): the exemplar store holds uint8 frames, decoded where they are replayed (a "
+                   help="GEM, the rehearsal baselines and iCaRL (--icarl_frames or --icarl_padded): the exemplar store holds uint8 frames, decoded where they are replayed (a "
                         "quarter of the store's bytes in HBM and in every checkpoint, bitwise the run on the decoded files).  "
                         "Belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars, or --u8_frames "
-                        "--rnd_pad --padded_exemplars): the train splits are augmented byte splits")
+                        "--rnd_pad with --padded_exemplars or --icarl_padded): the train splits are augmented byte splits")
     p.add_argument("--resized_exemplars", action="store_true",
                    help="GEM, the rehearsal baselines and iCaRL (--icarl_frames) with --rnd_resized: the stored exemplar frames are replayed through the "
                         "task's RandomResizedCrop + flip, a fresh window per exemplar and replay, resampled inside the step's batch "
@@ -109,7 +114,7 @@ def build_parser():
                    help="GEM and the rehearsal baselines with --rnd_pad: the exemplar store holds the tasks' unpadded frames and they "
                         "are replayed through the task's RandomCrop(hw, padding=M) + flip, a fresh window of the padded frame per "
                         "exemplar and replay, padded inside the step's batch assembly launch.  Without it these methods refuse "
-                        "--rnd_pad tasks; iCaRL refuses them either way")
+                        "--rnd_pad tasks; iCaRL takes them with --icarl_padded, not with this switch")
     p.add_argument("--rnd_resized", type=int, default=0,
                    help="with --synthetic, instead of --rnd_margin: images are generated M pixels larger than hw and every training "
                         "pass sees a fresh RandomResizedCrop to hw x hw (scale 0.08 - 1, ratio 3/4 - 4/3, antialiased bilinear) + "
@@ -119,8 +124,8 @@ def build_parser():
                    help="with --synthetic, instead of --rnd_margin / --rnd_resized: images are generated at hw, no margin, and every "
                         "training pass sees a fresh RandomCrop(hw, padding=M) + horizontal flip of them (pad, crop, flip: the "
                         "CIFAR-style rule), padded inside the batch gather; evaluation reads the images as they are.  GEM and "
-                        "the rehearsal baselines take such tasks with --padded_exemplars only, iCaRL refuses them (its padded "
-                        "replay is not built).  0: no augmentation")
+                        "the rehearsal baselines take such tasks with --padded_exemplars only, iCaRL with --icarl_padded only.  "
+                        "0: no augmentation")
     p.add_argument("--pad_mode", type=str, default=None, choices=("constant", "edge", "reflect", "symmetric"),
                    help="with --rnd_pad: torchvision's padding_mode (default constant, fill 0.0 = byte 128 of --u8_frames)")
     return p
@@ -799,10 +804,15 @@ def main(argv=None, method=None, dataset=None, train_node_factory=None):
         raise SystemExit("--resized_exemplars belongs with --rnd_resized: it replays the exemplars through the tasks' RandomResizedCrop")
     if args.padded_exemplars and not args.rnd_pad:
         raise SystemExit("--padded_exemplars belongs with --rnd_pad: it replays the exemplars through the tasks' padded RandomCrop")
+    if args.icarl_padded and not args.rnd_pad:
+        raise SystemExit("--icarl_padded belongs with --rnd_pad: it replays iCaRL's exemplars through the tasks' padded RandomCrop")
+    if args.icarl_padded and (args.icarl_frames or args.resized_exemplars):
+        raise SystemExit("--icarl_padded excludes --icarl_frames and --resized_exemplars: a train split carries one transform")
     if args.u8_exemplars and not (args.u8_frames and (args.rnd_margin or (args.rnd_resized and args.resized_exemplars) or
-                                                      (args.rnd_pad and args.padded_exemplars))):
+                                                      (args.rnd_pad and (args.padded_exemplars or args.icarl_padded)))):
         raise SystemExit("--u8_exemplars belongs with --u8_frames --rnd_margin (or --u8_frames --rnd_resized --resized_exemplars, or "
-                         "--u8_frames --rnd_pad --padded_exemplars): a byte exemplar store holds the frames of augmented byte splits")
+                         "--u8_frames --rnd_pad with --padded_exemplars or --icarl_padded): a byte exemplar store holds the frames of "
+                         "augmented byte splits")
     if args.rnd_resized and args.rnd_margin:
         raise SystemExit("--rnd_margin and --rnd_resized exclude each other: a train split carries one transform")
     if args.rnd_resized < 0:

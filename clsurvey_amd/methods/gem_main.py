@@ -130,14 +130,16 @@ def exemplar_split(args, dset_sizes):
     return args.total_batch_size + args.n_exemplars_to_append_per_batch
 
 
-def refuse_padded_replay(who, train):
-    """A train split carrying a RandomPadCropFlip is refused by iCaRL, and by GEM and the rehearsal baselines unless they were
-    asked for padded replay (main's exemplar_padded): by default the exemplar assemblies crop stored frames without padding.
+def refuse_padded_replay(who, train, switch=None):
+    """A train split carrying a RandomPadCropFlip is refused by iCaRL, GEM and the rehearsal baselines unless they were asked
+    for padded replay (gem_main.main's exemplar_padded, icarl_main.main's exemplar_pad_frames): by default the exemplar
+    assemblies crop stored frames without padding.  switch: the caller's opt-in, named in the message.
     Decided on the split alone, before any loader or device is needed."""
     spec = getattr(train, "transform", None)
     if isinstance(spec, RandomPadCropFlip):
         raise NotImplementedError("%s: padded replay is not built: exemplars are replayed with RandomCropFlip (or, opt-in, "
-                                  "RandomResizedCropFlip) only, the train split carries %r" % (who, spec))
+                                  "RandomResizedCropFlip) only, the train split carries %r%s"
+                                  % (who, spec, "" if switch is None else ".  Padded replay is opt-in: pass " + switch))
 
 
 def main(overwrite_args, nc_per_task, device="cuda"):

@@ -38,6 +38,13 @@ the mean, the costs of every pick and the stored target each see other crops of 
 with the loader's draws frozen over the passes.  Its forward redraws the exemplars' crops for every evaluated batch (:160-167);
 the class-mean view is one draw per (model, task, batch size), so an evaluation is reproducible.  Without freedom (frames of
 the crop size, p = 0) frame mode is bitwise crop mode.
+
+Padded frame mode (exemplar_transform a RandomPadCropFlip: RandomCrop(size, padding, fill, padding_mode) + flip, the CIFAR-style
+rule): the store holds the UNPADDED frames and store_ext their valid extents; a draw is (top, left, flip, h, w) with the corner in
+the frame's unpadded coordinates (>= -pad).  The two views gather through ops.gather_tasks_pad_crop_flip[_u8], the step and the
+class-mean view through clhip_icarl_assemble_pad_crop_flip[_u8], all with (padding_mode, padding, self.fill); fill is the device
+float[C] of the output domain that _bind rebuilds (a byte fill decoded through the table on a byte store).  Bitwise the crop-frame
+wrapper on the same frames padded on the host.  pad_if_needed is not built.
 """
 import random
 
@@ -46,7 +53,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-from ..data import ByteTaskDataset, RandomResizedCropFlip, _spec_key, _transform_of
+from ..data import ByteTaskDataset, RandomPadCropFlip, RandomResizedCropFlip, _spec_key, _transform_of
 from ..optim import SGD
 from .exemplar import BatchSource, ExemplarNet, PerRowDropout, _stream, compact_blocks, compute_offsets
 from .gem import extend_head
@@ -337,7 +344,13 @@ class IcarlNet(PerRowDropout, ExemplarNet):
 
     def _gather_view(self, table, idx, params):
         """The loaders' gather of this wrapper's spec and store kind: crops [len(idx)][C][th][tw] of the frames in `table`."""
-        resized = isinstance(self.exemplar_transform, RandomResizedCropFlip)
+        spec = self.exemplar_transform
+        if isinstance(spec, RandomPadCropFlip):
+            pad = (self.geometry, spec.padding_mode, spec.padding, self.fill)
+            if self.frame_norm is None:
+                return ops.gather_tasks_pad_crop_flip(table, *pad, idx, params)[0]
+            return ops.gather_tasks_pad_crop_flip_u8(table, *pad, self.lut, idx, params)[0]
+        resized = isinstance(spec, RandomResizedCropFlip)
         if self.frame_norm is None:
             gather = ops.gather_tasks_resized_crop_flip if resized else ops.gather_tasks_crop_flip
             return gather(table, self.geometry, idx, params)[0]
@@ -346,8 +359,16 @@ class IcarlNet(PerRowDropout, ExemplarNet):
 
     def _assemble_step(self, x, y, B, gather_dev, params_dev):
         """The step-assembly launch of this wrapper's spec and store kind: x_mix, y_mix and t_mix[B:B + E) in one launch."""
-        resized = isinstance(self.exemplar_transform, RandomResizedCropFlip)
+        spec = self.exemplar_transform
         args = (x, y, B, self.store_x, gather_dev, params_dev, self.store_t, self.x_mix, self.y_mix, self.t_mix)
+        if isinstance(spec, RandomPadCropFlip):
+            pad = (self.geometry, spec.padding_mode, spec.padding, self.fill)
+            if self.frame_norm is None:
+                ops.icarl_assemble_pad_crop_flip(*pad, *args)
+            else:
+                ops.icarl_assemble_pad_crop_flip_u8(*pad, self.lut, *args)
+            return
+        resized = isinstance(spec, RandomResizedCropFlip)
         if self.frame_norm is None:
             (ops.icarl_assemble_resized_crop_flip if resized else ops.icarl_assemble_crop_flip)(self.geometry, *args)
         else:

@@ -5,22 +5,33 @@ load of the IcarlNet wrapper, postprocess = manage_memory (exemplar herding) + s
 
 Augmented train splits (not in the reference's arguments): overwrite_args['exemplar_frames'] = True builds the wrapper in frame
 mode (icarl.py): the store holds the split's frames, herding ranks the herding view, every replay crops afresh.  Without it an
-augmented split is refused by manage_memory as before.  exemplar_resized / exemplar_dtype follow gem_main.main's rules."""
+augmented split is refused by manage_memory as before.  exemplar_resized / exemplar_dtype follow gem_main.main's rules.
+overwrite_args['exemplar_pad_frames'] = True is frame mode on a split carrying a RandomPadCropFlip (RandomCrop(size, padding, fill,
+padding_mode) + flip): the store holds the unpadded frames, every view and replay is a window of the padded frame."""
 import argparse
 import os
 
 import torch
 
-from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, RandomResizedCropFlip, load_task_datasets
+from ..data import ByteTaskDataset, DeviceLoader, RandomCropFlip, RandomPadCropFlip, RandomResizedCropFlip, load_task_datasets
 from . import gem_main
 from . import icarl as I
 
 
 def _frame_arguments(args, train):
     """exemplar_frames=True: the frame arguments of IcarlNet for the train split, after gem_main.main's rules for
-    exemplar_resized and exemplar_dtype.  Decided before a device is needed."""
+    exemplar_resized and exemplar_dtype.  exemplar_pad_frames=True: the same for a split carrying a RandomPadCropFlip (never
+    with exemplar_resized).  Decided before a device is needed."""
     spec = getattr(train, "transform", None)
-    if not isinstance(spec, (RandomCropFlip, RandomResizedCropFlip)):
+    padded = getattr(args, "exemplar_pad_frames", False)
+    if padded:
+        if not isinstance(spec, RandomPadCropFlip):
+            raise ValueError("icarl: exemplar_pad_frames=True stores the unpadded frames of a train split carrying a "
+                             "RandomPadCropFlip and replays them through it; this one carries %r" % (spec,))
+        if args.exemplar_resized:
+            raise ValueError("icarl: exemplar_pad_frames=True replays through a RandomPadCropFlip, exemplar_resized=True through a "
+                             "RandomResizedCropFlip; a train split carries one of them")
+    elif not isinstance(spec, (RandomCropFlip, RandomResizedCropFlip)):
         raise ValueError("icarl: exemplar_frames=True stores the frames of an augmented train split and replays them through its "
                          "transform; this one carries %r" % (spec,))
     resized = isinstance(spec, RandomResizedCropFlip)
@@ -45,11 +56,16 @@ def _frame_arguments(args, train):
     return frames
 
 
+def _spec_kind(spec):
+    """The class of frame-mode replay a spec stands for."""
+    return next(k for k in (RandomPadCropFlip, RandomResizedCropFlip, RandomCropFlip) if isinstance(spec, k))
+
+
 def _check_loaded(model, frames):
     """A loaded wrapper keeps the store it was built with: its kind and mode agree with this call's arguments."""
     if getattr(model, "exemplar_transform", None) is None:
         raise ValueError("icarl: exemplar_frames=True, the loaded wrapper's store holds crops (it was built without it)")
-    if isinstance(model.exemplar_transform, RandomResizedCropFlip) != isinstance(frames["exemplar_transform"], RandomResizedCropFlip):
+    if _spec_kind(model.exemplar_transform) is not _spec_kind(frames["exemplar_transform"]):          # padded, crop or resized
         raise ValueError("icarl: the loaded wrapper replays %r, the train split carries %r"
                          % (model.exemplar_transform, frames["exemplar_transform"]))
     if (model.frame_norm is not None) != ("frame_norm" in frames):
@@ -64,7 +80,11 @@ def main(overwrite_args, nc_per_task, device="cuda"):
     its transform (a split without a transform is a ValueError).  With it, overwrite_args['exemplar_resized'] = True goes with a
     RandomResizedCropFlip split (either without the other is refused) and overwrite_args['exemplar_dtype'] = 'uint8' with an
     augmented ByteTaskDataset (a byte store; 'uint8' on anything else is a ValueError).  Without exemplar_frames the other two are
-    not looked at and nothing differs from the plain entry."""
+    not looked at and nothing differs from the plain entry.
+    overwrite_args['exemplar_pad_frames'] (default False): True is frame mode on a train split carrying a RandomPadCropFlip: the
+    store holds the unpadded frames (icarl.py, padded frame mode).  It implies exemplar_frames; a split carrying anything else, or
+    exemplar_resized=True with it, is a ValueError; exemplar_dtype follows the byte rules above, with a byte fill per channel on a
+    ByteTaskDataset.  Without it a padded split is refused (gem_main.refuse_padded_replay) whatever the other keys say."""
     parser = argparse.ArgumentParser()
     for name, kw in (("--task_name", dict(type=str)), ("--task_count", dict(type=int)),
                      ("--prev_model_path", dict(type=str)), ("--save_path", dict(type=str, default="results/")),
@@ -75,7 +95,8 @@ def main(overwrite_args, nc_per_task, device="cuda"):
                      ("--n_epochs", dict(type=int, default=1)), ("--batch_size", dict(type=int, default=70)),
                      ("--lr", dict(type=float, default=1e-3)), ("--n_tasks", dict(type=int, default=10)),
                      ("--exemplar_frames", dict(action="store_true")), ("--exemplar_resized", dict(action="store_true")),
-                     ("--exemplar_dtype", dict(type=str, default="float32"))):
+                     ("--exemplar_dtype", dict(type=str, default="float32")),
+                     ("--exemplar_pad_frames", dict(action="store_true"))):
         parser.add_argument(name, **kw)
     args = parser.parse_known_args([])[0]
     args.nc_per_task = nc_per_task
@@ -96,7 +117,10 @@ def main(overwrite_args, nc_per_task, device="cuda"):
 
     dsets = load_task_datasets(args.dataset_path, device)
     args.task_imgfolders = dsets
-    gem_main.refuse_padded_replay("icarl", dsets["train"])           # with or without exemplar_frames
+    if args.exemplar_pad_frames:
+        args.exemplar_frames = True                                  # padded frame mode is frame mode
+    else:
+        gem_main.refuse_padded_replay("icarl", dsets["train"], "exemplar_pad_frames=True (the driver's --icarl_padded)")
     frames = _frame_arguments(args, dsets["train"]) if args.exemplar_frames else {}
     args.dset_loaders = {x: DeviceLoader(dsets[x], args.batch_size, True, device) for x in ["train", "val"]}
     dset_sizes = {x: len(dsets[x]) for x in ["train", "val"]}

@@ -499,6 +499,8 @@ def _icarl_run(self, args, manager, strength, out_dir, prev=None, finetune=False
         kw["exemplar_dtype"] = "uint8"
     if getattr(args, "resized_exemplars", False):               # (only then, as above)
         kw["exemplar_resized"] = True
+    if getattr(args, "icarl_padded", False):                    # (only then, as above)
+        kw["exemplar_pad_frames"] = True
     manager.overwrite_args = kw
     return _icarl.main(kw, nc, device=_dev(args))
 

@@ -1141,10 +1141,19 @@ def icarl_nme(feats, means, offset1, nc, n_outputs, n_rows=None):
     return out
 
 
-def _icarl_assemble(entry, frame_dtype, ncols, geometry, lut, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
-    """The iCaRL step-assembly entries: ncols = 3, params rows (top, left, flip); 5, (top, left, h, w, flip)."""
+def _icarl_assemble(entry, frame_dtype, ncols, geometry, lut, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix,
+                    pad=None):
+    """The iCaRL step-assembly entries: ncols = 3, params rows (top, left, flip); 5, (top, left, h, w, flip).  pad = (mode, pads,
+    fill) of the padded entries: 5 columns (top, left, flip, h, w); the three go after the geometry, fill may be None without
+    exemplars, and a store row may be smaller than the crop."""
     _chk(lut, x, y, store, gather, params, store_t, x_mix, y_mix, t_mix)
     C, Hs, Ws, th, tw = (int(v) for v in geometry)
+    padding = ()
+    if pad is not None:
+        mode, pads, fill = pad
+        _chk(fill)
+        assert fill is None or (fill.dtype == torch.float32 and tuple(fill.shape) == (C,) and fill.is_contiguous()), "fill: float32 [C]"
+        padding = (PAD_MODES.index(mode) if isinstance(mode, str) else int(mode),) + tuple(int(v) for v in pads) + (_ptr(fill),)
     B = int(B)
     E = 0 if gather is None else int(gather.shape[0])
     if B:
@@ -1165,8 +1174,10 @@ def _icarl_assemble(entry, frame_dtype, ncols, geometry, lut, x, y, B, store, ga
             assert lut is not None, "lut: needed to decode the exemplar rows"
             _chk_lut(lut, C)
         table = (_ptr(lut),)
+    if E and pad is not None:
+        assert pad[2] is not None, "fill: needed to pad the exemplar rows"
     check(getattr(_lib.lib(), entry)(
-        _ptr(x) if B else None, _ptr(y) if B else None, B, C, Hs, Ws, th, tw, *table, _ptr(store), 0 if store is None else store.shape[0],
+        _ptr(x) if B else None, _ptr(y) if B else None, B, C, Hs, Ws, th, tw, *padding, *table, _ptr(store), 0 if store is None else store.shape[0],
         _ptr(gather) if E else None, _ptr(params) if E else None, E, _ptr(store_t), n_outputs, _ptr(x_mix), _ptr(y_mix), _ptr(t_mix),
         _stream()), entry)
 
@@ -1199,3 +1210,20 @@ def icarl_assemble_resized_crop_flip_u8(geometry, lut, x, y, B, store, gather, p
     icarl_assemble_crop_flip_u8): bitwise the fp32 entry on the decoded store."""
     _icarl_assemble("clhip_icarl_assemble_resized_crop_flip_u8", torch.uint8, 5, geometry, lut, x, y, B, store, gather, params,
                     store_t, x_mix, y_mix, t_mix)
+
+
+def icarl_assemble_pad_crop_flip(geometry, mode, pads, fill, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
+    """clhip_icarl_assemble_pad_crop_flip: icarl_assemble_crop_flip over the PADDED frames of the store: mode one of PAD_MODES (or
+    its position), pads = (left, top, right, bottom), fill device float32[C] in the domain of the stored frames (may be None
+    without exemplars), params device int32[E, 5] of (top, left, flip, h, w) as gather_tasks_pad_crop_flip takes them.  The
+    exemplar rows are bitwise that gather over the store; a frame may be smaller than the crop."""
+    _icarl_assemble("clhip_icarl_assemble_pad_crop_flip", torch.float32, 5, geometry, None, x, y, B, store, gather, params, store_t,
+                    x_mix, y_mix, t_mix, pad=(mode, pads, fill))
+
+
+def icarl_assemble_pad_crop_flip_u8(geometry, mode, pads, fill, lut, x, y, B, store, gather, params, store_t, x_mix, y_mix, t_mix):
+    """clhip_icarl_assemble_pad_crop_flip_u8: icarl_assemble_pad_crop_flip with uint8 frames in store (lut as
+    icarl_assemble_crop_flip_u8); fill stays float32[C] in the OUTPUT domain (lut[c, fill byte of c]): bitwise the fp32 entry on
+    the decoded store."""
+    _icarl_assemble("clhip_icarl_assemble_pad_crop_flip_u8", torch.uint8, 5, geometry, lut, x, y, B, store, gather, params, store_t,
+                    x_mix, y_mix, t_mix, pad=(mode, pads, fill))

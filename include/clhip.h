@@ -1004,7 +1004,24 @@ int clhip_icarl_nme(const float* feats, const float* means, int N, int F, int C,
  *                       no plan fits the LDS (clhip_gather_tasks_resized_crop_flip's limit).
  *   ..._u8              store_frames holds BYTE frames (byte frames, above): a stored byte v of channel c means lut[c][v]
  *                       (device float32 [C][256], staged per block in LDS), decoded where the window is loaded: bitwise the
- *                       fp32 entry on the decoded store.  lut may be NULL with E == 0, CLHIP_EINVAL otherwise.           */
+ *                       fp32 entry on the decoded store.  lut may be NULL with E == 0, CLHIP_EINVAL otherwise.
+ *   icarl_assemble_pad_crop_flip   the same under RandomCrop(size, padding, fill, padding_mode) + flip, the CIFAR-style train
+ *                       transform (datasets/dataset_utils.py; rebuilt for the exemplar loader at icarl.py:560-561): the store
+ *                       holds the UNPADDED frames and a replayed exemplar is a fresh window of its padded frame.  Same launch
+ *                       shape and the same copy and target runs; mode, (pl, pt, pr, pb) and fill (device float[C], output
+ *                       domain) as clhip_gather_tasks_pad_crop_flip takes them, gather_params int32[E][5] of (top, left, flip,
+ *                       h, w), that gather's row: the corner in the frame's unpadded coordinates, (h, w) the frame's valid
+ *                       extent.  The window is copied by the block body of clhip_gather_tasks_pad_crop_flip /
+ *                       clhip_rehearsal_assemble_pad_crop_flip (bitwise their result), and with all pads 0 and full extents
+ *                       the whole launch is bitwise icarl_assemble_crop_flip.
+ *                       Bad rows: clhip_rehearsal_assemble_pad_crop_flip's rule (a gather row outside [0, store_rows), flip
+ *                       outside {0, 1}, h outside [1, Hs] or w outside [1, Ws], top outside [-pt, h + pb - th] or left outside
+ *                       [-pl, w + pr - tw], pads over the mode's limit for (h, w): reflect extent - 1, symmetric extent),
+ *                       treated as above: neither window nor target row, label -1, no address formed from the row.
+ *                       CLHIP_EINVAL before any launch: the checks of icarl_assemble_crop_flip except th > Hs and tw > Ws
+ *                       (the padded image may hold the crop), and mode outside 0..3, a pad < 0 or > CLHIP_PAD_MAX, Hs or Ws >
+ *                       CLHIP_PAD_MAX_EXTENT, fill == NULL with E > 0.  The _u8 form takes lut after fill; entry 256 of the
+ *                       staged table is the decoded fill.                                                              */
 int clhip_icarl_assemble_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
                                    const float* store_frames, long store_rows, const int* gather_rows, const int* gather_params,
                                    int E, const float* store_t, int n_outputs, float* x_mix, int64_t* labels_mix, float* t_mix,
@@ -1021,6 +1038,16 @@ int clhip_icarl_assemble_resized_crop_flip_u8(const float* x, const int64_t* lab
                                               int tw, const float* lut, const uint8_t* store_frames, long store_rows,
                                               const int* gather_rows, const int* gather_params, int E, const float* store_t,
                                               int n_outputs, float* x_mix, int64_t* labels_mix, float* t_mix, void* stream);
+int clhip_icarl_assemble_pad_crop_flip(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                       int mode, int pl, int pt, int pr, int pb, const float* fill, const float* store_frames,
+                                       long store_rows, const int* gather_rows, const int* gather_params, int E,
+                                       const float* store_t, int n_outputs, float* x_mix, int64_t* labels_mix, float* t_mix,
+                                       void* stream);
+int clhip_icarl_assemble_pad_crop_flip_u8(const float* x, const int64_t* labels_i64, int B, int C, int Hs, int Ws, int th, int tw,
+                                          int mode, int pl, int pt, int pr, int pb, const float* fill, const float* lut,
+                                          const uint8_t* store_frames, long store_rows, const int* gather_rows,
+                                          const int* gather_params, int E, const float* store_t, int n_outputs, float* x_mix,
+                                          int64_t* labels_mix, float* t_mix, void* stream);
 
 #ifdef CLHIP_VISIBILITY_PUSHED
 #pragma GCC visibility pop
