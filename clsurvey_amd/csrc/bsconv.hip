@@ -40,6 +40,7 @@
 #include "common.hpp"
 #include "bs_weight.hpp"
 #include "wgrad_reduce.hpp"
+#include "stage_map.hpp"
 #include <cstdlib>
 
 // Timing-only ablations (tools/experiments; results wrong by design; the product is built with 0): 1 no MFMAs, 2 no weight-operand
@@ -123,8 +124,10 @@ __device__ __forceinline__ void bs_conv_body(
     unsigned char* __restrict__ lds, const int b, const float* __restrict__ in, const clhip_u32x4* __restrict__ wimg,
     const float* __restrict__ bias, const float* __restrict__ mask_src, float* __restrict__ out, uint8_t* __restrict__ pool_idx, int N,
     int Cin, int Cout, int H, int W, int relu, int tiles_x, int tiles_y, int npb) {
-    constexpr int RW = G::RW, RH = G::RH, NI = G::NI, WM = G::WM, WN = G::WN, P = G::P, HR = G::HR, HW_ = G::HW_;
-    constexpr int ROUNDS = G::ROUNDS;
+    constexpr int WM = G::WM, WN = G::WN, P = G::P, HR = G::HR, HW_ = G::HW_;
+    // un-pooling: an item is a pooled window of a halo row and writes PX = 2 pixels (stage_map.hpp)
+    using UM = BsUnpoolMap<G>;
+    constexpr int ROUNDS = UNPOOL ? UM::ROUNDS : G::ROUNDS, PX = UNPOOL ? 2 : 1;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kts = (Cout + BS_BN - 1) / BS_BN;
@@ -132,8 +135,8 @@ __device__ __forceinline__ void bs_conv_body(
     // from HBM once per XCD L2
     const int kt = (b >> 3) % kts, pb = (b / (8 * kts)) * 8 + (b & 7);
     if (pb >= npb) return;
-    const int tx = pb % tiles_x, ty = (pb / tiles_x) % tiles_y, grp = pb / (tiles_x * tiles_y);
-    const int n0 = grp * NI, y0 = ty * RH, x0 = tx * RW;
+    int n0, y0, x0;
+    bs_tile_origin<G>(pb, tiles_x, tiles_y, n0, y0, x0);
     const int n_chunks = Cin / BS_CK;
     const int IH = UNPOOL ? H >> 1 : H, IW = UNPOOL ? W >> 1 : W;          // the input tensor's own plane
     const int plane_in = IH * IW;
@@ -147,20 +150,32 @@ __device__ __forceinline__ void bs_conv_body(
     const __amdgpu_buffer_rsrc_t rs_w = clhip_rsrc(wimg, (size_t)n_nt * n_chunks * 3 * TAPS * 1024);
 
     // ---- staging items of this thread: (halo pixel, k half) -> element offset of channel 8 h of the chunk, LDS slot
-    int xoff[ROUNDS], lw[ROUNDS], pos[ROUNDS];
+    //      un-pooling: (window of a halo row, k half) -> the pooled element, the LDS slots and window positions of its two pixels
+    int xoff[ROUNDS], lw[ROUNDS][PX], pos[ROUNDS][PX];
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
         // (the last round wraps around: its spare threads stage the first items a second time — same data to the same slots —
-        // so that no load / LDS write of the loop sits under a branch)
-        const int it_ = r * 256 + tid, it = it_ < G::ITEMS ? it_ : it_ - G::ITEMS;
-        const int h = it >= G::NHALO ? 1 : 0, p = it - h * G::NHALO;
-        const int ni = p / (HR * HW_), rem = p - ni * (HR * HW_), hy = rem / HW_, hx = rem - hy * HW_;
-        const int gy = y0 + hy - G::HP, gx = x0 + hx - G::HP, n = n0 + ni;
-        const bool ok = n < N && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const int e = UNPOOL ? (gy >> 1) * IW + (gx >> 1) : gy * IW + gx;
-        xoff[r] = ok ? (ni * Cin + 8 * h) * plane_in + e : CLHIP_OOB;
-        pos[r] = ((gy & 1) << 1) | (gx & 1);
-        lw[r] = (h * G::PLANE_SLOTS + ((ni / G::IPR) * HR + hy) * P + (ni % G::IPR) * HW_ + hx) * 16;
+        // so that no load / LDS write of the loop sits under a branch; un-pooling: they stage zeros into row padding, stage_map.hpp)
+        if constexpr (UNPOOL) {
+            const BsStageItem s = UM::item(r * 256 + tid);
+            int ps[2];
+            const int so = bs_unpool_source<G>(s, n0, y0, x0, N, Cin, H, W, ps);
+            xoff[r] = so >= 0 ? so : CLHIP_OOB;
+#pragma unroll
+            for (int p = 0; p < PX; ++p) {
+                pos[r][p] = ps[p];
+                lw[r][p] = UM::slot(s, p) * 16;
+            }
+        } else {
+            const int it_ = r * 256 + tid, it = it_ < G::ITEMS ? it_ : it_ - G::ITEMS;
+            const int h = it >= G::NHALO ? 1 : 0, p = it - h * G::NHALO;
+            const int ni = p / (HR * HW_), rem = p - ni * (HR * HW_), hy = rem / HW_, hx = rem - hy * HW_;
+            const int gy = y0 + hy - G::HP, gx = x0 + hx - G::HP, n = n0 + ni;
+            const bool ok = n < N && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            xoff[r] = ok ? (ni * Cin + 8 * h) * plane_in + gy * IW + gx : CLHIP_OOB;
+            pos[r][0] = 0;
+            lw[r][0] = (h * G::PLANE_SLOTS + ((ni / G::IPR) * HR + hy) * P + (ni % G::IPR) * HW_ + hx) * 16;
+        }
     }
     float xr[ROUNDS][8];
     unsigned xi[UNPOOL ? ROUNDS : 1][8];
@@ -179,20 +194,22 @@ __device__ __forceinline__ void bs_conv_body(
     auto store_chunk = [&](int buf) {
         if (BS_ABL & 4) return;
 #pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-            float v[8];
+        for (int r = 0; r < ROUNDS; ++r)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if constexpr (UNPOOL) v[e] = xi[r][e] == (unsigned)pos[r] ? xr[r][e] : 0.f;     // max_pool2d backward (+ ReLU: dead code 4)
-                else v[e] = xr[r][e];
+            for (int p = 0; p < PX; ++p) {
+                float v[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    if constexpr (UNPOOL) v[e] = xi[r][e] == (unsigned)pos[r][p] ? xr[r][e] : 0.f; // max_pool2d backward (+ ReLU: dead code 4)
+                    else v[e] = xr[r][e];
+                }
+                clhip_u32x4 q0, q1, q2;
+                bs_split8(v, q0, q1, q2);
+                unsigned char* d = lds + buf * G::BUF_BYTES + lw[r][p];
+                *reinterpret_cast<clhip_u32x4*>(d) = q0;
+                *reinterpret_cast<clhip_u32x4*>(d + 2 * G::PLANE_BYTES) = q1;
+                *reinterpret_cast<clhip_u32x4*>(d + 4 * G::PLANE_BYTES) = q2;
             }
-            clhip_u32x4 q0, q1, q2;
-            bs_split8(v, q0, q1, q2);
-            unsigned char* d = lds + buf * G::BUF_BYTES + lw[r];
-            *reinterpret_cast<clhip_u32x4*>(d) = q0;
-            *reinterpret_cast<clhip_u32x4*>(d + 2 * G::PLANE_BYTES) = q1;
-            *reinterpret_cast<clhip_u32x4*>(d + 4 * G::PLANE_BYTES) = q2;
-        }
     };
 
     // ---- this wave's M tiles / N tiles
@@ -463,11 +480,12 @@ __device__ __forceinline__ void bs_conv_body(
 }
 
 // (three blocks per CU — 45 KB of LDS each — where the registers allow: every forward / plain backward-data instance at <= 162, the
-// un-pooling instance of the 32-wide geometry at 168 without spills; its narrower geometries would spill 11 - 12 registers)
+// un-pooling instances at 160 since they stage per window row, stage_map.hpp — per pixel the 32-wide one took 168 and the narrower
+// geometries, at 230, stayed at two blocks)
 template <class G, bool UNPOOL>
 constexpr int bs_blocks_per_cu() {
     // (the 25-tap instances of the narrow geometries would spill 56 - 64 bytes at three blocks per CU)
-    return (3 * 2 * G::BUF_BYTES <= 160 * 1024 && (G::RW == 32 || (!UNPOOL && G::KS == 3))) ? 3 : 2;
+    return (3 * 2 * G::BUF_BYTES <= 160 * 1024 && (G::RW == 32 || G::KS == 3)) ? 3 : 2;
 }
 
 template <class G, int MODE, bool UNPOOL>
@@ -700,6 +718,32 @@ int bs_launch5(const float* in, const clhip_u32x4* wimg, const float* bias, cons
     return bs_launch_geo<BsGeo<16, 8, 1, 2, 2, 1, 5>, MODE, false>(in, wimg, bias, mask_src, out, nullptr, N, Cin, Cout, H, W, relu, s);
 }
 
+// every LDS write of the un-pooling staging loop of pixel block `block`, read off the maps the kernel itself uses (stage_map.hpp)
+template <class G>
+int bs_stage_map(int N, int Cin, int H, int W, int block, int* src, int* pos, int* slot, int cap) {
+    using UM = BsUnpoolMap<G>;
+    const int tiles_x = (W + G::RW - 1) / G::RW, tiles_y = (H + G::RH - 1) / G::RH, groups = (N + G::NI - 1) / G::NI;
+    const long long npb = (long long)tiles_x * tiles_y * groups;
+    if (npb > 0x7fffffffLL) return CLHIP_EINVAL;
+    if (block < 0) return (int)npb;
+    if (block >= npb || !src || !pos || !slot) return CLHIP_EINVAL;
+    int n0, y0, x0, n = 0;
+    bs_tile_origin<G>(block, tiles_x, tiles_y, n0, y0, x0);
+    const int plane_in = (H >> 1) * (W >> 1);
+    for (int it = 0; it < UM::ROUNDS * 256; ++it) {
+        const BsStageItem s = UM::item(it);
+        int ps[2];
+        const int so = bs_unpool_source<G>(s, n0, y0, x0, N, Cin, H, W, ps);
+        for (int p = 0; p < 2; ++p, ++n) {
+            if (n >= cap) continue;
+            src[n] = so >= 0 ? n0 * Cin * plane_in + so : -1;
+            pos[n] = ps[p];
+            slot[n] = UM::slot(s, p);
+        }
+    }
+    return n;
+}
+
 }  // namespace
 
 // shapes this path takes: whole 32-channel k pairs on the input side, whole 64-channel groups on the output side; any H, W >= 4
@@ -900,6 +944,22 @@ int clhip_conv3x3_bs_bwd_data_riders(const float* dy, const uint8_t* idx_u8_or_n
     if (rc) return rc;
     return clhip_internal_bs_conv_u_riders(dy, ws, relu_src, dx, const_cast<uint8_t*>(idx_u8_or_null), idx_u8_or_null != nullptr, N, K, C, H,
                                            W, q, n_jobs, place, riders, as_stream(stream));
+}
+
+// the staging map of one pixel block of an un-pooling backward-data launch (stage_map.hpp: a test hook); host arrays, nothing is launched
+int clhip_internal_stage_map(int kernel, int geo, int N, int Cin, int H, int W, int block, int* src, int* pos, int* slot, int cap) {
+    if (kernel < 0 || kernel > 2) return CLHIP_ENOTSUP;
+    if (N <= 0 || Cin <= 0 || H < 2 || W < 2 || ((H | W) & 1) || cap < 0) return CLHIP_EINVAL;
+    if ((long long)N * Cin * (H >> 1) * (W >> 1) > 0x7fffffffLL) return CLHIP_EINVAL;
+    if (kernel >= 1) return clhip_internal_wino_stage_map(kernel, geo, N, Cin, H, W, block, src, pos, slot, cap);
+    if (Cin < BS_CK || Cin % BS_CK) return CLHIP_EINVAL;
+    switch (geo) {
+        case 0: return bs_stage_map<BsGA32>(N, Cin, H, W, block, src, pos, slot, cap);
+        case 1: return bs_stage_map<BsGB32>(N, Cin, H, W, block, src, pos, slot, cap);
+        case 2: return bs_stage_map<BsGeo<16, 8, 1, 2, 2, 1>>(N, Cin, H, W, block, src, pos, slot, cap);
+        case 3: return bs_stage_map<BsGeo<8, 8, 2, 2, 2, 1>>(N, Cin, H, W, block, src, pos, slot, cap);
+    }
+    return CLHIP_ENOTSUP;
 }
 
 }  // extern "C"

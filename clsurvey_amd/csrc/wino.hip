@@ -32,6 +32,7 @@
 //   wino_wgrad_ps_kernel    weight gradient of layers with few stages per block: 32 x 32 tiles, pixel split, two blocks per CU
 #include "common.hpp"
 #include "weight_images.hpp"
+#include "stage_map.hpp"
 #include <cstdlib>
 
 namespace {
@@ -742,16 +743,37 @@ __device__ __forceinline__ void wino_conv16_body(
                      (size_t)2 * n_chunks * WD_FLOATS * sizeof(float))
         : clhip_rsrc(U + (size_t)kt * n_chunks * W_FLOATS, (size_t)n_chunks * W_FLOATS * sizeof(float));
 
-    // ---- staging units (as above: one instruction each, weights = straight 16-byte copy, activations = one scalar per halo element)
+    // ---- staging units (as above: one instruction each, weights = straight 16-byte copy, activations = one scalar per halo element;
+    //      plain instances (VEC): ONE float4 of an image row per thread and chunk, the zero ring written once — stage_map.hpp)
+    constexpr bool VEC = !UNPOOL;
+    using PM = W16PlainMap<KT2>;
+    static_assert(PM::PLANE == PLANE && PM::CK == WCK, "stage_map.hpp states this kernel's chunk buffer");
     constexpr int W_IT = ADIRECT ? 0 : W_FLOATS / 4 / 256;           // 10
-    constexpr int X_IT = (X_FLOATS + 255) / 256;                     // 7
+    constexpr int X_IT = VEC ? 1 : (X_FLOATS + 255) / 256;           // 7
     constexpr int NU = W_IT + X_IT;
     float4 wv[W_IT ? W_IT : 1];
+    float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);                     // VEC: the item on its way to LDS
     float xr[X_IT];
     unsigned xi[UNPOOL ? X_IT : 1];
     int xoff[X_IT], xcode[UNPOOL ? X_IT : 1];
+    int xvi = 0;                                                     // VEC: first LDS float of the item
+    if constexpr (VEC) {
+        int nb, src;
+        PM::item(tid < PM::ITEMS ? tid : 0, Cin, nb, src, xvi);
+        xoff[0] = (tid < PM::ITEMS && n0 + nb < N) ? src * 4 : CLHIP_OOB;
+        // the ring of both chunk buffers: zero for good (the items write interior floats only)
 #pragma unroll
-    for (int j = 0; j < X_IT; ++j) {
+        for (int j = 0; j < (PM::RING + 255) / 256; ++j) {
+            const int r = tid + 256 * j;
+            if (256 * (j + 1) <= PM::RING || r < PM::RING) {
+                const int o = WOFF + PM::ring(r);
+                lds[o] = 0.f;
+                lds[BUF + o] = 0.f;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < (VEC ? 0 : X_IT); ++j) {
         const int e = tid + 256 * j;
         xoff[j] = CLHIP_OOB;
         if (e < X_FLOATS) {
@@ -780,7 +802,7 @@ __device__ __forceinline__ void wino_conv16_body(
                 xr[j] = clhip_buf_load(rs_x, xoff[j] != CLHIP_OOB ? xoff[j] * 4 : CLHIP_OOB, xb * 4);
                 xi[j] = clhip_buf_load_u8(rs_i, xoff[j], xb);
             } else {
-                xr[j] = clhip_buf_load(rs_x, xoff[j], xb * 4);
+                xv = clhip_buf_load4(rs_x, xoff[0], xb * 4);
             }
         }
     };
@@ -791,9 +813,12 @@ __device__ __forceinline__ void wino_conv16_body(
         } else {
             const int j = u - W_IT;
             float* xs = lds + bo + WOFF;
-            if (256 * (j + 1) <= X_FLOATS || tid + 256 * j < X_FLOATS) {
-                if constexpr (UNPOOL) xs[tid + 256 * j] = ((int)xi[j] == xcode[j]) ? xr[j] : 0.f;
-                else xs[tid + 256 * j] = xr[j];
+            if constexpr (VEC) {
+                if (PM::ITEMS == 256 || tid < PM::ITEMS) {
+                    xs[xvi] = xv.x; xs[xvi + 1] = xv.y; xs[xvi + 2] = xv.z; xs[xvi + 3] = xv.w;
+                }
+            } else if (256 * (j + 1) <= X_FLOATS || tid + 256 * j < X_FLOATS) {
+                xs[tid + 256 * j] = ((int)xi[j] == xcode[j]) ? xr[j] : 0.f;
             }
         }
     };
@@ -1022,31 +1047,36 @@ __device__ __forceinline__ void wino_conv16g_body(
         clhip_rsrc(U + (size_t)((Cout + WKT - 1) / WKT) * (Cin / WCK) * W_FLOATS + (size_t)kt * n_chunks * WD_FLOATS,
                    (size_t)n_chunks * WD_FLOATS * sizeof(float));
 
-    constexpr int X_IT = (X_FLOATS + 255) / 256;
+    // Staging items: a halo element each — or, un-pooling, a pooled window of a (channel, entity) plane each: one value + one code
+    // loaded, the window's four pixels written (stage_map.hpp).
+    using UM = W16gUnpoolMap<TC, TR, EROWS>;
+    static_assert(UM::PLANE == PLANE && UM::PW == PW && UM::PRE == PRE, "stage_map.hpp states this kernel's chunk buffer");
+    constexpr int X_ITEMS = UNPOOL ? UM::ITEMS : X_FLOATS;
+    constexpr int X_IT = (X_ITEMS + 255) / 256;
     struct Stage {                                                    // the halo planes of one chunk on their way from global memory to LDS
         float4 wv[1];                                                 // unused: see `ab` in compute()
         float xr[X_IT];
         unsigned xi[UNPOOL ? X_IT : 1];
     };
-    int xoff[X_IT], xcode[UNPOOL ? X_IT : 1];
+    int xoff[X_IT];
+    int xa[UNPOOL ? X_IT : 1][4], xp[UNPOOL ? X_IT : 1][4];          // un-pooling: LDS index and window position of the item's four pixels
 #pragma unroll
     for (int j = 0; j < X_IT; ++j) {
         const int e = tid + 256 * j;
         xoff[j] = CLHIP_OOB;
-        if (e < X_FLOATS) {
+        if constexpr (UNPOOL) {
+            const W16gStageItem it = UM::item(e < X_ITEMS ? e : 0);
+            const int so = UM::source(it, v0, w0, tiles_h, N, Cin, H, W);
+            if (e < X_ITEMS && so >= 0) xoff[j] = so;                                              // ELEMENT offset
+#pragma unroll
+            for (int p = 0; p < 4; ++p) { xa[j][p] = it.idx[p]; xp[j][p] = it.pos[p]; }
+        } else if (e < X_FLOATS) {
             const int cl = e / PLANE, rem = e - cl * PLANE;
             const int col = rem % PW, rr = rem / PW;
             const int row = rr % PRE, v = v0 + rr / PRE;
             const int nn = v / tiles_h, g = v - nn * tiles_h;
             const int h = g * 2 * EROWS - 1 + row, w = w0 - 1 + col;
-            if (nn < N && h >= 0 && h < H && w >= 0 && w < W) {
-                if constexpr (UNPOOL) {
-                    xoff[j] = ((nn - nb0) * Cin + cl) * plane_in + (h >> 1) * Wi + (w >> 1);       // ELEMENT offset
-                    xcode[j] = ((h & 1) << 1) | (w & 1);
-                } else {
-                    xoff[j] = (((nn - nb0) * Cin + cl) * plane_in + h * W + w) * 4;
-                }
-            }
+            if (nn < N && h >= 0 && h < H && w >= 0 && w < W) xoff[j] = (((nn - nb0) * Cin + cl) * plane_in + h * W + w) * 4;
         }
     }
     auto load_chunk = [&](int chunk, Stage& st) {
@@ -1066,9 +1096,11 @@ __device__ __forceinline__ void wino_conv16g_body(
         float* xs = lds + bo;
 #pragma unroll
         for (int j = 0; j < X_IT; ++j)
-            if (256 * (j + 1) <= X_FLOATS || tid + 256 * j < X_FLOATS) {
-                if constexpr (UNPOOL) xs[tid + 256 * j] = ((int)st.xi[j] == xcode[j]) ? st.xr[j] : 0.f;
-                else xs[tid + 256 * j] = st.xr[j];
+            if (256 * (j + 1) <= X_ITEMS || tid + 256 * j < X_ITEMS) {
+                if constexpr (UNPOOL) {
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) xs[xa[j][p]] = ((int)st.xi[j] == xp[j][p]) ? st.xr[j] : 0.f;
+                } else xs[tid + 256 * j] = st.xr[j];
             }
     };
 
@@ -1132,7 +1164,9 @@ __device__ __forceinline__ void wino_conv16g_body(
         // 4 - 13 % FASTER on every instance that stages plain activations (forward, backward-data without a fused un-pool: wide_VGG9
         // 359 -> 311, 188 -> 166 us) and 4 - 5 % SLOWER on the instances that rebuild the un-pooled gradient while staging (more VALU in
         // front of the burst), so those run without it (round 4, per instance: profiles/r04_w16g_priority_variants.txt; what matters is
-        // the fence, the s_setprio pair costs nothing).
+        // the fence, the s_setprio pair costs nothing).  Re-measured with the un-pooling instances staging per window (fewer loads and
+        // staging registers in front of the burst): the step with the fence on them is not distinguishable from the step without
+        // (profiles/unpool_once_ab.json, head_fenced against head), so they stay unfenced.
         constexpr bool FENCED = !UNPOOL;
         if constexpr (FENCED) {
             __builtin_amdgcn_sched_barrier(0);
@@ -1698,7 +1732,63 @@ int launch_wino(const float* in, const float* U, const float* bias, const float*
     return 0;
 }
 
+// every LDS write of the un-pooling staging loop of pixel block `block` of launch_wino's 16-tile launch (stage_map.hpp)
+template <int TC, int TR, int EROWS>
+int wino16g_stage_map(int N, int Cin, int H, int W, int block, int* src, int* pos, int* slot, int cap) {
+    using UM = W16gUnpoolMap<TC, TR, EROWS>;
+    const int tiles_w = ((W + 1) / 2 + TC - 1) / TC, tiles_h = ((H + 1) / 2 + EROWS - 1) / EROWS;
+    const long long npb = (((long long)N * tiles_h + UM::NE - 1) / UM::NE) * tiles_w;
+    if (npb > 0x7fffffffLL) return CLHIP_EINVAL;
+    if (block < 0) return (int)npb;
+    if (block >= npb || !src || !pos || !slot) return CLHIP_EINVAL;
+    const int bw = block % tiles_w, v0 = (block / tiles_w) * UM::NE, nb0 = v0 / tiles_h, w0 = bw * 2 * TC;       // as wino_conv16g_body
+    int n = 0;
+    for (int e = 0; e < UM::ITEMS; ++e) {
+        const W16gStageItem it = UM::item(e);
+        const int so = UM::source(it, v0, w0, tiles_h, N, Cin, H, W);
+        for (int p = 0; p < 4; ++p, ++n) {
+            if (n >= cap) continue;
+            src[n] = so >= 0 ? nb0 * Cin * (H >> 1) * (W >> 1) + so : -1;
+            pos[n] = it.pos[p];
+            slot[n] = it.idx[p];
+        }
+    }
+    return n;
+}
+
 }  // namespace
+
+// every LDS write of the plain 8 x 8 staging of image group `block` of wino_conv16_kernel<MODE, false, KT2> (stage_map.hpp)
+template <int KT2>
+static int wino16_plain_stage_map(int N, int Cin, int block, int* src, int* pos, int* slot, int cap) {
+    using PM = W16PlainMap<KT2>;
+    const int n_grp = (N + KT2 - 1) / KT2;
+    if (block < 0) return n_grp;
+    if (block >= n_grp || !src || !pos || !slot) return CLHIP_EINVAL;
+    const int n0 = block * KT2;                                       // as wino_conv16_body
+    int n = 0;
+    auto put = [&](int s_, int q) { if (n < cap) { src[n] = s_; pos[n] = -1; slot[n] = q; } ++n; };
+    for (int f = 0; f < PM::ITEMS; ++f) {
+        int nb, so, idx;
+        PM::item(f, Cin, nb, so, idx);
+        for (int e = 0; e < 4; ++e) put(n0 + nb < N ? n0 * Cin * 64 + so + e : -1, idx + e);
+    }
+    for (int r = 0; r < PM::RING; ++r) put(-1, PM::ring(r));
+    return n;
+}
+
+int clhip_internal_wino_stage_map(int kernel, int geo, int N, int Cin, int H, int W, int block, int* src, int* pos, int* slot, int cap) {
+    if (Cin % WCK || Cin < 16) return CLHIP_EINVAL;
+    if (kernel == 2) {
+        if (H != 8 || W != 8) return CLHIP_EINVAL;
+        if (geo == 0) return wino16_plain_stage_map<1>(N, Cin, block, src, pos, slot, cap);
+        if (geo == 1) return wino16_plain_stage_map<2>(N, Cin, block, src, pos, slot, cap);
+        return CLHIP_ENOTSUP;
+    }
+    if (geo == 0) return wino16g_stage_map<8, 2, 4>(N, Cin, H, W, block, src, pos, slot, cap);
+    if (geo == 1) return wino16g_stage_map<4, 4, 4>(N, Cin, H, W, block, src, pos, slot, cap);
+    return CLHIP_ENOTSUP;
+}
 
 // shapes this path takes: channel counts in whole chunks; even H, W (2x2 output tiles, 8-byte stores), or odd maps 9..16 wide
 // through the 16-tile kernel's row-packed geometry (no fused pooling there: callers pass pool_idx / unpool only for even maps)

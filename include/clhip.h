@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 /* The library is built with -fvisibility=hidden: the prototypes of this header are its whole dynamic symbol table (the
- * cross-translation-unit helpers of csrc/common.hpp stay inside the .so). */
+ * cross-translation-unit helpers of csrc/common.hpp stay inside the .so; one test hook, clhip_internal_stage_map, is exported from
+ * csrc/stage_map.hpp and is not part of this API). */
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility push(default)
 #define CLHIP_VISIBILITY_PUSHED 1
