@@ -109,6 +109,8 @@ SIGNATURES = {
     "clhip_conv2d_s2d_bwd_weight": (_i, [_p, _p, _p, _p] + [_i] * 8 + [_p, _z, _p]),
     "clhip_imm_merge": (_i, [_p, _p, _p, _i, _z, _p, _p]),
     "clhip_lwf_loss": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p]),
+    "clhip_lwf_loss_wide_ws": (_z, [_i, _i]),
+    "clhip_lwf_loss_wide": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _z, _p]),
     "clhip_packnet_finetune_mask": (_i, [_p, _z, _i, _p]),
     "clhip_packnet_kth_ws": (_z, []),
     "clhip_packnet_kth_abs": (_i, [_p, _p, _z, _i, _z, _p, _p, _z, _p]),

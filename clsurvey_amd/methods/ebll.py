@@ -11,7 +11,7 @@ Two stages per task (method.py:822-936):
      (Finetune_SGD_EBLL.py:219-395, 507-518).
 
 Execution: the feature extractor / classifier run on the static-plan executor exactly as for LwF (stacked heads as ONE
-Linear, `clhip_lwf_loss`); the code layers are a side branch off the flattened features (`NetEngine.layer_input`), their
+Linear, `clhip_lwf_loss` or, for heads of any size and up to 64 of them, `clhip_lwf_loss_wide`); the code layers are a side branch off the flattened features (`NetEngine.layer_input`), their
 loss gradient comes back through `clhip_sigmoid_bwd` / `clhip_fc_bwd_data` and is added to the feature gradient inside the
 plan's backward (`clhip_net_set_input_grad`).  Stage 1 runs the (frozen) feature extractor forward-only on the executor
 and the small autoencoder + classifier tail on the autograd bridges.

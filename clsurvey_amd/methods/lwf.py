@@ -4,8 +4,9 @@ The reference stacks one Linear head per task at the end of `model.classifier` (
 module from index `last_layer_name` on to the same shared features) and trains with
     total = CrossEntropy(new head) + lambda * sum_old distillation(old head, frozen previous model)   (main_LWF.py:184-202).
 Here the stacked heads run as ONE Linear: their weights (and biases) are laid out back to back in the parameter arena,
-the plan executor sees a [sum of head sizes]-way layer, and clhip_lwf_loss turns the side-by-side logits + the teacher's
-logits into the loss and d loss / d logits in one launch.  The teacher forward is one plan execution on its own arena.
+the plan executor sees a [sum of head sizes]-way layer, and clhip_lwf_loss (heads that are multiples of 4, at most 32 of
+them: one launch) or clhip_lwf_loss_wide (any head size, up to 64 heads: rows spread over the GPU) turns the side-by-side
+logits + the teacher's logits into the loss and d loss / d logits.  The teacher forward is one plan execution on its own arena.
 """
 import copy
 import ctypes as C
@@ -49,9 +50,15 @@ class AlexNet_LwF(nn.Module):
         return outputs
 
 
+LWF_MAX_HEADS = 32          # clhip_lwf_loss (csrc/loss.hip)
+LWF_MAX_HEADS_WIDE = 64     # CLHIP_LWF_MAX_HEADS_WIDE: clhip_lwf_loss_wide (csrc/lwf_wide.hip)
+
+
 def lwf_plan(wrapper):
-    """(layers, params, head_sizes) for NetEngine: conv / shared Linear layers as they are, all heads as ONE Linear whose
-    rows are the heads' rows back to back (arena order: ..., head weights, head biases)."""
+    """(layers, params, head_sizes, drops, runs) for NetEngine: conv / shared Linear layers as they are, all heads as ONE
+    Linear whose rows are the heads' rows back to back (arena order: ..., head weights, head biases).  runs: the two packed
+    runs of the parameter arena (head weights, head biases) that keep heads of any size back to back, or None where every
+    head is a multiple of 4 and there are at most 32 of them: the arena's pad-to-4 slots are back to back already."""
     from ..net import parse_net, conv_geometry
     m = getattr(wrapper, "model", wrapper)          # AlexNet_LwF holds the net in .model, AlexNet_EBLL is the net
     cls = list(m.classifier.children())
@@ -65,27 +72,45 @@ def lwf_plan(wrapper):
     heads = cls[wrapper.last_layer_name:]
     if not heads or any(not isinstance(h, nn.Linear) for h in heads):
         raise NotImplementedError("LwF: the modules from last_layer_name on must be Linear heads")
+    if len(heads) > LWF_MAX_HEADS_WIDE:
+        raise NotImplementedError("LwF: %d heads, the loss kernels take CLHIP_LWF_MAX_HEADS_WIDE = %d"
+                                  % (len(heads), LWF_MAX_HEADS_WIDE))
     feat = heads[0].in_features
-    for h in heads:
-        if (h.out_features * feat) % 4 or h.out_features % 4:
-            raise NotImplementedError("LwF head sizes must be multiples of 4 (arena slots are 16-byte aligned)")
     sizes = [h.out_features for h in heads]
     layers.append(("fc", heads[0].weight, heads[0].bias, feat, sum(sizes), False, False))
     params = [p for _, w, b, *_ in layers[:-1] for p in (w, b)] + [h.weight for h in heads] + [h.bias for h in heads]
-    return layers, params, sizes, drops
+    runs = None
+    if len(heads) > LWF_MAX_HEADS or any((c * feat) % 4 or c % 4 for c in sizes):
+        first = len(params) - 2 * len(heads)
+        runs = [(first, len(heads)), (first + len(heads), len(heads))]
+    return layers, params, sizes, drops, runs
 
 
 class LwfEngine:
     """forward of all heads + LwF loss + backward for one batch."""
 
-    def __init__(self, wrapper, max_batch, in_shape, device="cuda"):
-        layers, params, self.sizes, drops = lwf_plan(wrapper)
-        self.engine = NetEngine(wrapper, max_batch, in_shape, device, layers=layers, params=params, drops=drops)
+    def __init__(self, wrapper, max_batch, in_shape, device="cuda", wide=None):
+        """wide: which loss kernel runs.  None: clhip_lwf_loss for the plans it has always taken (every head a multiple of
+        4, at most 32 heads: same arena, same launches, same bits), clhip_lwf_loss_wide for everything else; True / False
+        force one of them (False with more than 32 heads raises)."""
+        layers, params, self.sizes, drops, runs = lwf_plan(wrapper)
+        if wide is None:
+            wide = runs is not None
+        if not wide and len(self.sizes) > LWF_MAX_HEADS:
+            raise NotImplementedError("LwF: clhip_lwf_loss takes %d heads, this plan has %d" % (LWF_MAX_HEADS, len(self.sizes)))
+        self.wide = bool(wide)
+        self.engine = NetEngine(wrapper, max_batch, in_shape, device, layers=layers, params=params, drops=drops, param_runs=runs)
         self.device = self.engine.device
         self.n_out = sum(self.sizes)
         self._sizes = (C.c_int * len(self.sizes))(*self.sizes)
         self.loss2 = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.dlogits = torch.zeros((max_batch, self.n_out), dtype=torch.float32, device=self.device)
+        self._ws = None
+        if self.wide:
+            need = _lib.lib().clhip_lwf_loss_wide_ws(len(self.sizes), int(max_batch))
+            if need == 0:
+                raise NotImplementedError("LwF: clhip_lwf_loss_wide takes batches of 1..1024 rows")
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
 
     @property
     def arena(self):
@@ -101,11 +126,15 @@ class LwfEngine:
             z = self.engine.forward(x)
         n = x.shape[0]
         dl = self.dlogits[:n]
-        check(_lib.lib().clhip_lwf_loss(
-            z.data_ptr(), y.data_ptr(), teacher_logits.data_ptr() if teacher_logits is not None else None, self._sizes,
-            len(self.sizes), n, self.n_out, teacher_logits.shape[1] if teacher_logits is not None else 0, float(T),
-            float(reg_lambda), int(backward and teacher_logits is not None), dl.data_ptr(), self.loss2.data_ptr(),
-            stats.data_ptr() if stats is not None else None, torch.cuda.current_stream().cuda_stream), "clhip_lwf_loss")
+        args = (z.data_ptr(), y.data_ptr(), teacher_logits.data_ptr() if teacher_logits is not None else None, self._sizes,
+                len(self.sizes), n, self.n_out, teacher_logits.shape[1] if teacher_logits is not None else 0, float(T),
+                float(reg_lambda), int(backward and teacher_logits is not None), dl.data_ptr(), self.loss2.data_ptr(),
+                stats.data_ptr() if stats is not None else None)
+        stream = torch.cuda.current_stream().cuda_stream
+        if self.wide:
+            check(_lib.lib().clhip_lwf_loss_wide(*args, self._ws.data_ptr(), self._ws.numel(), stream), "clhip_lwf_loss_wide")
+        else:
+            check(_lib.lib().clhip_lwf_loss(*args, stream), "clhip_lwf_loss")
         if backward:
             self.engine.backward(x, dl)
         return self.loss2

@@ -1,7 +1,7 @@
 """ParamArena + NetEngine: the MI355X execution model for a VGG-style net.
 
 * ParamArena lays all parameters of a model out in ONE contiguous fp32 HBM buffer (16-byte
-  aligned slots, module order) and re-points every nn.Parameter's .data / .grad at views of it.
+  aligned slots, module order; `runs` packs chosen neighbours back to back) and re-points every nn.Parameter's .data / .grad at views of it.
   The Parameter OBJECTS are untouched, so the reference's `reg_params` dict (keyed by Parameter
   identity, pickled with the model: EWC/main_EWC.py:160-232) keeps working.  Every optimizer /
   importance update then is a single HBM-bound kernel over the arena instead of ~8 eager ops
@@ -37,16 +37,31 @@ class ParamArena:
             return None
         return a
 
-    def __init__(self, params, device=None):
+    def __init__(self, params, device=None, runs=None):
+        """runs (optional): [(first_index, count)] ranges of consecutive entries of params that are laid out back to back
+        with no per-slot padding (LwF's stacked heads of any size: the plan reads a run as ONE tensor at the offset of its
+        first parameter).  A run starts on a 16-byte boundary and its total is padded to 4 floats; inside it the slots are
+        only 4-byte aligned.  runs=None: every slot padded to 4 floats."""
         self.params = list(params)
         if device is None:
             device = self.params[0].device
         self.device = torch.device(device)
+        packed = [False] * len(self.params)          # True: the next slot follows without padding
+        last = 0
+        for first, count in sorted(runs or []):
+            if first < last or count < 1 or first + count > len(self.params):
+                raise ValueError("ParamArena: runs must be disjoint ranges of the parameter list")
+            for i in range(first, first + count - 1):
+                packed[i] = True
+            last = first + count
+        self.runs = [tuple(r) for r in runs] if runs else None
         self.offsets = []
         off = 0
-        for p in self.params:
+        for p, joined in zip(self.params, packed):
             self.offsets.append(off)
-            off += _pad4(p.numel())
+            off += p.numel()
+            if not joined:                           # a slot of its own, or the last of a run: the total is padded to 4 floats
+                off = _pad4(off)
         self.numel = off
         self.theta = torch.zeros(off, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros(off, dtype=torch.float32, device=self.device)
@@ -174,10 +189,10 @@ def conv_geometry(m):
 class NetEngine:
     LOSS = {"ce_mean": 0, "ce_sum": 1, "mse_sum_zero": 2}
 
-    def __init__(self, model, max_batch, in_shape, device="cuda", layers=None, params=None, drops=None):
+    def __init__(self, model, max_batch, in_shape, device="cuda", layers=None, params=None, drops=None, param_runs=None):
         """layers / params (optional): an explicit plan [(kind, weight, bias, cin, cout, relu, pool)] and the parameter
         order of the arena, for models whose module tree is not plain VGGSlim (e.g. LwF's stacked heads run as ONE
-        Linear over head parameters laid out back to back)."""
+        Linear over head parameters laid out back to back).  param_runs: ParamArena's packed runs."""
         self.model = model
         self.device = torch.device(device)
         self.drops, self.bns = {}, {}
@@ -192,7 +207,7 @@ class NetEngine:
             self.drops = dict(drops or {})
         if any(sp[2] is None for sp in specs):
             raise NotImplementedError("NetEngine: layers without bias")
-        self.arena = ParamArena(list(model.parameters()) if params is None else list(params), self.device)
+        self.arena = ParamArena(list(model.parameters()) if params is None else list(params), self.device, runs=param_runs)
         descs = (LayerDesc * len(specs))()
         for d, sp in zip(descs, specs):
             kind, w, b, cin, cout, relu, pool = sp[:7]

@@ -212,6 +212,29 @@ int clhip_mse_zero_sum(const float* logits, size_t n, float* dlogits, float* los
 int clhip_lwf_loss(const float* logits, const int64_t* labels_i64, const float* teacher, const int* head_sizes, int n_heads,
                    int N, int ld, int ld_teacher, float T, float reg_lambda, int distill, float* dlogits, float* loss_out2,
                    double* stats, void* stream);
+/* The same objective (LwF/main_LWF.py:47-76, 184-202), the same contract and the same fp32 formulas for up to
+ * CLHIP_LWF_MAX_HEADS_WIDE heads of any size (clhip_lwf_loss takes 32 heads and is one block with one thread per row by
+ * design: a 10 x 20 layout on one CU).  Rows are spread over the GPU: one wave per row, 4 rows per block, the lanes of a wave
+ * across the columns of a head (dword accesses only: no row, head or ld is assumed 16-byte aligned); each row leaves
+ * (task, distillation, hit) in ws and a second one-block launch sums the rows in a fixed order (f64), so the result does not
+ * depend on scheduling; no atomics.  loss_out2, stats, distill = 0, the zeros past the last head, the lowest-index arg-max rule
+ * and "a single head needs no teacher" are those of clhip_lwf_loss.  ws: clhip_lwf_loss_wide_ws(n_heads, N) bytes (a multiple
+ * of 16; 0 for n_heads outside 1..64 or N outside 1..1024), 4-byte aligned.
+ * Refusals, in the order they are checked (a refused call launches nothing and writes nothing):
+ *   CLHIP_EINVAL  logits, labels_i64, head_sizes, dlogits, loss_out2 or ws is NULL
+ *   CLHIP_EINVAL  n_heads outside 1..CLHIP_LWF_MAX_HEADS_WIDE
+ *   CLHIP_EINVAL  a head size <= 0
+ *   CLHIP_EINVAL  the heads together wider than ld
+ *   CLHIP_EINVAL  distill with more than one head and the old heads together wider than ld_teacher
+ *   CLHIP_EINVAL  N outside 1..1024
+ *   CLHIP_EINVAL  T <= 0 (or NaN)
+ *   CLHIP_EINVAL  distill with more than one head and teacher NULL
+ *   CLHIP_ENOSPC  ws_bytes < clhip_lwf_loss_wide_ws(n_heads, N)                                                          */
+#define CLHIP_LWF_MAX_HEADS_WIDE 64          /* = CLHIP_MAX_TASKS */
+size_t clhip_lwf_loss_wide_ws(int n_heads, int N);
+int clhip_lwf_loss_wide(const float* logits, const int64_t* labels_i64, const float* teacher, const int* head_sizes, int n_heads,
+                        int N, int ld, int ld_teacher, float T, float reg_lambda, int distill, float* dlogits, float* loss_out2,
+                        double* stats, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ penalised optimizers
  * Weight_Regularized_SGD.step — EWC/train_EWC.py:23-86 == MAS/train_MAS.py:32-95.
